@@ -8,13 +8,20 @@ N > 1 GPUs -- the one RCCL all-gather of the decoded images.  N=1 runs BASELINE.
 point of the same family).  Synthetic data, synthetic weights of the exact architecture (no
 checkpoints / datasets in the environment).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step if --dump-outputs is
+given, and prints the result line (`value`, `ms_per_step` ...).  --full adds the secondary figures below, each
+outside the timed region: `roofline` and the per-kernel figures (one more, instrumented batch), `stage_ms_per_batch`
+(one more batch) and `cpu_baseline` (the CPU oracle on the host cores).
+--dump-outputs DIR: DIR/images.npy (the decoded images every rank receives, [global batch, 3, H, W]) and
+DIR/latents.npy (rank 0's final latents), float32; an array above 32 MB is written as a fixed, seeded sample of its
+elements (see dump_outputs).  Inputs and synthetic weights are seeded, so two builds can be compared array for array.
 N > 1 without WORLD_SIZE in the environment: this process starts the N ranks itself (one per GPU,
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`), relays rank 0's JSON line
 and fails loudly -- non-zero exit, the ranks' stderr -- on a rank failure or after --launch-timeout seconds instead of
 hanging; under torch.distributed.run (WORLD_SIZE set, what the driver does) it is simply one of the ranks.
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live inside this process with HIP-event pairs
+Prints ONE JSON line (rank 0).  With --full, `roofline` is measured live inside this process with HIP-event pairs
 around every launch of every kernel family on its launch stream (libpfd_hip's pfd_prof_*): with
 --no-graph during the timed region itself; by default the timed region replays hipGraphs (events cannot
 be captured), so the same kernels, shapes and data path are timed on ONE more, eagerly launched, batch
@@ -141,6 +148,23 @@ def launch_ranks(args, argv):
     return 0
 
 
+DUMP_MAX_BYTES = 32 << 20     # per array; two arrays stay under 64 MB
+
+
+def dump_outputs(outdir, arrays):
+    """write each tensor as <outdir>/<name>.npy in float32.  An array above DUMP_MAX_BYTES is written as a fixed sample
+    of its flattened elements: the sorted indices numpy.random.default_rng(0).choice(size, DUMP_MAX_BYTES // 4,
+    replace=False) -- the same positions in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > DUMP_MAX_BYTES:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_BYTES // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -158,8 +182,13 @@ def main():
                          "unconditional context")
     ap.add_argument("--per-sample-image", action="store_true",
                     help="one reference image (one SeeCoder encode) per sample instead of one per batch (SURVEY 8(d))")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prof", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures (roofline / per-kernel figures, per-stage split, CPU baseline); "
+                         "a plain run only times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
+    ap.add_argument("--no-prof", action="store_true", help="with --full: no roofline / per-kernel figures")
     ap.add_argument("--no-graph", action="store_true", help="launch the DDIM loop eagerly instead of one hipGraph")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help='"nccl" is RCCL on ROCm; gloo: CPU tests')
     ap.add_argument("--launch-timeout", type=float, default=float(os.environ.get("PFD_BENCH_TIMEOUT", "3000")),
@@ -169,6 +198,10 @@ def main():
                     help="TEST ONLY: per-sample stand-ins for the GPU compute (tests/stubs.py) on the CPU, to drive the "
                          "launcher / sharding / collective path without a GPU (tests/test_distributed_cpu.py)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_prof = args.no_cpu_baseline = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args, sys.argv[1:]))
     if args.config == "c5":
@@ -243,9 +276,9 @@ def main():
     stage_ms = {}
 
     def step(i, gather=True, timings=None):
-        img, _ = pipe.generate(image, n_global, args.height, args.width, steps=args.ddim_steps, scale=args.scale,
-                               eta=0.0, seed=20 + i, gather=gather, control=control, uncond=uncond, timings=timings)
-        return img
+        """(images, latents) of one batch"""
+        return pipe.generate(image, n_global, args.height, args.width, steps=args.ddim_steps, scale=args.scale,
+                             eta=0.0, seed=20 + i, gather=gather, control=control, uncond=uncond, timings=timings)
 
     for i in range(args.warmup):
         step(i)
@@ -264,11 +297,13 @@ def main():
     if prof_live:
         binding.prof_enable(True)
     t0 = time.perf_counter()
-    out = None
+    out = latents = None
     for i in range(args.steps):
-        out = step(100 + i)
+        out, latents = step(100 + i)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"images": out, "latents": latents})
     prof, prof_steps, prof_where = [], args.steps, "timed region (eager launches)"
     if prof_live:
         prof = binding.prof_read()
@@ -283,7 +318,7 @@ def main():
         pipe.enable_graph(True)
     if binding is not None:
         binding.prof_enable(False)
-    if rank == 0:   # per-stage split of one more (graph-replayed) batch, outside the timed region
+    if rank == 0 and args.full:   # per-stage split of one more (graph-replayed) batch, outside the timed region
         step(998, gather=False, timings=stage_ms)
     dt = max_over_ranks(dt, world, device=dev)     # a step is as slow as its slowest rank
     assert out is not None and out.shape[0] == n_global and bool(torch.isfinite(out).all())
@@ -378,7 +413,8 @@ def main():
                                         "by_bucket": {b["name"]: int(b["launches"] / prof_steps) for b in prof}}
             res["instrumented_kernel_ms_per_step"] = tot / prof_steps          # eager, before the normalisation
             res["launch_mode"] = "eager" if args.no_graph else "hipGraph (DDIM loop)"
-        res["stage_ms_per_batch"] = {k: round(v, 2) for k, v in stage_ms.items()}
+        if args.full:
+            res["stage_ms_per_batch"] = {k: round(v, 2) for k, v in stage_ms.items()}
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(net, args.height, args.width, ddim_real, args.scale)
         print(json.dumps(res))

@@ -148,6 +148,26 @@ def test_bench_starts_its_own_ranks():
     assert res["ms_per_step"] >= 40.0            # the slowest rank's time (rank 1 sleeps 40 ms per batch)
 
 
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs DIR writes the last timed step's images (all ranks' samples) and rank 0's latents as float32 .npy,
+    the same arrays from run to run; a plain run's line has the headline fields and none of the --full figures"""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = _bench("--gpus", "2", "--steps", "3", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-3000:]
+        res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert res["steps"] == 3 and res["ms_per_step"] > 0 and res["value"] > 0
+        for k in ("metric", "unit", "higher_is_better", "dtype"):
+            assert k in res, k
+        assert "cpu_baseline" not in res and "roofline" not in res and "stage_ms_per_batch" not in res
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("images", "latents")})
+    assert dumps[0]["images"].shape == (8, 3, 64, 96) and dumps[0]["latents"].shape == (4, 4, 8, 12)
+    for n, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.array_equal(a, dumps[1][n]), n
+
+
 def test_bench_launcher_fails_loudly_instead_of_hanging():
     """a job whose ranks cannot finish in time is killed and reported (exit code 124), not waited for forever"""
     r = _bench("--gpus", "2", "--launch-timeout", "0.5", timeout=120)
