@@ -34,7 +34,7 @@ extern "C" {
 #define PFD_ESHAPE (-2)   /* shape outside what the kernels are built for           */
 #define PFD_ELAUNCH (-3)  /* hipGetLastError() != hipSuccess after the launch       */
 
-#define PFD_ABI_VERSION 9
+#define PFD_ABI_VERSION 10
 
 typedef void* pfd_stream_t; /* hipStream_t */
 
@@ -397,6 +397,48 @@ int pfd_add_rowvec_lnstats_f16(const void* x, int64_t ldx, const void* v, void* 
  * The request front-end hands the bytes to the client without a float image ever leaving the device. */
 int pfd_image_u8_f16(const void* x, void* y, int64_t n, float mul, float add, int32_t f16_image,
                      pfd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Request front door (ABI 10): packed uint8 pictures [B, H, W, C], C in {1, 3}, to the model's input -- what the
+ * reference does on the host in front of the model, `imctl.resize([w, h], Image.Resampling.BICUBIC)` (app.py:232)
+ * and `tvtrans.ToTensor()(im)[None].to(device).to(self.dtype)` (app.py:234,244).
+ *
+ * The resize is Pillow's ImagingResample for 8 bits per channel, bicubic (a = -0.5), byte for byte.  Per axis with
+ * in != out, horizontal first: scale = in / out, support = 2 * max(scale, 1) (doubles); output sample xx has
+ * center = (xx + 0.5) * scale, window [xmin, xmax) = [max((int)(center - support + 0.5), 0),
+ * min((int)(center + support + 0.5), in)), coefficients bicubic((x + xmin - center + 0.5) / max(scale, 1)) divided by
+ * their sum and rounded half away from zero at PFD_IMG_PRECISION_BITS = 32 - 8 - 2 bits.  A sample is
+ *     clamp((2^21 + sum_x src[xmin + x] * kk[x]) >> 22, 0, 255)      int32, arithmetic shift.
+ * The horizontal pass writes a rounded, clamped uint8 picture [B, Hin, Wout, C]; the vertical pass reads THAT.
+ * The tables are built by the caller (lib/image_io.py pillow_bicubic_taps) and passed as device pointers:
+ * int32 kk[out][ktaps] (rows padded with zeros), int32 xmin[out], int32 klen[out] (<= ktaps <= 66).  Indices taken
+ * from them are clamped to the picture, so a wrong table gives wrong pixels, never an access outside src.
+ * ToTensor: (float)u8 / 255.0f, correctly rounded, then one rounding to f16 where the output is f16.
+ *
+ * Bounds: B >= 1; sides 1 ... 8192; in <= 16 * out per axis (64 taps at 1024 -> 64), enlarging unbounded; at most 2^30
+ * rows and 2^36 pixels per call.  Anything else is PFD_ESHAPE with nothing launched; null pointers are PFD_EINVAL.
+ * RGBA is out of scope (Image.resize premultiplies alpha).  The library allocates nothing: the caller owns the
+ * intermediate picture.
+ * ---------------------------------------------------------------------------------- */
+#define PFD_IMG_PRECISION_BITS 22
+#define PFD_IMG_U8 0        /* uint8 [B, H, W, C]                       */
+#define PFD_IMG_NCHW_F16 1  /* f16 [B, C, H, W]: ctx_encode / prepare_hint input of an fp16 model */
+#define PFD_IMG_NCHW_F32 2  /* f32 [B, C, H, W]                         */
+#define PFD_IMG_NHWC_F16 3  /* f16 [B, H, W, C]: the product path's own layout */
+
+/* PFD_OK iff the two passes take [B, Hin, Win, C] -> [B, Hout, Wout, C] (the bounds above); launches nothing. */
+int pfd_image_resample_check(int32_t B, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout, int32_t C);
+
+/* Horizontal pass: src uint8 [B, H, Win, C] -> dst uint8 [B, H, Wout, C]. */
+int pfd_image_resample_h_u8(const void* src, void* dst, int32_t B, int32_t H, int32_t Win, int32_t Wout, int32_t C,
+                            const int32_t* kk, const int32_t* xmin, const int32_t* klen, int32_t ktaps,
+                            pfd_stream_t stream);
+
+/* Vertical (last) pass: src uint8 [B, Hin, W, C] -> dst in the layout out_kind (PFD_IMG_*) with Hout rows.
+ * kk == NULL (Hin == Hout): no resampling -- ToTensor alone, or a copy for PFD_IMG_U8. */
+int pfd_image_resample_v_u8(const void* src, void* dst, int32_t out_kind, int32_t B, int32_t Hin, int32_t Hout,
+                            int32_t W, int32_t C, const int32_t* kk, const int32_t* ymin, const int32_t* klen,
+                            int32_t ktaps, pfd_stream_t stream);
 
 /* y = act(x) elementwise (act in NONE|GELU|RELU|SILU), n f16 elements.  The SiLU in front
  * of every ResBlock emb_layers Linear (openaimodel.py:217-218) applied once to the shared

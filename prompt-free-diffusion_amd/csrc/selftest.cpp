@@ -1052,6 +1052,105 @@ static void run_elementwise() {
   }
 }
 
+// ------------------------------------------------------------------ uint8 picture ingest (image.hip)
+// Pillow's tap table of one axis, restated in doubles (the product builds it in lib/image_io.py)
+struct ImgTaps {
+  std::vector<int32_t> xmin, klen, kk;
+  int ktaps = 0;
+};
+static ImgTaps image_taps(int in, int out) {
+  auto cubic = [](double t) {
+    const double a = -0.5;
+    t = fabs(t);
+    if (t < 1.0) return ((a + 2.0) * t - (a + 3.0)) * t * t + 1;
+    if (t < 2.0) return (((t - 5) * t + 8) * t - 4) * a;
+    return 0.0;
+  };
+  const double scale = (double)in / out, fs = scale > 1.0 ? scale : 1.0, support = 2.0 * fs, ss = 1.0 / fs;
+  ImgTaps t;
+  std::vector<std::vector<int32_t>> rows(out);
+  for (int xx = 0; xx < out; ++xx) {
+    const double center = (xx + 0.5) * scale;
+    const int x0 = std::max((int)(center - support + 0.5), 0), x1 = std::min((int)(center + support + 0.5), in);
+    std::vector<double> k(x1 - x0);
+    double ww = 0;
+    for (int x = 0; x < x1 - x0; ++x) ww += k[x] = cubic((x + x0 - center + 0.5) * ss);
+    for (double& v : k) {
+      if (ww != 0.0) v /= ww;
+      rows[xx].push_back(v < 0 ? (int)(-0.5 + v * (1 << PFD_IMG_PRECISION_BITS)) : (int)(0.5 + v * (1 << PFD_IMG_PRECISION_BITS)));
+    }
+    t.xmin.push_back(x0);
+    t.klen.push_back(x1 - x0);
+    t.ktaps = std::max(t.ktaps, x1 - x0);
+  }
+  t.kk.assign((size_t)out * t.ktaps, 0);
+  for (int xx = 0; xx < out; ++xx) std::copy(rows[xx].begin(), rows[xx].end(), t.kk.begin() + (size_t)xx * t.ktaps);
+  return t;
+}
+
+static void report_bytes(const std::string& name, size_t bad, size_t n) {
+  ++g_total;
+  if (bad) ++g_fail;
+  printf("%s %-58s %zu of %zu values differ\n", bad ? "FAIL" : "ok  ", name.c_str(), bad, n);
+  fflush(stdout);
+}
+
+// one case per pass against a scalar host loop (int32 sums, arithmetic shift, clamp), then ToTensor of the result: exact
+static void run_image_case(int B, int H, int W, int C, int Ho, int Wo) {
+  std::vector<uint8_t> src((size_t)B * H * W * C);
+  for (size_t i = 0; i < src.size(); ++i) src[i] = (i / 7 + i / 31) % 5 == 0 ? (i & 1 ? 255 : 0) : (uint8_t)((i * 2654435761u) >> 13);
+  auto clamp8 = [](int v) { return (uint8_t)std::min(std::max(v, 0), 255); };
+  const ImgTaps th = image_taps(W, Wo), tv = image_taps(H, Ho);
+  std::vector<uint8_t> mid((size_t)B * H * Wo * C), ref((size_t)B * Ho * Wo * C);
+  for (int b = 0; b < B; ++b) for (int y = 0; y < H; ++y) for (int x = 0; x < Wo; ++x) for (int c = 0; c < C; ++c) {
+    int acc = 1 << (PFD_IMG_PRECISION_BITS - 1);
+    for (int t = 0; t < th.klen[x]; ++t) acc += (int)src[(((size_t)b * H + y) * W + th.xmin[x] + t) * C + c] * th.kk[(size_t)x * th.ktaps + t];
+    mid[(((size_t)b * H + y) * Wo + x) * C + c] = clamp8(acc >> PFD_IMG_PRECISION_BITS);
+  }
+  for (int b = 0; b < B; ++b) for (int y = 0; y < Ho; ++y) for (int x = 0; x < Wo; ++x) for (int c = 0; c < C; ++c) {
+    int acc = 1 << (PFD_IMG_PRECISION_BITS - 1);
+    for (int t = 0; t < tv.klen[y]; ++t) acc += (int)mid[(((size_t)b * H + tv.xmin[y] + t) * Wo + x) * C + c] * tv.kk[(size_t)y * tv.ktaps + t];
+    ref[(((size_t)b * Ho + y) * Wo + x) * C + c] = clamp8(acc >> PFD_IMG_PRECISION_BITS);
+  }
+  Dev<uint8_t> dsrc(src), dmid(mid.size()), du8(ref.size());
+  Dev<int32_t> hk(th.kk), hx(th.xmin), hl(th.klen), vk(tv.kk), vx(tv.xmin), vl(tv.klen);
+  Dev<float> df32(ref.size());
+  Dev<h16> df16(ref.size());
+  char tag[96];
+  snprintf(tag, sizeof(tag), "%dx%dx%dx%d -> %dx%d", B, H, W, C, Ho, Wo);
+  int rc = pfd_image_resample_h_u8(dsrc.p, dmid.p, B, H, W, Wo, C, hk.p, hx.p, hl.p, th.ktaps, nullptr);
+  auto gmid = dmid.get();
+  size_t bad = 0;
+  for (size_t i = 0; i < mid.size(); ++i) bad += gmid[i] != mid[i];
+  report_bytes(std::string("image horizontal pass ") + tag + " rc=" + std::to_string(rc), bad + (rc != 0), mid.size());
+  rc = pfd_image_resample_v_u8(dmid.p, du8.p, PFD_IMG_U8, B, H, Ho, Wo, C, vk.p, vx.p, vl.p, tv.ktaps, nullptr);
+  auto gu8 = du8.get();
+  bad = 0;
+  for (size_t i = 0; i < ref.size(); ++i) bad += gu8[i] != ref[i];
+  report_bytes(std::string("image vertical pass ") + tag + " rc=" + std::to_string(rc), bad + (rc != 0), ref.size());
+  rc = pfd_image_resample_v_u8(dmid.p, df32.p, PFD_IMG_NCHW_F32, B, H, Ho, Wo, C, vk.p, vx.p, vl.p, tv.ktaps, nullptr);
+  rc |= pfd_image_resample_v_u8(du8.p, df16.p, PFD_IMG_NCHW_F16, B, Ho, Ho, Wo, C, nullptr, nullptr, nullptr, 0, nullptr);   // ToTensor alone
+  auto g32 = df32.get();
+  auto g16 = df16.get();
+  bad = 0;
+  for (int b = 0; b < B; ++b) for (int c = 0; c < C; ++c) for (int y = 0; y < Ho; ++y) for (int x = 0; x < Wo; ++x) {
+    const float want = (float)ref[(((size_t)b * Ho + y) * Wo + x) * C + c] / 255.0f;
+    const h16 want16 = (h16)want;
+    const size_t i = (((size_t)b * C + c) * Ho + y) * Wo + x;
+    bad += memcmp(&g32[i], &want, 4) != 0;
+    bad += memcmp(&g16[i], &want16, 2) != 0;
+  }
+  report_bytes(std::string("image ToTensor f32 (fused) / f16 (alone) ") + tag + " rc=" + std::to_string(rc), bad + (rc != 0), 2 * ref.size());
+}
+
+static void run_image() {
+  run_image_case(2, 37, 53, 3, 64, 96);     // enlarging: 4 taps, odd row pitch (byte heads and tails), 4-pixel vertical form
+  run_image_case(1, 200, 333, 3, 50, 70);   // shrinking by 4 and 4.8, 1-pixel vertical form (70 % 4 != 0)
+  run_image_case(1, 300, 300, 1, 20, 20);   // one channel, ratio 15
+  const int rc = pfd_image_resample_check(1, 1025, 64, 64, 64, 3);
+  report_bytes("image resample bounds: ratio above 16 is PFD_ESHAPE rc=" + std::to_string(rc), rc != PFD_ESHAPE, 1);
+}
+
 // ------------------------------------------------------------------ bench
 static float time_ms(const std::function<void()>& f, int iters) {
   hipEvent_t a, b;
@@ -1660,6 +1759,11 @@ int main(int argc, char** argv) {
     printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
     return g_fail;
   }
+  if (argc > 1 && !strcmp(argv[1], "--image")) {   // the uint8 picture ingest only
+    run_image();
+    printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
+    return g_fail;
+  }
   if (argc > 1 && !strcmp(argv[1], "--ln")) {
     run_ln_fold_suite();
     printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
@@ -1886,6 +1990,7 @@ int main(int argc, char** argv) {
     run_softmax_case(2, 36864, 0.044f);   // long-row form (N > 16384)
     run_softmax_case(2, 16392, 0.05f);
     run_elementwise();
+    run_image();
     printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
   }
 

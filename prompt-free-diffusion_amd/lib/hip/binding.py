@@ -14,7 +14,7 @@ import os
 _LIB = None
 _LIB_PATH = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "libpfd_hip.so"))
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SILU, ACT_GEGLU = 0, 1, 2, 3, 4
 
@@ -88,6 +88,9 @@ SIGNATURES = {
     "pfd_add_rowvec_lnstats_f16": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "pfd_act_f16": (_i32, [_vp, _vp, _i64, _i32, _vp]),
     "pfd_image_u8_f16": (_i32, [_vp, _vp, _i64, _f32, _f32, _i32, _vp]),
+    "pfd_image_resample_check": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "pfd_image_resample_h_u8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "pfd_image_resample_v_u8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
     "pfd_prof_enable": (_i32, [_i32]),
     "pfd_prof_read": (_i32, [_i32, C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(C.c_double),
                              C.POINTER(C.c_double)]),
@@ -127,6 +130,8 @@ def load():
 class PfdError(RuntimeError):
     pass
 
+
+IMG_U8, IMG_NCHW_F16, IMG_NCHW_F32, IMG_NHWC_F16 = 0, 1, 2, 3
 
 PFD_EINVAL, PFD_ESHAPE, PFD_ELAUNCH = -1, -2, -3
 _ERR = {PFD_EINVAL: "PFD_EINVAL", PFD_ESHAPE: "PFD_ESHAPE", PFD_ELAUNCH: "PFD_ELAUNCH"}

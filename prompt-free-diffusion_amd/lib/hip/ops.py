@@ -647,6 +647,66 @@ def image_u8(x, mul=1.0, add=0.0, f16_image=True):
     return out
 
 
+_TAPS = {}
+_IMG_KIND = {('nchw', torch.float16): _b.IMG_NCHW_F16, ('nchw', torch.float32): _b.IMG_NCHW_F32,
+             ('nhwc', torch.float16): _b.IMG_NHWC_F16, ('u8', torch.uint8): _b.IMG_U8}
+
+
+def _resample_taps(in_size, out_size, device):
+    """device copy of Pillow's tap tables for one axis (lib/image_io.py): (kk, xmin, klen, ktaps).  They depend on
+    (in, out) only: built once on the host and kept in a small bounded cache, like PPE_MLP.features -- so a hipGraph
+    capture never sees a pageable host->device copy, and a table for a new size requested during capture raises"""
+    key = (int(in_size), int(out_size), str(device))
+    hit = _TAPS.get(key)
+    if hit is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"image_from_u8: tap table for a new size {key[0]} -> {key[1]} requested during stream capture")
+        from ..image_io import pillow_bicubic_taps
+        xmin, klen, kk = pillow_bicubic_taps(*key[:2])
+        if len(_TAPS) >= 32:
+            _TAPS.clear()
+        i32 = functools.partial(torch.tensor, dtype=torch.int32)
+        hit = _TAPS[key] = (i32(kk).to(device), i32(xmin).to(device), i32(klen).to(device), len(kk[0]))
+    return hit
+
+
+def image_from_u8(img, size=None, dtype=torch.float16, layout='nchw'):
+    """uint8 picture(s) [H,W,C] | [B,H,W,C] (C in {1, 3}) on the device -> the model's input [B,C,H',W'] in [0, 1]:
+    Pillow's 8-bit bicubic `resize` to size = (H', W') (app.py:232; None: no resize) and torchvision's ToTensor + the
+    cast to `dtype` (fp16 | fp32; app.py:234,244), byte for byte / bit for bit.  layout='nhwc' gives the fp16
+    [B,H',W',C] of the product path, layout='u8' the resized uint8 [B,H',W',C] (Image.resize alone)."""
+    if not (torch.is_tensor(img) and img.dtype == torch.uint8 and img.dim() in (3, 4)):
+        raise ValueError("image_from_u8: a uint8 tensor [H, W, C] or [B, H, W, C] expected")
+    if not img.is_cuda:
+        raise RuntimeError("image_from_u8: input must live on the GPU; the HIP path has no CPU fallback")
+    if layout == 'u8':
+        dtype = torch.uint8
+    kind = _IMG_KIND.get((layout, dtype))
+    if kind is None:
+        raise ValueError(f"image_from_u8: no output {layout!r} / {dtype} (nchw fp16 | fp32, nhwc fp16, u8)")
+    x = (img[None] if img.dim() == 3 else img).contiguous()
+    B, H, W_, Cc = x.shape
+    Ho, Wo = (H, W_) if size is None else (int(size[0]), int(size[1]))
+    lib = _lib()
+    _b.check(lib.pfd_image_resample_check(B, H, W_, Ho, Wo, Cc), "pfd_image_resample_check")
+    if Wo != W_:                                    # horizontal pass first, into a rounded uint8 picture (as Pillow)
+        kk, xmin, klen, ktaps = _resample_taps(W_, Wo, x.device)
+        mid = torch.empty((B, H, Wo, Cc), dtype=torch.uint8, device=x.device)
+        _b.check(lib.pfd_image_resample_h_u8(x.data_ptr(), mid.data_ptr(), B, H, W_, Wo, Cc, kk.data_ptr(),
+                                             xmin.data_ptr(), klen.data_ptr(), ktaps, _stream()),
+                 "pfd_image_resample_h_u8")
+        if Ho == H and kind == _b.IMG_U8:
+            return mid
+        x = mid
+    shape = {_b.IMG_U8: (B, Ho, Wo, Cc), _b.IMG_NHWC_F16: (B, Ho, Wo, Cc)}.get(kind, (B, Cc, Ho, Wo))
+    out = torch.empty(shape, dtype=dtype, device=x.device)
+    kk, ymin, klen, ktaps = _resample_taps(H, Ho, x.device) if Ho != H else (None, None, None, 0)
+    _b.check(lib.pfd_image_resample_v_u8(x.data_ptr(), out.data_ptr(), kind, B, H, Ho, Wo, Cc, _ptr(kk), _ptr(ymin),
+                                         _ptr(klen), ktaps, _stream()),
+             "pfd_image_resample_v_u8")
+    return out
+
+
 def timestep_embedding(t, dim, max_period=10000.0):
     t = t.to(torch.int64).contiguous()
     out = torch.empty((t.shape[0], dim), dtype=torch.float16, device=t.device)

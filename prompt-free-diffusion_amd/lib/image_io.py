@@ -1,0 +1,110 @@
+"""uint8 pictures at the front door: the host half of the device ingest (csrc/image.hip, ops.image_from_u8).
+
+The reference resizes the control picture with Pillow and converts both pictures with torchvision's ToTensor before
+anything reaches the device (app.py:232,234,244).  Here the client hands over the packed uint8 HWC picture; the resize
+(Pillow's 8-bit bicubic, byte for byte) and ToTensor (+ the cast to the model dtype) run as HIP kernels.  This module
+holds what those kernels need from the host and nothing else:
+
+  * `pillow_bicubic_taps`: the fixed-point tap tables of Pillow's ImagingResample for one axis.  Pure Python floats
+    (doubles, as Pillow's C code), no torch, no numpy, no Pillow.
+  * `to_device_u8` / `check_u8_picture`: argument checks of a uint8 picture and its move to the device.
+"""
+
+PRECISION_BITS = 32 - 8 - 2          # Pillow's 8-bit fixed point: coefficients are scaled by 2^22
+MAX_SIDE = 8192                      # bounds of the kernels (include/pfd_hip.h)
+MAX_RATIO = 16
+
+
+def _bicubic(t):
+    """Keys cubic, a = -0.5 (Pillow's bicubic_filter)"""
+    a = -0.5
+    if t < 0.0:
+        t = -t
+    if t < 1.0:
+        return ((a + 2.0) * t - (a + 3.0)) * t * t + 1
+    if t < 2.0:
+        return (((t - 5) * t + 8) * t - 4) * a
+    return 0.0
+
+
+def pillow_bicubic_taps(in_size, out_size):
+    """Tap tables of one axis, in_size -> out_size samples: (xmin, klen, kk).
+
+    Output sample xx = clamp((2^21 + sum_{x < klen[xx]} src[xmin[xx] + x] * kk[xx][x]) >> 22, 0, 255), 32-bit integers,
+    arithmetic shift.  Every row of kk is padded with zeros to the longest row, so len(kk[0]) is the table's pitch.
+    The floating-point steps are Pillow's, in its order, in doubles: support = 2 * max(scale, 1); the window is
+    [trunc(center - support + 0.5), trunc(center + support + 0.5)) clipped to the axis; the coefficients are summed
+    left to right, divided by the sum, and rounded half away from zero at 22 bits."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError("pillow_bicubic_taps: sizes must be positive")
+    scale = in_size / out_size
+    filterscale = scale if scale > 1.0 else 1.0
+    support = 2.0 * filterscale
+    ss = 1.0 / filterscale
+    xmins, klens, rows = [], [], []
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = int(center - support + 0.5)
+        if xmin < 0:
+            xmin = 0
+        xmax = int(center + support + 0.5)
+        if xmax > in_size:
+            xmax = in_size
+        n = xmax - xmin
+        k, ww = [], 0.0
+        for x in range(n):
+            w = _bicubic((x + xmin - center + 0.5) * ss)
+            k.append(w)
+            ww += w                  # (a plain running sum: the built-in sum() compensates since Python 3.12)
+        row = []
+        for w in k:
+            if ww != 0.0:
+                w /= ww
+            row.append(int(-0.5 + w * (1 << PRECISION_BITS)) if w < 0 else int(0.5 + w * (1 << PRECISION_BITS)))
+        xmins.append(xmin)
+        klens.append(n)
+        rows.append(row)
+    ktaps = max(klens)
+    return xmins, klens, [r + [0] * (ktaps - len(r)) for r in rows]
+
+
+def check_u8_picture(x, what, min_side=1):
+    """x: uint8 torch tensor or numpy array [h, w, 3] or [1, h, w, 3].  Raises ValueError; touches no device."""
+    shape, dtype = getattr(x, "shape", None), str(getattr(x, "dtype", ""))
+    if shape is None or not dtype.endswith("uint8"):
+        raise ValueError(f"{what}: a uint8 picture [h, w, 3] expected, got {type(x).__name__} {dtype}")
+    shape = tuple(int(s) for s in shape)
+    if len(shape) == 4 and shape[0] == 1:
+        shape = shape[1:]
+    if len(shape) != 3:
+        raise ValueError(f"{what}: a uint8 picture must be [h, w, 3] or [1, h, w, 3], got {tuple(x.shape)}")
+    if shape[2] != 3:
+        raise ValueError(f"{what}: a uint8 picture must have 3 channels last (RGB, HWC), got {tuple(x.shape)}")
+    if min(shape[:2]) < min_side or max(shape[:2]) > MAX_SIDE:
+        raise ValueError(f"{what}: picture sides must be in [{min_side}, {MAX_SIDE}], got {shape[0]} x {shape[1]}")
+    return shape
+
+
+def check_resize(in_hw, out_hw, what):
+    """the kernels shrink an axis by at most MAX_RATIO (64 taps); enlarging is unbounded within MAX_SIDE"""
+    for i, o in zip(in_hw, out_hw):
+        if o < 1 or o > MAX_SIDE or i > MAX_RATIO * o:
+            raise ValueError(f"{what}: cannot resize {in_hw[0]} x {in_hw[1]} to {out_hw[0]} x {out_hw[1]} "
+                             f"(sides up to {MAX_SIDE}, shrink by at most {MAX_RATIO})")
+
+
+def wants_ingest(x):
+    """a uint8 torch tensor, or anything that is not a torch tensor (a numpy picture), goes through the device ingest and
+    its checks; every other torch tensor keeps the float-tensor contract unchanged"""
+    import torch
+    return not torch.is_tensor(x) or x.dtype == torch.uint8
+
+
+def to_device_u8(x, device, what="image", min_side=1):
+    """checked uint8 picture -> contiguous uint8 tensor [1, h, w, 3] on `device` (one byte per channel over PCIe)"""
+    import torch
+    h, w, c = check_u8_picture(x, what, min_side)
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(x)
+    return x.reshape(1, h, w, c).contiguous().to(device)

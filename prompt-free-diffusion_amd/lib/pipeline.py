@@ -16,6 +16,7 @@ import os
 
 import torch
 
+from . import image_io
 from .hip import ops
 from .hip.ops import serialised
 
@@ -192,18 +193,40 @@ class PromptFreePipeline:
 
     @serialised
     @torch.no_grad()
+    def ingest(self, picture, size=None, what='image'):
+        """uint8 HWC picture (torch or numpy, any size) -> [1,3,H,W] in [0,1] in the model dtype, on the device:
+        `ToTensor()(im)[None].to(device).to(dtype)` (app.py:234), behind `im.resize([W, H], BICUBIC)` when size = (H, W)
+        is given (app.py:232,244) -- both as HIP kernels (ops.image_from_u8); one byte per channel crosses PCIe"""
+        u8 = image_io.to_device_u8(picture, self.net.device, what)
+        dtype = self.net.get_dtype() if hasattr(self.net, 'get_dtype') else torch.float32
+        kdtype = dtype if dtype in (torch.float16, torch.float32) else torch.float32
+        x = ops.image_from_u8(u8, size, dtype=kdtype)
+        return x if kdtype == dtype else x.to(dtype)
+
+    @serialised
+    @torch.no_grad()
     def generate(self, image, n_global, height, width, steps=50, scale=2.0, eta=0.0, seed=20, control=None,
                  uncond=None, decode=True, gather=False, verbose=False, timings=None, as_uint8=False):
         """returns (images, latents [n_local,4,h,w]); images = [n_local | n_global (gather), 3, H, W] in [0,1]
         in the model dtype, or -- as_uint8 -- packed uint8 [n, H, W, 3] (the bytes ToPILImage would produce,
-        app.py:273-275; 4x fewer bytes through the all-gather); decode=False returns the latents twice"""
+        app.py:273-275; 4x fewer bytes through the all-gather); decode=False returns the latents twice.
+        `image` and `control` may each be a uint8 HWC picture of any size instead of a float tensor (`ingest`): the
+        reference picture is converted as it is and shared by all samples, the control picture is resized to
+        (height, width) first"""
         P, r = self.world_size, self.rank
         dev = self.net.device
+        u8_image, u8_control = image_io.wants_ingest(image), control is not None and image_io.wants_ingest(control)
+        if u8_image:                 # checked before anything touches the device
+            image_io.check_u8_picture(image, 'image', min_side=32)
+        if u8_control:
+            image_io.check_resize(image_io.check_u8_picture(control, 'control')[:2], (height, width), 'control')
         mk = _Marks(torch.device(dev).type == 'cuda') if timings is not None else None
         if mk:
             mk.mark()
         xT = shard_xT(n_global, height, width, seed, r, P)
         n = xT.shape[0]
+        if u8_image:
+            image = self.ingest(image)
         if image.shape[0] > 1:
             # one reference image PER SAMPLE (SURVEY 8(d): the "+737 GFLOP/img" variant): SeeCoder is run once per image
             # (its decoder MHA attends across the batch axis, seecoder.py:70,83 -- a batch of images would mix them)
@@ -221,7 +244,7 @@ class PromptFreePipeline:
         c_info = {'type': 'image', 'conditioning': cond, 'unconditional_conditioning': uncond,
                   'unconditional_guidance_scale': scale}
         if control is not None:
-            c_info['control'] = control.to(dev)
+            c_info['control'] = self.ingest(control, (height, width), 'control') if u8_control else control.to(dev)
         x, _ = self.sampler.sample(steps=steps, shape=list(xT.shape), x_info=x_info, c_info=c_info, eta=eta,
                                    verbose=verbose)
         if mk:

@@ -20,6 +20,7 @@ from concurrent.futures import Future
 
 import torch
 
+from . import image_io
 from .pipeline import PromptFreePipeline, shard_xT
 
 
@@ -58,6 +59,9 @@ class PromptFreeServer:
     def submit(self, image, n_samples=1, height=512, width=512, steps=50, scale=2.0, eta=0.0, seed=20,
                control=None, uncond=None, as_uint8=True):
         """image [1,3,h,w] in [0,1] (any size); control [1,3,H,W] or None; uncond [1,148,768] or None (zeros).
+        image and control may each be a uint8 HWC picture [h,w,3] (torch or numpy, any size; the reference picture
+        at least 32 a side) instead: the request carries the bytes and the worker converts them on the device
+        (PromptFreePipeline.ingest), the control picture resized to (height, width) as app.py:232 does.
         -> Future of uint8 [n,H,W,3] (as_uint8) or float [n,3,H,W] images"""
         if self._stop:
             raise RuntimeError("server is closed")
@@ -69,15 +73,19 @@ class PromptFreeServer:
             raise ValueError(f"n_samples must be in [1, {self.max_batch}]")
         if steps < 1:
             raise ValueError("steps must be >= 1")
-        if not (torch.is_tensor(image) and image.dim() == 4 and image.shape[0] == 1 and image.shape[1] == 3 and
-                image.is_floating_point() and min(image.shape[2:]) >= 32):
-            raise ValueError("image must be a float tensor [1, 3, h, w] in [0, 1]")
+        if image_io.wants_ingest(image):            # a uint8 picture (anything that is not a torch tensor is checked as one)
+            image_io.check_u8_picture(image, "image", min_side=32)
+        elif not (image.dim() == 4 and image.shape[0] == 1 and image.shape[1] == 3 and image.is_floating_point() and
+                  min(image.shape[2:]) >= 32):
+            raise ValueError("image must be a float tensor [1, 3, h, w] in [0, 1] or a uint8 picture [h, w, 3]")
         if uncond is not None and not (torch.is_tensor(uncond) and uncond.is_floating_point() and
                                        tuple(uncond.shape) == (1, 148, 768)):
             raise ValueError("uncond must be a float tensor [1, 148, 768]")
-        if control is not None and not (torch.is_tensor(control) and control.is_floating_point() and
-                                        tuple(control.shape) == (1, 3, int(height), int(width))):
-            raise ValueError(f"control must be a float tensor [1, 3, {height}, {width}]")
+        if control is not None and image_io.wants_ingest(control):
+            image_io.check_resize(image_io.check_u8_picture(control, "control")[:2], (int(height), int(width)), "control")
+        elif control is not None and not (control.is_floating_point() and
+                                          tuple(control.shape) == (1, 3, int(height), int(width))):
+            raise ValueError(f"control must be a float tensor [1, 3, {height}, {width}] or a uint8 picture [h, w, 3]")
         r = _Request(image=image, n=int(n_samples), height=int(height), width=int(width), steps=int(steps),
                      scale=scale, eta=eta, seed=int(seed), control=control, uncond=uncond, as_uint8=as_uint8,
                      future=Future())
@@ -177,7 +185,8 @@ class PromptFreeServer:
                 torch.manual_seed(r0.seed)
             conds, xts, unconds = [], [], []
             for r in batch:
-                c, z = self.pipe.encode_reference(r.image.to(dev), r.n)
+                img = self.pipe.ingest(r.image) if image_io.wants_ingest(r.image) else r.image.to(dev)
+                c, z = self.pipe.encode_reference(img, r.n)
                 conds.append(c)
                 unconds.append(z if r.uncond is None else r.uncond.to(dev).to(c.dtype).expand(r.n, -1, -1))
                 xts.append(shard_xT(r.n, r.height, r.width, r.seed, 0, 1))      # each request keeps ITS x_T stream
@@ -185,7 +194,8 @@ class PromptFreeServer:
             c_info = {'type': 'image', 'conditioning': cond, 'unconditional_conditioning': uncond,
                       'unconditional_guidance_scale': r0.scale}
             if r0.control is not None:
-                c_info['control'] = r0.control.to(dev)
+                c_info['control'] = (self.pipe.ingest(r0.control, (r0.height, r0.width), 'control')
+                                     if image_io.wants_ingest(r0.control) else r0.control.to(dev))
             x, _ = self.pipe.sampler.sample(steps=r0.steps, shape=list(xT.shape), x_info={'type': 'image', 'xt': xT},
                                             c_info=c_info, eta=r0.eta, verbose=False)
             img = self.net.vae_decode(x, 'image', out_uint8=True) if r0.as_uint8 else self.net.vae_decode(x, 'image')

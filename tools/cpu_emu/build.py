@@ -1,8 +1,8 @@
 #!/usr/bin/env python
-"""Build the CPU emulation of csrc/gemm_glds.hip, csrc/norm.hip and csrc/attention.hip (tools/cpu_emu/emu_*.cpp): write
+"""Build the CPU emulation of csrc/gemm_glds.hip, csrc/norm.hip, csrc/attention.hip and csrc/image.hip (tools/cpu_emu/emu_*.cpp): write
 <file>_emu.inc = the kernel file with its gfx950 inline-asm statements replaced by their C meaning, then compile the
 drivers for the host with clang++.
-usage: [EMU_DEFINES="-DPFD_FAST_PROLOGUE ..."] build.py [outdir]   (default /tmp/pfd_cpu_emu)  -> <outdir>/emu_gemm, <outdir>/emu_norm, <outdir>/emu_attn"""
+usage: [EMU_DEFINES="-DPFD_FAST_PROLOGUE ..."] build.py [outdir]   (default /tmp/pfd_cpu_emu)  -> <outdir>/emu_gemm, <outdir>/emu_norm, <outdir>/emu_attn, <outdir>/emu_image"""
 import os
 import re
 import subprocess
@@ -44,14 +44,14 @@ def main():
     os.makedirs(out, exist_ok=True)
     procs = []
     only = os.environ.get("EMU_ONLY", "").split()     # e.g. EMU_ONLY=emu_gemm: just that driver
-    for name, driver in (("gemm_glds", "emu_gemm"), ("norm", "emu_norm"), ("attention", "emu_attn")):
+    for name, driver in (("gemm_glds", "emu_gemm"), ("norm", "emu_norm"), ("attention", "emu_attn"), ("image", "emu_image")):
         if only and driver not in only:
             continue
         preprocess(name, out)
         exe = os.path.join(out, driver)
         cmd = [CXX, "-std=c++17", os.environ.get("EMU_OPT", "-O0"), "-pthread", "-w", f"-I{HERE}", f"-I{out}", f"-I{REPO}/include", f"-I{CSRC}",
                os.path.join(HERE, driver + ".cpp"), "-o", exe] + os.environ.get("EMU_DEFINES", "").split()
-        procs.append((exe, cmd, subprocess.Popen(cmd)))     # the three drivers compile side by side
+        procs.append((exe, cmd, subprocess.Popen(cmd)))     # the drivers compile side by side
     for exe, cmd, p in procs:
         if p.wait() != 0:
             sys.exit("build.py: " + " ".join(cmd) + " failed")
