@@ -58,6 +58,18 @@ const char* pfd_last_error(void);
  *                stride lda): m = (b, oy, ox), k = (ky, kx, ci),
  *                iy = oy*stride + ky - pad, ix likewise; out-of-range taps read 0;
  *                with ups=1 the image is first nearest-2x upsampled (gather iy>>1).
+ *                with ups=2 the same upsample + 3x3 / stride 1 / pad 1 convolution runs as four 2x2-tap PHASE
+ *                convolutions over the low-res image: output pixel (2y+py, 2x+px) reads the low-res pixels
+ *                (y+py-1+ty, x+px-1+tx), ty, tx in {0,1} (zero outside the image), so K = 4*Cin and W holds four
+ *                phase blocks [py][px], each [N][2*2*Cin] (tap-major, channel-minor) in the launch's weight layout
+ *                (row-major with row stride ldw, block stride N*ldw; or w_tiled per block, block stride N*K), with
+ *                Wp[py][px][ty][tx] = sum of w[ky][kx] over ky in R(py,ty), kx in R(px,tx), R(0,0)={0}, R(0,1)={1,2},
+ *                R(1,0)={0,1}, R(1,1)={2}.  H, Wd are the low-res image, Ho = 2H, Wo = 2Wd; C, bias, act and gn_out
+ *                mean what they mean for ups=1 (the GroupNorm slabs of a sample cover the same rows in another order).
+ *                Served only by the 256-row loader-wave kernel, unsplit: ksize 3, stride 1, pad 1, Cin % 64 == 0,
+ *                H*Wd % 256 == 0, N % 160 == 0 or N % 128 == 0, act != GEGLU, no R / rowvec / Ct / gn_table / gnf_y /
+ *                ln_* / k_split / zero_rows, tile 0 or the forced variants 47 / 48; anything else is PFD_ESHAPE with
+ *                nothing launched and nothing written (callers run ups=1 with the 9-tap weight).
  *                W is [N][ksize*ksize*Cin] (tap-major, channel-minor), ldw its row stride.
  *   epi(v) = act(v + bias[n or m] + rowvec[(m / rows_per_rv)*ldrv + n]) + R[m*ldr + n]
  *

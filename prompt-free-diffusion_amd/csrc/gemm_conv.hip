@@ -449,7 +449,7 @@ extern "C" int pfd_gemm_f16_ex(const PfdGemmDesc* d, int32_t tile, pfd_stream_t 
   if (d->rowvec && d->rows_per_rv < 1) return PFD_EINVAL;
   if (d->act < PFD_ACT_NONE || d->act > PFD_ACT_GEGLU) return PFD_EINVAL;
   if (d->ksize > 0) {
-    if (d->Cin <= 0 || d->K != d->ksize * d->ksize * d->Cin) return PFD_EINVAL;
+    if (d->Cin <= 0 || d->K != (d->ups == 2 ? 4 : d->ksize * d->ksize) * d->Cin) return PFD_EINVAL;   // ups = 2: four folded 2x2-tap phase kernels
     if ((long)d->B * d->Ho * d->Wo != d->M) return PFD_EINVAL;
     if (d->stride < 1) return PFD_EINVAL;
   }
@@ -460,6 +460,10 @@ extern "C" int pfd_gemm_f16_ex(const PfdGemmDesc* d, int32_t tile, pfd_stream_t 
     const int rc = pfd_gemm160_try(d, enc / 100, enc % 100, (hipStream_t)stream);
     if (rc <= 0) return rc;
     if (tile >= 1000 || d->Ct) return PFD_ESHAPE;  // forced (or transposed tail) but not applicable
+  }
+  if (d->ksize > 0 && d->ups == 2) {
+    pfd_set_error("pfd_gemm_f16: the phase-folded upsample convolution is served by the 256-row loader-wave kernel only (see PfdGemmDesc.ups)");
+    return PFD_ESHAPE;
   }
   if (d->gn_table) {
     pfd_set_error("pfd_gemm_f16: the GroupNorm prologue is served by the 3x3 patch kernel only (see PfdGemmDesc.gn_table)");

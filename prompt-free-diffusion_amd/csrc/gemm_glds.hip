@@ -181,10 +181,18 @@ __device__ __forceinline__ void gst(void* ptr, T val) {
 }
 
 // output row (index into M) of row `row` of the tile that starts at m0 (see G160Params.pt_w)
-// PT = false (every kernel but the 3x3 patch kernels): rows are consecutive, the mapping folds away
-template <bool PT>
+// PT = 0 (every kernel but the 3x3 patch kernels): rows are consecutive, the mapping folds away
+// PT = 2 (phase form of the upsample convolution, PfdGemmDesc.ups = 2): GEMM row m = (b, phase, y, x) over the LOW-RES image,
+// phase = py * 2 + px, is output pixel (b, 2y + py, 2x + px); a tile lies in one phase of one sample (host: H * Wd % 256 == 0)
+template <int PT>
 __device__ __forceinline__ int tile_row_m(const G160Params& p, int m0, int row) {
-  if constexpr (PT) return p.pt_w ? m0 + (row >> p.pt_sh) * p.Wd + (row & (p.pt_w - 1)) : m0 + row;
+  if constexpr (PT == 2) {
+    const int hw = p.H * p.Wd;
+    const int bp = m0 / hw;                    // b * 4 + phase
+    const int q = m0 - bp * hw + row;
+    const int y = q / p.Wd, x = q - y * p.Wd;
+    return ((bp >> 2) * 2 * p.H + 2 * y + ((bp >> 1) & 1)) * (2 * p.Wd) + 2 * x + (bp & 1);
+  } else if constexpr (PT == 1) return p.pt_w ? m0 + (row >> p.pt_sh) * p.Wd + (row & (p.pt_w - 1)) : m0 + row;
   else return m0 + row;
 }
 
@@ -465,7 +473,7 @@ __device__ __forceinline__ void gn_slab_reduce(float (&cs)[8], float (&cq)[8], i
   }
 }
 
-template <int BM, int NTHREADS, bool PT>
+template <int BM, int NTHREADS, int PT>
 __device__ __forceinline__ void epilogue_store_gn(const G160Params& p, int m0, int n0, int slab0, char* smem, int tid) {
   constexpr int RS = stage_row_bytes(160);
   constexpr int NSLAB = BM / GN_SLAB, W = NTHREADS / 64, WPS = W / NSLAB, SWEEP = 3 * WPS;
@@ -522,7 +530,7 @@ __device__ __forceinline__ void epilogue_store_gn(const G160Params& p, int m0, i
 // pass 2 (every thread of the block, after a barrier): + residual, 16-byte chunks of contiguous row segments
 // LNOUT: compile the statistics-emitting store pass (linear kernels only: convolutions never feed a LayerNorm, and the
 // loader-wave kernels have no registers to spare for it)
-template <int BM, int NT, int NTHREADS, bool LNOUT = false, bool PT = false>
+template <int BM, int NT, int NTHREADS, bool LNOUT = false, int PT = 0>
 __device__ __forceinline__ void epilogue_store(const G160Params& p, int m0, int n0, char* smem, int tid, int slab0 = 0) {
   constexpr int BN = 32 * NT;
   constexpr bool GEGLU_ONLY = NT == 10;
@@ -915,8 +923,13 @@ __global__ __launch_bounds__(WAVES_M * 128) void gemm160_kernel(const G160Params
 //  step -- measured no better than lock-step consumers in round 3, profiles/r03_krot_pp_replay.log, and were removed in round 5.)
 // NST: operand stages.  2 = one K tile ahead (loaders wait vmcnt(0) per K step); 3 = two K tiles ahead with a counted
 // vmcnt (round 4; 156 KiB of LDS at the 160-wide tile), lock-step consumers only.
-template <bool CONV, int NT, int NST = 2>
+// PH: phase form of the fused nearest-2x upsample + 3x3 convolution (PfdGemmDesc.ups = 2).  Output pixel (2y + py, 2x + px)'s nine
+// taps read only the four low-res pixels (y + py - 1 + ty, x + px - 1 + tx), ty, tx in {0, 1}: four 2x2-tap convolutions over
+// the low-res image with host-folded weights (K = 4 Cin instead of 9 Cin: 4/9 of the MFMAs).  GEMM rows are (b, phase, y, x),
+// a tile's phase picks its weight block, and the store pass scatters the rows to their output pixels (tile_row_m<2>).
+template <bool CONV, int NT, int NST = 2, bool PH = false>
 __global__ __launch_bounds__(768) void gemm160ws_kernel(const G160Params p) {
+  static_assert(CONV || !PH, "the phase form is a convolution");
   constexpr int WMB = 4, NCW = 8, NLW = 4;
   constexpr int BN = 32 * NT, BM = 256;
   constexpr int A_INSTR = BM / 8, B_INSTR = BN / 8;
@@ -969,7 +982,16 @@ __global__ __launch_bounds__(768) void gemm160ws_kernel(const G160Params p) {
       a_chunk[j] = c * 8;
       const int m = m0 + r;
       a_ok[j] = m < p.M;
-      if (CONV) {
+      if constexpr (PH) {
+        const int hw = p.H * p.Wd;
+        const int bp = m0 / hw;                 // b * 4 + phase: tile-uniform
+        const int q = m0 - bp * hw + r;
+        const int y = q / p.Wd;
+        a_oy[j] = y + ((bp >> 1) & 1) - 1;      // low-res pixel under tap (0, 0)
+        a_ox[j] = q - y * p.Wd + (bp & 1) - 1;
+        a_img[j] = (long)(bp >> 2) * hw * p.lda;
+        a_ptr[j] = p.A;
+      } else if (CONV) {
         const int hw = p.Ho * p.Wo;
         const int b = m / hw;
         const int rem = m - b * hw;
@@ -990,9 +1012,11 @@ __global__ __launch_bounds__(768) void gemm160ws_kernel(const G160Params p) {
       const int r = (lw + NLW * j) * 8 + srow;
       const int c = cpos ^ ((r >> 1) & 7);
       b_ptr[j] = PFD_W_ROW_PTR(BN, p, tile_n, n0, r, c * 8);
+      if constexpr (PH) b_ptr[j] += (long)((m0 / (p.H * p.Wd)) & 3) * p.N * (p.w_tu ? (long)p.K : p.ldw);   // this tile's phase block
     }
-    const int Hin = p.ups ? 2 * p.H : p.H;
-    const int Win = p.ups ? 2 * p.Wd : p.Wd;
+    const int Hin = (!PH && p.ups) ? 2 * p.H : p.H;
+    const int Win = (!PH && p.ups) ? 2 * p.Wd : p.Wd;
+    const int ksz = PH ? 2 : p.ksize;
     int kt_issue = kt_begin + k_rotation(p.krot, tile_m, p.tiles_m, nsteps);   // rotated K walk, see k_rotation
     int tap_ky = 0, tap_kx = 0, ci0 = 0;
     const half_t* a_tap[A_PL];
@@ -1001,7 +1025,7 @@ __global__ __launch_bounds__(768) void gemm160ws_kernel(const G160Params p) {
       for (int j = 0; j < A_PL; ++j) {
         int iy = a_oy[j] + tap_ky, ix = a_ox[j] + tap_kx;
         const bool ok = a_ok[j] && iy >= 0 && iy < Hin && ix >= 0 && ix < Win;
-        if (p.ups) {
+        if (!PH && p.ups) {
           iy >>= 1;
           ix >>= 1;
         }
@@ -1012,8 +1036,8 @@ __global__ __launch_bounds__(768) void gemm160ws_kernel(const G160Params p) {
       const int k0 = kt * BK;
       const int tap = k0 / p.Cin;
       ci0 = k0 - tap * p.Cin;
-      tap_ky = tap / p.ksize;
-      tap_kx = tap - tap_ky * p.ksize;
+      tap_ky = tap / ksz;
+      tap_kx = tap - tap_ky * ksz;
       set_tap();
     };
     if (CONV) seek(kt_issue);
@@ -1038,7 +1062,7 @@ __global__ __launch_bounds__(768) void gemm160ws_kernel(const G160Params p) {
         ci0 += BK;
         if (ci0 >= p.Cin) {
           ci0 = 0;
-          if (++tap_kx == p.ksize) {
+          if (++tap_kx == ksz) {
             tap_kx = 0;
             ++tap_ky;
           }
@@ -1112,7 +1136,7 @@ __global__ __launch_bounds__(768) void gemm160ws_kernel(const G160Params p) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     block_barrier();                          // (C)
   }
-  epilogue_store<BM, NT, 768>(p, m0, n0, smem, tid, tile_m * (BM / GN_SLAB));
+  epilogue_store<BM, NT, 768, false, PH ? 2 : 0>(p, m0, n0, smem, tid, tile_m * (BM / GN_SLAB));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2048,7 +2072,10 @@ int launch160ws(G160Params& p, int bucket, hipStream_t s, int pp) {
     const double n_out = p.act == PFD_ACT_GEGLU ? p.N / 2 : p.N;
     pfd_prof_begin(bucket, 2.0 * p.M * p.N * p.K, a_bytes + 2.0 * p.N * p.K + 2.0 * p.M * n_out * (p.R ? 2 : 1), s);
   }
-  if (p.ksize > 0) {
+  if (p.ksize > 0 && p.ups == 2) {
+    if (pp == 2) hipLaunchKernelGGL((gemm160ws_kernel<true, NT, 3, true>), grid, dim3(768), 0, s, p);
+    else hipLaunchKernelGGL((gemm160ws_kernel<true, NT, 2, true>), grid, dim3(768), 0, s, p);
+  } else if (p.ksize > 0) {
     if (pp == 2) hipLaunchKernelGGL((gemm160ws_kernel<true, NT, 3>), grid, dim3(768), 0, s, p);
     else hipLaunchKernelGGL((gemm160ws_kernel<true, NT>), grid, dim3(768), 0, s, p);
   } else {
@@ -2175,6 +2202,18 @@ int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s
     p.zero_rows = d->zero_rows;
   }
   if (p.ksize == 0 && p.k_split == d->K) { p.A2 = p.A; p.lda2 = p.lda; }
+  // phase form of the upsample convolution (PfdGemmDesc.ups = 2): the 256-row loader-wave kernel, unsplit, plain epilogue
+  // (bias, activation, GroupNorm statistics); every tile inside one phase of one sample.  Anything else: not served.
+  if (d->ksize > 0 && d->ups == 2) {
+    if (d->ksize != 3 || d->stride != 1 || d->pad != 1 || d->K != 4 * d->Cin || d->Ho != 2 * d->H || d->Wo != 2 * d->Wd ||
+        ((long)d->H * d->Wd) % 256 || d->R || d->rowvec || d->Ct || d->gn_table || d->gnf_y || d->ln_stats || d->ln_out ||
+        d->k_split > 0 || d->zero_rows > 0 || d->act == PFD_ACT_GEGLU || (variant != 0 && variant != 47 && variant != 48) || splits > 1)
+      return 1;
+    p.splits = 1;
+    const int mode = variant == 48 ? 0 : 2;   // the 3-stage ring unless the two-stage form is forced
+    if (bn == 128) return launch160ws<4>(p, 16, s, mode) < 0 ? PFD_ELAUNCH : 0;
+    return launch160ws<5>(p, 16, s, mode) < 0 ? PFD_ELAUNCH : 0;
+  }
   if (p.ln_in) {   // LayerNorm fold: plain linear, statistics over K = ln_parts slices of 160 columns
     if (d->ksize > 0 || !p.ln_cs || p.ln_P < 1 || p.ln_P > 8 || p.ln_P * 160 != d->K) return 1;
     if ((reinterpret_cast<uintptr_t>(p.ln_in) & 7) || (reinterpret_cast<uintptr_t>(p.ln_cs) & 15)) return 1;

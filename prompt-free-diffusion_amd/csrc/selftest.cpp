@@ -130,7 +130,31 @@ struct GemmCase {
   int zero_rows = 0;  // > 0: the first rows of the operand are all zero and not stored (PfdGemmDesc.zero_rows)
   int gn_out = 0;     // 1: the launch also emits the GroupNorm statistics of its output (PfdGemmDesc.gn_out)
   int res_rows = 0;   // > 0: the residual holds that many rows and is read with one wrap (PfdGemmDesc.res_rows)
+  int declined = 0;   // 1: the library must answer PFD_ESHAPE and leave the output untouched
 };
+
+// PfdGemmDesc.ups = 2: the 3x3 weight [N][ldw >= 9 Cin] folded in fp32 and rounded once into four 2x2-tap phase blocks
+// [py][px][N][ldf >= 4 Cin]; phase tap (ty, tx) sums the 3x3 taps that read the same low-res pixel
+static std::vector<h16> fold_phase_weight(const std::vector<h16>& W, int N, int Cin, long ldw, long ldf) {
+  auto taps = [](int ph, int t, int* lo, int* hi) { *lo = ph == 0 ? (t == 0 ? 0 : 1) : (t == 0 ? 0 : 2); *hi = ph == 0 ? (t == 0 ? 0 : 2) : (t == 0 ? 1 : 2); };
+  std::vector<h16> out((size_t)4 * N * ldf, (h16)0);
+  for (int py = 0; py < 2; ++py)
+    for (int px = 0; px < 2; ++px)
+      for (int n = 0; n < N; ++n)
+        for (int ty = 0; ty < 2; ++ty)
+          for (int tx = 0; tx < 2; ++tx) {
+            int y0, y1, x0, x1;
+            taps(py, ty, &y0, &y1);
+            taps(px, tx, &x0, &x1);
+            for (int ci = 0; ci < Cin; ++ci) {
+              float a = 0.f;
+              for (int ky = y0; ky <= y1; ++ky)
+                for (int kx = x0; kx <= x1; ++kx) a += (float)W[(size_t)n * ldw + (ky * 3 + kx) * Cin + ci];
+              out[((size_t)(py * 2 + px) * N + n) * ldf + (ty * 2 + tx) * Cin + ci] = (h16)a;
+            }
+          }
+  return out;
+}
 
 static void run_gemm_case(const GemmCase& c) {
   const bool conv = c.ksize > 0;
@@ -155,12 +179,18 @@ static void run_gemm_case(const GemmCase& c) {
   auto rv = rand_h((size_t)n_rv * ldrv, 0.5f);
   auto R = rand_h((size_t)M * ldr, 1.0f);
   std::vector<h16> Wup = W;
-  if (c.w_tiled) {   // (n, k) -> (((n / T) * (K / 64) + k / 64) * T + n % T) * 64 + k % 64
-    const int T = N % 160 == 0 ? 160 : 128, nkt = K / 64;
-    Wup.assign((size_t)N * K, (h16)0);
-    for (int n = 0; n < N; ++n)
-      for (int k = 0; k < K; ++k)
-        Wup[(((size_t)(n / T) * nkt + k / 64) * T + n % T) * 64 + k % 64] = W[(size_t)n * ldw + k];
+  // what the device contracts over: the four folded phase blocks of ups = 2 (the reference keeps the 9-tap weight)
+  const int Kd = c.ups == 2 ? 4 * c.Cin : K, nblk = c.ups == 2 ? 4 : 1;
+  const long ldwd = Kd + c.extra_ld;
+  if (c.ups == 2) Wup = fold_phase_weight(W, N, c.Cin, ldw, ldwd);
+  if (c.w_tiled) {   // (n, k) -> (((n / T) * (K / 64) + k / 64) * T + n % T) * 64 + k % 64, per weight block
+    const int T = N % 160 == 0 ? 160 : 128, nkt = Kd / 64;
+    const std::vector<h16> Wsrc = Wup;
+    Wup.assign((size_t)nblk * N * Kd, (h16)0);
+    for (int bl = 0; bl < nblk; ++bl)
+      for (int n = 0; n < N; ++n)
+        for (int k = 0; k < Kd; ++k)
+          Wup[(size_t)bl * N * Kd + (((size_t)(n / T) * nkt + k / 64) * T + n % T) * 64 + k % 64] = Wsrc[((size_t)bl * N + n) * ldwd + k];
   }
   for (long r = 0; r < c.zero_rows; ++r)                     // the reference sees zero rows ...
     for (long k = 0; k < lda; ++k) A[r * lda + k] = (h16)0;
@@ -180,8 +210,8 @@ static void run_gemm_case(const GemmCase& c) {
   d.ws = dWS.p; d.ws_bytes = ((size_t)8 * M * N + 64) * sizeof(float);
   d.A = dA.p; d.W = dW.p; d.bias = c.bias ? dB.p : nullptr; d.rowvec = c.rowvec ? dRV.p : nullptr;
   d.R = c.res ? dR.p : nullptr; d.C = dC.p;
-  d.lda = lda; d.ldw = ldw; d.ldr = ldr; d.ldc = ldc; d.ldrv = ldrv;
-  d.M = M; d.N = N; d.K = K; d.rows_per_rv = rows_per_rv; d.act = c.act; d.bias_per_row = c.bias_row;
+  d.lda = lda; d.ldw = ldwd; d.ldr = ldr; d.ldc = ldc; d.ldrv = ldrv;
+  d.M = M; d.N = N; d.K = Kd; d.rows_per_rv = rows_per_rv; d.act = c.act; d.bias_per_row = c.bias_row;
   d.ksize = c.ksize; d.stride = c.stride; d.pad = c.pad; d.ups = c.ups;
   d.B = c.B; d.H = c.H; d.Wd = c.W; d.Cin = c.Cin; d.Ho = Ho; d.Wo = Wo;
   const long ldct = (M + 7) / 8 * 8 + 8;
@@ -205,6 +235,16 @@ static void run_gemm_case(const GemmCase& c) {
                    std::to_string(c.pad) + " u" + std::to_string(c.ups))
                       .c_str()
                 : "");
+  if (c.declined) {   // nothing launched, nothing written (the output buffer is zero-filled at allocation)
+    auto got = dC.get();
+    size_t touched = 0;
+    for (const auto& v : got) touched += (float)v != 0.f;
+    ++g_total;
+    const bool ok = rc == PFD_ESHAPE && touched == 0;
+    if (!ok) ++g_fail;
+    printf("%s %-58s declined: rc=%d, %zu elements written\n", ok ? "ok  " : "FAIL", name, rc, touched);
+    return;
+  }
   if (rc != 0) {
     ++g_total; ++g_fail;
     printf("FAIL %-58s rc=%d (%s)\n", name, rc, pfd_last_error());
@@ -284,7 +324,8 @@ static void run_gemm_case(const GemmCase& c) {
         }
     // 2-D patch tiles (48- / 96-wide images) partition a sample into slabs of 64 tile-local rows, not 64 consecutive pixels:
     // what the consumer uses -- and what is compared then -- are the per-sample totals
-    const bool tile2d = conv && c.ksize == 3 && c.stride == 1 && !c.ups && c.W != 16 && c.W != 32 && c.W != 64;
+    // (the phase form of the upsample convolution, ups = 2, orders a sample's rows (phase, y, x): per-sample totals as well)
+    const bool tile2d = conv && c.ksize == 3 && c.stride == 1 && ((!c.ups && c.W != 16 && c.W != 32 && c.W != 64) || c.ups == 2);
     if (tile2d) {
       const int spS = Ho * Wo / 64;
       std::vector<double> tref((size_t)c.B * tn * 32, 0.0);
@@ -311,6 +352,18 @@ static void run_narrow_conv_cases() {
   run_gemm_case({0, 8, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 0, 1, 8, 16, 512});     // N = 8: two row groups store
   run_gemm_case({0, 13, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 0, 1, 5, 130, 64});    // N = 13: element stores, three segments
   run_gemm_case({0, 4, 0, PFD_ACT_SILU, true, false, false, false, 0, 0, 3, 1, 1, 0, 1, 8, 64, 64});   // an activation: the general kernel
+}
+
+// PfdGemmDesc.ups = 2 against the nearest-2x + 3x3 reference: one 256-row tile per phase, both tile widths, both forms of the
+// loader-wave kernel, statistics, K-tile-contiguous phase blocks, several samples, a 4x16 image, and a declined request
+static void run_ups_fold_cases() {
+  { GemmCase c{0, 320, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 2, 1, 16, 16, 64}; c.gn_out = 1; run_gemm_case(c); }
+  run_gemm_case({0, 160, 0, 0, true, false, false, false, 5800, 0, 3, 1, 1, 2, 1, 16, 16, 64});
+  run_gemm_case({0, 128, 0, PFD_ACT_SILU, true, false, false, false, 0, 8, 3, 1, 1, 2, 1, 16, 16, 64});
+  { GemmCase c{0, 160, 0, 0, false, false, false, false, 0, 0, 3, 1, 1, 2, 3, 8, 32, 128}; c.w_tiled = 1; run_gemm_case(c); }
+  run_gemm_case({0, 320, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 2, 2, 16, 48, 64});
+  { GemmCase c{0, 160, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 2, 1, 8, 8, 64}; c.declined = 1; run_gemm_case(c); }
+  { GemmCase c{0, 160, 0, 0, true, true, false, false, 0, 0, 3, 1, 1, 2, 1, 16, 16, 64}; c.declined = 1; run_gemm_case(c); }   // residual: not served
 }
 
 static void run_tiled_weight_cases() {
@@ -1521,7 +1574,7 @@ static int replay(const char* path, bool timed = false, int force_tile = 0) {
   for (auto& q : rows) {
     const long M = q[0], N = q[1], K = q[2], ks = q[8];
     const size_t a = ks > 0 ? (size_t)q[12] * q[13] * q[14] * q[15] : (size_t)M * K;
-    maxA = std::max(maxA, a); maxW = std::max(maxW, (size_t)N * K); maxC = std::max(maxC, (size_t)M * N);
+    maxA = std::max(maxA, a); maxW = std::max(maxW, (size_t)N * K * (ks > 0 && q[11] == 2 ? 4 : 1)); maxC = std::max(maxC, (size_t)M * N);
     maxV = std::max(maxV, (size_t)std::max(M, N) * 4);
   }
   Dev<h16> dA(rand_h(maxA)), dW(rand_h(maxW, 0.05f)), dB(rand_h(maxV)), dRV(rand_h(maxC)), dR(rand_h(maxC)), dC(maxC), dY(maxC);
@@ -1575,7 +1628,7 @@ static int replay(const char* path, bool timed = false, int force_tile = 0) {
       if (q[23] > 0 && d.R && !q[22]) d.res_rows = (int)q[23];
       static const bool replay_warm = getenv("PFD_REPLAY_WARM") && atoi(getenv("PFD_REPLAY_WARM")) != 0;   // weights of every launch from ONE buffer (cache-warm): the bound of any weight prefetch
       if (timed && !replay_warm) {
-        const size_t wn = ((size_t)d.N * d.K + 4095) & ~(size_t)4095;
+        const size_t wn = ((size_t)d.N * d.K * (d.ksize > 0 && d.ups == 2 ? 4 : 1) + 4095) & ~(size_t)4095;   // (ups = 2: four phase blocks)
         if (pool_off + wn > pool_elems) pool_off = 0;
         d.W = dPool.p + pool_off;
         pool_off += wn;
@@ -1733,6 +1786,15 @@ int main(int argc, char** argv) {
     run_gn_pstats_case(8, 4096, 320, 320, PFD_ACT_SILU, 1e-5f);
     run_gn_pstats_case(3, 1024, 640, 0, PFD_ACT_NONE, 1e-6f);
     run_gn_pstats_case(2, 256, 1280, 1280, PFD_ACT_SILU, 1e-5f);
+    printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
+    return g_fail;
+  }
+  if (argc > 1 && !strcmp(argv[1], "--ups-fold")) {   // upsample convolution as four 2x2-tap phase convolutions (PfdGemmDesc.ups = 2)
+    run_ups_fold_cases();
+    if (argc > 2 && !strcmp(argv[2], "full")) {       // the two large upsample convolutions of a C2 UNet pass against fp64 (a minute of host time)
+      { GemmCase c{0, 640, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 2, 8, 32, 32, 640}; c.gn_out = 1; run_gemm_case(c); }
+      { GemmCase c{0, 1280, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 2, 8, 16, 16, 1280}; c.gn_out = 1; run_gemm_case(c); }
+    }
     printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
     return g_fail;
   }
@@ -1942,6 +2004,7 @@ int main(int argc, char** argv) {
     run_gemm_case({0, 160, 0, 0, true, true, false, false, 3402, 0, 3, 1, 1, 1, 1, 5, 6, 128});           // upsample + split
     run_gemm_case({0, 320, 0, 0, true, false, false, false, 0, 8, 3, 2, 0, 0, 1, 9, 9, 64});               // pad 0, ld+8
     run_gemm_case({0, 160, 0, 0, true, false, false, false, 0, 0, 1, 1, 0, 0, 2, 6, 6, 128});              // 1x1 as conv
+    run_ups_fold_cases();
     run_narrow_conv_cases();
 
     run_gemm_case({0, 160, 0, PFD_ACT_SILU, true, true, true, false, 0, 0, 3, 1, 1, 0, 1, 16, 48, 128});   // patch kernel, 2-D tiles

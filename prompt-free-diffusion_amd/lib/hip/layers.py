@@ -75,6 +75,34 @@ def pack_conv_weight(w4d):
     return pack_matrix(w.permute(0, 2, 3, 1).reshape(Cout, -1))
 
 
+# 3x3 taps of the nearest-2x upsampled image that read the same low-res pixel: _UPS_TAPS[phase][tap of the 2x2 kernel]
+_UPS_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))
+
+
+def pack_conv_weight_ups(w4d, dtype=torch.float16):
+    """[Cout, Cin, 3, 3] of `conv3x3(nearest-2x(x))` -> [4, Cout, 4*Cin]: the four phase kernels [py][px] of 2x2 taps over the
+    LOW-RES image (tap (ty, tx) at offset (py - 1 + ty, px - 1 + tx), tap-major / channel-minor), each tap the sum of the 3x3
+    taps that read the same low-res pixel (PfdGemmDesc.ups = 2).  Folded in fp32 (fp64 weights: in fp64) and rounded ONCE."""
+    w = w4d.detach()
+    w = w if w.dtype == torch.float64 else w.float()
+    Cout, Cin = w.shape[:2]
+    if tuple(w.shape[2:]) != (3, 3):
+        raise ValueError(f"pack_conv_weight_ups: a 3x3 kernel, got {tuple(w4d.shape)}")
+    blocks = []
+    for py in range(2):
+        for px in range(2):
+            taps = []
+            for ty in range(2):
+                for tx in range(2):
+                    acc = None
+                    for ky in _UPS_TAPS[py][ty]:
+                        for kx in _UPS_TAPS[px][tx]:
+                            acc = w[:, :, ky, kx] if acc is None else acc + w[:, :, ky, kx]
+                    taps.append(acc)
+            blocks.append(torch.stack(taps, 1).reshape(Cout, 4 * Cin))
+    return torch.stack(blocks, 0).to(dtype).contiguous()
+
+
 def pack_vec(b):
     return None if b is None else _dev16(b).contiguous()
 
@@ -120,6 +148,9 @@ class Conv2d(nn.Conv2d, _Packed):
     def _pk(self):
         return self._packed("w", lambda: (pack_conv_weight(self.weight), pack_vec(self.bias)), self.weight, self.bias)
 
+    def _pk_ups(self):
+        return self._packed("w_ups", lambda: (pack_conv_weight_ups(self.weight), pack_vec(self.bias)), self.weight, self.bias)
+
     def hip_gn(self, x, norm, *, silu=True, keep_raw=False, rowvec=None, res=None, rows_per_rv=None):
         """this convolution followed by `norm` (a GroupNorm(32) over its output, + SiLU) with the normalisation done inside the
         convolution's split-K reduction (ops.conv gn_fuse, PfdGemmDesc.gnf_y): -> (raw | None, normalised), or None when the
@@ -138,9 +169,20 @@ class Conv2d(nn.Conv2d, _Packed):
         res_rows (1x1 convolutions only): the residual is stored once for a doubled batch, see ops.gemm.
         gn_out=True: this output will be read by a GroupNorm -- where that norm takes the two-launch form the launch also
         emits its statistics (PfdGemmDesc.gn_out); they ride on the returned tensor (ops.get_gn_stats)"""
-        w, b = self._pk()
         k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
         cin = self.in_channels
+        if ups and ops.UPS_FOLD and gn is None and cin % 64 == 0 and (k, s, p) == (3, 1, 1) and rowvec is None and res is None and out_hw is None \
+                and ln_out in (None, False) and res_rows is None:
+            # nearest-2x + 3x3 as four 2x2-tap phase convolutions (4/9 of the MFMAs) where the library serves the shape; a shape
+            # it declined once is not asked again and its folded pack is not kept
+            key = ops.ups_fold_key(x, self.out_channels, act, self.bias, out, gn_out)
+            if not ops.ups_fold_declined(key):
+                wf, b = self._pk_ups()
+                y = ops.conv(x, wf, k, ups=2, bias=b, act=act, out=out, gn_out=gn_out)
+                if y is not None:
+                    return y
+                self.__dict__.get("_pk_cache", {}).pop("w_ups", None)
+        w, b = self._pk()
         if gn is not None:     # GroupNorm prologue: x (| gn[1]) is the un-normalised input (ops.conv)
             return ops.conv(x, w, k, stride=s, pad=p, bias=b, rowvec=rowvec, res=res, act=act, out=out,
                             rows_per_rv=rows_per_rv, gn=gn)

@@ -350,10 +350,31 @@ def conv_gn_fusable(B, H, W_, C1, C2, N, ksize=3, stride=1, pad=1):
 _GNF_DECLINED = set()
 
 
+# Upsample convolutions as four 2x2-tap phase convolutions (PfdGemmDesc.ups = 2) where the library serves the shape;
+# PFD_UPS_FOLD=0: every upsample convolution runs the 9-tap gather of ups = 1 (A/B runs)
+UPS_FOLD = os.environ.get("PFD_UPS_FOLD", "1") != "0"
+# Shapes whose phase-folded upsample convolution (conv(ups=2)) the library declined once: not asked again.
+_UPS_FOLD_DECLINED = set()
+
+
+def ups_fold_key(x, N, act, bias, out, gn_out):
+    """everything the library's decision about conv(ups=2) can depend on (heuristic calls only)"""
+    return (tuple(x.shape), int(N), int(act), bias is not None, bool(gn_out), int(x.stride(2)),
+            int(N) if out is None else int(_rows(out)[2]), str(x.device))
+
+
+def ups_fold_declined(key):
+    return key in _UPS_FOLD_DECLINED
+
+
 def conv(x, w, ksize, *, stride=1, pad=None, ups=False, bias=None, rowvec=None, res=None, act=ACT_NONE,
          out=None, tile=0, out_hw=None, rows_per_rv=None, gn=None, gn_out=False, gn_fuse=None):
     """Implicit-GEMM convolution of an NHWC image x[B,H,W,Cin] (Cin % 64 == 0) with packed
     weights w[N, ksize*ksize*Cin]; returns [B,Ho,Wo,N].  rowvec: [B, N] per-sample vector.
+    ups: False | True (nearest-2x upsample fused into the gather of the 9-tap weight, PfdGemmDesc.ups = 1) | 2 (the same
+    convolution as four 2x2-tap phase convolutions over the low-res image, PfdGemmDesc.ups = 2: w is the folded pack
+    [4, N, 4*Cin] of layers.pack_conv_weight_ups; returns None with NOTHING launched where the library does not serve the
+    shape -- the caller runs ups=True with the 9-tap pack).
     gn = (table, x2, silu): GroupNorm(+SiLU) of the virtual concat [x | x2] applied while the input is staged
     (table from groupnorm_table; see PfdGemmDesc.gn_table) -- x is then the UN-normalised tensor.
     gn_fuse = (gamma, beta, eps, silu, keep_raw): GroupNorm(32)(+SiLU) of the OUTPUT inside the launch's split-K reduction
@@ -389,9 +410,20 @@ def conv(x, w, ksize, *, stride=1, pad=None, ups=False, bias=None, rowvec=None, 
     Wo = (Win + 2 * pad - ksize) // stride + 1
     if out_hw is not None:  # asymmetric (bottom/right) zero padding: taps past the image read 0
         Ho, Wo = out_hw
-    N, K, ldw = _rows(w)
-    if K != ksize * ksize * Cin:
-        raise ValueError(f"conv: packed weight K {K} != {ksize}*{ksize}*{Cin}")
+    phase = ups == 2
+    if phase:
+        if gn is not None or gn_fuse is not None:
+            raise ValueError("conv: ups=2 cannot be combined with gn= / gn_fuse=")
+        if ksize != 3 or w.dim() != 3 or tuple(w.shape[::2]) != (4, 4 * Cin) or not w.is_contiguous():
+            raise ValueError(f"conv: ups=2 takes the folded weight [4, N, {4 * Cin}] of a 3x3 convolution, got {tuple(w.shape)}")
+        N, K, ldw = w.shape[1], w.shape[2], w.shape[2]
+        fold_key = ups_fold_key(x, N, act, bias, out, gn_out)
+        if tile == 0 and fold_key in _UPS_FOLD_DECLINED:
+            return None
+    else:
+        N, K, ldw = _rows(w)
+        if K != ksize * ksize * Cin:
+            raise ValueError(f"conv: packed weight K {K} != {ksize}*{ksize}*{Cin}")
     M = B * Ho * Wo
     if out is None:
         out = torch.empty((B, Ho, Wo, N), dtype=torch.float16, device=x.device)
@@ -407,7 +439,7 @@ def conv(x, w, ksize, *, stride=1, pad=None, ups=False, bias=None, rowvec=None, 
     d.ldrv = _rows(rowvec)[2] if rowvec is not None else 0
     d.M, d.N, d.K = M, N, K
     d.rows_per_rv, d.act, d.bias_per_row = (Ho * Wo if rows_per_rv is None else rows_per_rv), act, 0
-    d.ksize, d.stride, d.pad, d.ups = ksize, stride, pad, 1 if ups else 0
+    d.ksize, d.stride, d.pad, d.ups = ksize, stride, pad, 2 if phase else 1 if ups else 0
     d.B, d.H, d.Wd, d.Cin, d.Ho, d.Wo = B, H, W_, Cin, Ho, Wo
     d.ws, d.ws_bytes = _workspace(x.device).data_ptr(), _WS_BYTES
     if gn is not None:
@@ -445,6 +477,17 @@ def conv(x, w, ksize, *, stride=1, pad=None, ups=False, bias=None, rowvec=None, 
     if gn_out and gn is None and gn_stats_wanted(B, Ho * Wo, N) and Cin % 64 == 0:   # (True = "where a GroupNorm will use them")
         gst = _new_gn_stats(M, N, x.device)
         d.gn_out = gst.data_ptr()
+    if phase:
+        lib = _lib()
+        rc = lib.pfd_gemm_f16_ex(_byref(d), tile, _stream()) if tile else lib.pfd_gemm_f16(_byref(d), _stream())
+        if rc == _b.PFD_ESHAPE:      # nothing was launched, nothing written (include/pfd_hip.h)
+            if tile == 0:
+                _UPS_FOLD_DECLINED.add(fold_key)
+            return None
+        _b.check(rc, f"pfd_gemm_f16(conv, phase-folded upsample) M{M} N{N} K{K}")
+        if _TRACE:
+            _trace(d)
+        return _written(out, gst)
     if _TRACE:
         _trace(d)
     lib = _lib()

@@ -47,7 +47,31 @@ struct Case {
   bool gn_stats = false;   // the launch emits GroupNorm statistics (PfdGemmDesc.gn_out): checked against the sums of what it stored
   int gnf = 0;             // 1 / 2: GroupNorm(+SiLU) fused into the split-K reduction (PfdGemmDesc.gnf_y), raw tensor skipped / kept
   int res_rows = 0;        // > 0: the residual holds that many rows, read with one wrap (PfdGemmDesc.res_rows)
+  bool declined = false;   // the library must not serve the request: return value 1, nothing written
 };
+
+// PfdGemmDesc.ups = 2: the 3x3 weight [N][9 Cin] folded (fp32, rounded once) into four 2x2-tap phase blocks [py][px][N][4 Cin]:
+// phase tap (ty, tx) sums the 3x3 taps that read the same low-res pixel, rows R(0,0) = {0}, R(0,1) = {1,2}, R(1,0) = {0,1}, R(1,1) = {2}
+static std::vector<_Float16> fold_phase_weight(const std::vector<_Float16>& Wt, int N, int Cin) {
+  auto taps = [](int ph, int t, int* lo, int* hi) { *lo = ph == 0 ? (t == 0 ? 0 : 1) : (t == 0 ? 0 : 2); *hi = ph == 0 ? (t == 0 ? 0 : 2) : (t == 0 ? 1 : 2); };
+  std::vector<_Float16> out((size_t)4 * N * 4 * Cin);
+  for (int py = 0; py < 2; ++py)
+    for (int px = 0; px < 2; ++px)
+      for (int n = 0; n < N; ++n)
+        for (int ty = 0; ty < 2; ++ty)
+          for (int tx = 0; tx < 2; ++tx) {
+            int y0, y1, x0, x1;
+            taps(py, ty, &y0, &y1);
+            taps(px, tx, &x0, &x1);
+            for (int ci = 0; ci < Cin; ++ci) {
+              float a = 0.f;
+              for (int ky = y0; ky <= y1; ++ky)
+                for (int kx = x0; kx <= x1; ++kx) a += (float)Wt[(size_t)n * 9 * Cin + (ky * 3 + kx) * Cin + ci];
+              out[(((size_t)(py * 2 + px) * N + n) * 4 + ty * 2 + tx) * Cin + ci] = (_Float16)a;
+            }
+          }
+  return out;
+}
 
 static int run_variant(const Case& c, int variant, const std::vector<h16>& A, const std::vector<h16>& A2, const std::vector<h16>& Wt,
                        const std::vector<h16>& bias, const std::vector<h16>& rv, const std::vector<h16>& R, int M, int K, int Ho, int Wo,
@@ -57,13 +81,19 @@ static int run_variant(const Case& c, int variant, const std::vector<h16>& A, co
   PfdGemmDesc d;
   memset(&d, 0, sizeof(d));
   d.M = M; d.N = c.N; d.K = K;
-  std::vector<h16> Wtiled;
-  if (c.w_tiled) {   // (n, k) -> (((n / 160) * (K / 64) + k / 64) * 160 + n % 160) * 64 + k % 64
-    Wtiled.resize(Wt.size());
-    for (int n = 0; n < c.N; ++n)
-      for (int k = 0; k < K; ++k) Wtiled[(((size_t)(n / 160) * (K / 64) + k / 64) * 160 + n % 160) * 64 + k % 64] = Wt[(size_t)n * K + k];
+  std::vector<h16> Wtiled, Wfold;
+  const std::vector<h16>* Wsrc = &Wt;
+  int nblk = 1;                       // weight blocks of [N][K] each
+  if (c.ups == 2) { Wfold = fold_phase_weight(Wt, c.N, c.Cin); Wsrc = &Wfold; K = 4 * c.Cin; d.K = K; nblk = 4; }
+  if (c.w_tiled) {   // (n, k) -> (((n / T) * (K / 64) + k / 64) * T + n % T) * 64 + k % 64, T = the tile width
+    const int T = c.N % 160 == 0 ? 160 : 128;
+    Wtiled.resize(Wsrc->size());
+    for (int bl = 0; bl < nblk; ++bl)
+      for (int n = 0; n < c.N; ++n)
+        for (int k = 0; k < K; ++k)
+          Wtiled[(size_t)bl * c.N * K + (((size_t)(n / T) * (K / 64) + k / 64) * T + n % T) * 64 + k % 64] = (*Wsrc)[((size_t)bl * c.N + n) * K + k];
   }
-  d.A = A.data(); d.W = c.w_tiled ? Wtiled.data() : Wt.data(); d.bias = bias.data(); d.C = C.data();
+  d.A = A.data(); d.W = c.w_tiled ? Wtiled.data() : Wsrc->data(); d.bias = bias.data(); d.C = C.data();
   d.w_tiled = c.w_tiled ? 1 : 0;
   d.R = c.res ? R.data() : nullptr;
   d.rowvec = c.rowvec ? rv.data() : nullptr;
@@ -116,6 +146,13 @@ static int run_case(const Case& c) {
   g_err.clear();
   std::vector<float> gn1((size_t)(M / 64 + 1) * (N / 160) * 32, -1.f), gn2 = gn1;
   const int rc = run_variant(c, c.variant, A1, A2, Wt, bias, rv, R, M, K, Ho, Wo, C, ws, c.gn_stats ? &gn1 : nullptr);
+  if (c.declined) {
+    size_t touched = 0;
+    for (const auto& v : C) touched += (float)v != -77.f;
+    const bool ok = rc == 1 && touched == 0;
+    printf("%s %-70s rc %d, %zu elements written (declined requests launch nothing)\n", ok ? "ok  " : "FAIL", c.what, rc, touched);
+    return ok ? 0 : 1;
+  }
   if (rc != 0) { printf("FAIL %-70s rc=%d %s\n", c.what, rc, g_err.c_str()); return 1; }
   // double-precision reference
   double max_err = 0, max_ref = 0;
@@ -162,6 +199,21 @@ static int run_case(const Case& c) {
     // the statistics are the sums of the f16 values the launch stored, per 64-row slab and group of N / 32 channels
     const int cpg = N / 32, tn = N / 160, ngl = 160 / cpg;
     double worst = 0;
+    if (c.ups == 2) {
+      // the phase form's slabs are 64 rows of the (b, phase, y, x) order: what the consumer uses are the per-sample totals
+      const int spS = Ho * Wo / 64;
+      for (int b = 0; b < c.B; ++b)
+        for (int t = 0; t < tn; ++t)
+          for (int gl = 0; gl < ngl; ++gl) {
+            double a = 0, q = 0, ga = 0, gq = 0;
+            for (int r = 0; r < Ho * Wo; ++r)
+              for (int cc = 0; cc < cpg; ++cc) { const double v = (double)C[((size_t)b * Ho * Wo + r) * N + t * 160 + gl * cpg + cc]; a += v; q += v * v; }
+            for (int sl = b * spS; sl < (b + 1) * spS; ++sl) { const size_t o = (((size_t)sl * tn + t) * 16 + gl) * 2; ga += gn1[o]; gq += gn1[o + 1]; }
+            worst = std::max(worst, std::max(fabs(a - ga) / (1 + fabs(a)), fabs(q - gq) / (1 + fabs(q))));
+          }
+      if (worst > 1e-3) fails = 1;
+      extra += std::string(" | per-sample group sums err ") + std::to_string(worst);
+    } else {
     for (int sl = 0; sl < M / 64; ++sl)
       for (int t = 0; t < tn; ++t)
         for (int gl = 0; gl < ngl; ++gl) {
@@ -173,6 +225,7 @@ static int run_case(const Case& c) {
         }
     if (worst > 1e-3) fails = 1;
     extra += std::string(" | statistics err ") + std::to_string(worst);
+    }
   }
   if (ok && c.gnf) {
     // the same launch with the fused GroupNorm request: raw result (when kept) bit for bit the plain reduction's, the normalised
@@ -245,6 +298,13 @@ int main(int argc, char** argv) {
   { auto c = conv("variant 96 patch conv 16x16, K-tile-contiguous weights, two column tiles", 320, 96, 1, 3, 1, 1, 0, 1, 16, 16, 128, true, -1); c->w_tiled = true; }
   { auto c = conv("variant 83 implicit-GEMM conv, K-tile-contiguous weights, two column tiles", 320, 83, 1, 3, 1, 1, 0, 1, 8, 8, 128, false, -1); c->w_tiled = true; }
   conv("variant 99 patch conv 16x16 (8-wave form), 2 channel blocks", 160, 99, 1, 3, 1, 1, 0, 1, 16, 16, 128, true, 98);
+  // upsample convolution as four folded 2x2-tap phase convolutions (PfdGemmDesc.ups = 2) against the nearest-2x + 3x3 reference:
+  // 16x16 -> 32x32, one 256-row tile per phase
+  { auto c = conv("phase-fold: upsample conv 16x16x64 -> 320, group sums of the output (cpg 10)", 320, 0, 0, 3, 1, 1, 2, 1, 16, 16, 64, false, -1); c->gn_stats = true; }
+  conv("phase-fold: upsample conv 16x16x64 -> 160, two-stage form forced", 160, 48, 0, 3, 1, 1, 2, 1, 16, 16, 64, false, -1);
+  conv("phase-fold: upsample conv 16x16x64 -> 128 (128-wide tile)", 128, 0, 0, 3, 1, 1, 2, 1, 16, 16, 64, false, -1);
+  { auto c = conv("phase-fold: upsample conv 16x16x128 -> 160, K-tile-contiguous phase blocks", 160, 0, 0, 3, 1, 1, 2, 1, 16, 16, 128, false, -1); c->w_tiled = true; }
+  { auto c = conv("phase-fold: upsample conv 8x8x64 -> 160 is declined (a tile would straddle two phases)", 160, 0, 0, 3, 1, 1, 2, 1, 8, 8, 64, false, -1); c->declined = true; }
   int fails = 0, n = 0;
   for (const auto& c : cases) {
     if (argc > 1) {
