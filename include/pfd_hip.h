@@ -383,6 +383,23 @@ int pfd_timestep_embedding_f16(const int64_t* t, void* out, int32_t B, int32_t d
 int pfd_cfg_ddim_step(const void* eps, int32_t nb, const float* x, const float* noise,
                       const float* coef, float* x_prev, float* pred_x0, void* xin_next, int32_t rep,
                       int32_t B, int32_t C, int32_t h, int32_t w, pfd_stream_t stream);
+/* Seeded counter-based noise for the stochastic DDIM step (eta > 0: `noise = sigma_t * noise_like(...) * temperature`,
+ * ddim.py:166-169), as a function of (seed, sample_id, step, element) instead of a stream drawn in program order.
+ * key: device int64 [B, 2] = {seed, sample_id} per sample; step: the DDIM step index (`index` of ddim.py:160-163).
+ * Element e of a sample (NCHW order) takes output word e & 3 of Philox4x32-10 with
+ *   key (seed & 0xffffffff, (seed >> 32) & 0xffffffff), counter (e >> 2, step, sample_id & 0xffffffff, 0),
+ * multipliers D2511F53 / CD9E8D57, Weyl increments 9E3779B9 / BB67AE85; words (r0, r1) and (r2, r3) each give two
+ * normals by Box-Muller: u = ((ra >> 8) + 1) 2^-24, v = (rb >> 8) 2^-24, rad = sqrtf(-2 logf(u)),
+ * z = rad * (cospif(2v), sinpif(2v)).  lib/noise.py is the same specification on the host.
+ * out: fp32 [B, n_per_sample] (n_per_sample <= 2^34: the quad index is one counter word). */
+int pfd_philox_normal_f32(const int64_t* key, int32_t step, float* out, int32_t B, int64_t n_per_sample,
+                          pfd_stream_t stream);
+/* pfd_cfg_ddim_step with `sigma * noise_mul * z(key[b], step, e)` (z as pfd_philox_normal_f32, e the NCHW index inside
+ * sample b) in place of `sigma * noise[i]` (ddim.py:166-169; noise_mul is the sampler's `temperature`): no noise tensor,
+ * no extra launch, capturable in a hipGraph.  Every other operand as in pfd_cfg_ddim_step; key == NULL is PFD_EINVAL. */
+int pfd_cfg_ddim_step_rng(const void* eps, int32_t nb, const float* x, const int64_t* key, int32_t step,
+                          float noise_mul, const float* coef, float* x_prev, float* pred_x0, void* xin_next,
+                          int32_t rep, int32_t B, int32_t C, int32_t h, int32_t w, pfd_stream_t stream);
 /* y = a + b (f16, fp32 add), n elements; b may be NULL (copy). */
 int pfd_add_f16(const void* a, const void* b, void* y, int64_t n, pfd_stream_t stream);
 /* y = alpha*a + beta*b (f16 storage, fp32 math), n elements; b may be NULL (y = alpha*a).  The

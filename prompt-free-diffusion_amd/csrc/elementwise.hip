@@ -3,6 +3,7 @@
 // All HBM-bound; small tensors (latents are 4 channels), so simplicity over peak bandwidth
 // except pfd_nhwc_to_nchw / pfd_add_f16 which see full-size images.
 #include "pfd_common.h"
+#include "philox.h"
 
 namespace {
 
@@ -123,6 +124,103 @@ __global__ void cfg_ddim_kernel(const half_t* __restrict__ eps, int nb, const fl
     if (xin_next) {
       const half_t hv = (half_t)xp;
       for (int r = 0; r < rep; ++r) xin_next[(long)r * n + ei] = hv;
+    }
+  }
+}
+
+// The generator on its own: one thread per quad (one Philox call), out[b, 4q .. 4q+3].  VEC: n_per_sample % 4 == 0 and
+// `out` 16-byte aligned -> one 16-byte store; otherwise scalar stores, the tail of a sample's last quad dropped.
+template <bool VEC>
+__global__ void philox_normal_kernel(const int64_t* __restrict__ key, int step, float* __restrict__ out, int B,
+                                     long ns) {
+  const long nq = (ns + 3) >> 2;
+  const long total = (long)B * nq;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / nq);
+    const long q = i - (long)b * nq;
+    float z[4];
+    pfd_philox_normal4(key[2 * b], key[2 * b + 1], step, (uint32_t)q, z);
+    float* o = out + (long)b * ns + q * 4;
+    if (VEC) {
+      *reinterpret_cast<float4*>(o) = make_float4(z[0], z[1], z[2], z[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (q * 4 + j < ns) o[j] = z[j];
+    }
+  }
+}
+
+// cfg_ddim_kernel with the noise evaluated in place: thread = four consecutive NCHW elements of ONE sample = one Philox
+// call.  VEC (w % 4 == 0, 16-byte aligned x / x_prev / pred_x0): the four share a row, 16-byte accesses; otherwise the
+// scalar path computes the same values.  After `nz` the arithmetic is cfg_ddim_kernel's, in its order.
+template <bool VEC>
+__global__ void cfg_ddim_rng_kernel(const half_t* __restrict__ eps, int nb, const float* __restrict__ x,
+                                    const int64_t* __restrict__ key, int step, float noise_mul,
+                                    const float* __restrict__ coef, float* __restrict__ x_prev,
+                                    float* __restrict__ pred_x0, half_t* __restrict__ xin_next, int rep, int B, int C,
+                                    int h, int w) {
+  const long ns = (long)C * h * w;
+  const long n = (long)B * ns;
+  const long nq = (ns + 3) >> 2;
+  const long total = (long)B * nq;
+  const float a_t = coef[0], a_prev = coef[1], sigma = coef[2], s1mat = coef[3], scale = coef[4];
+  const float isq_at = 1.0f / sqrtf(a_t);
+  const float sq_aprev = sqrtf(a_prev);
+  const float dir = sqrtf(fmaxf(1.0f - a_prev - sigma * sigma, 0.f));
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / nq);
+    const long q = i - (long)b * nq;
+    const long e0 = q * 4;
+    const long base = (long)b * ns + e0;
+    float z[4], xv[4], xp4[4], p04[4];
+    pfd_philox_normal4(key[2 * b], key[2 * b + 1], step, (uint32_t)q, z);
+    if (VEC) {
+      const float4 v = *reinterpret_cast<const float4*>(x + base);
+      xv[0] = v.x; xv[1] = v.y; xv[2] = v.z; xv[3] = v.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) xv[j] = e0 + j < ns ? x[base + j] : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      xp4[j] = p04[j] = 0.f;
+      if (!VEC && e0 + j >= ns) continue;
+      const long el = e0 + j;   // (c*h + y)*w + x inside the sample
+      const int xw = (int)(el % w);
+      const long t = el / w;
+      const int yh = (int)(t % h);
+      const int c = (int)(t / h);
+      const long ei = (((long)b * h + yh) * w + xw) * C + c;  // NHWC
+      float e;
+      if (nb == 2) {
+        const float eu = (float)eps[ei];
+        const float ec = (float)eps[n + ei];
+        e = eu + scale * (ec - eu);
+      } else {
+        e = (float)eps[ei] * scale;
+      }
+      const float nz = noise_mul * z[j];
+      const float p0 = (xv[j] - s1mat * e) * isq_at;
+      float xp = sq_aprev * p0 + dir * e;
+      xp += sigma * nz;
+      xp4[j] = xp;
+      p04[j] = p0;
+      if (xin_next) {
+        const half_t hv = (half_t)xp;
+        for (int r = 0; r < rep; ++r) xin_next[(long)r * n + ei] = hv;
+      }
+    }
+    if (VEC) {
+      *reinterpret_cast<float4*>(x_prev + base) = make_float4(xp4[0], xp4[1], xp4[2], xp4[3]);
+      *reinterpret_cast<float4*>(pred_x0 + base) = make_float4(p04[0], p04[1], p04[2], p04[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (e0 + j < ns) {
+          x_prev[base + j] = xp4[j];
+          pred_x0[base + j] = p04[j];
+        }
     }
   }
 }
@@ -300,6 +398,44 @@ extern "C" int pfd_cfg_ddim_step(const void* eps, int32_t nb, const float* x, co
   hipLaunchKernelGGL(cfg_ddim_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
                      (const half_t*)eps, nb, x, noise, coef, x_prev, pred_x0, (half_t*)xin_next, rep, B, C, h, w);
   return pfd_check_launch("pfd_cfg_ddim_step");
+}
+
+extern "C" int pfd_philox_normal_f32(const int64_t* key, int32_t step, float* out, int32_t B, int64_t n_per_sample,
+                                     pfd_stream_t stream) {
+  if (!key || !out || B <= 0 || n_per_sample <= 0 || step < 0) return PFD_EINVAL;
+  if (n_per_sample > ((int64_t)1 << 34)) return PFD_ESHAPE;   // the quad index is one 32-bit counter word
+  const long nq = ((long)n_per_sample + 3) >> 2;
+  const bool vec = !(n_per_sample & 3) && !(reinterpret_cast<uintptr_t>(out) & 15);
+  PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
+  if (vec)
+    hipLaunchKernelGGL(philox_normal_kernel<true>, dim3(grid_for((long)B * nq, 256)), dim3(256), 0,
+                       (hipStream_t)stream, key, step, out, B, (long)n_per_sample);
+  else
+    hipLaunchKernelGGL(philox_normal_kernel<false>, dim3(grid_for((long)B * nq, 256)), dim3(256), 0,
+                       (hipStream_t)stream, key, step, out, B, (long)n_per_sample);
+  return pfd_check_launch("pfd_philox_normal_f32");
+}
+
+extern "C" int pfd_cfg_ddim_step_rng(const void* eps, int32_t nb, const float* x, const int64_t* key, int32_t step,
+                                     float noise_mul, const float* coef, float* x_prev, float* pred_x0, void* xin_next,
+                                     int32_t rep, int32_t B, int32_t C, int32_t h, int32_t w, pfd_stream_t stream) {
+  if (!eps || !x || !key || !coef || !x_prev || !pred_x0 || step < 0) return PFD_EINVAL;
+  if (nb < 1 || nb > 2 || B <= 0 || C <= 0 || h <= 0 || w <= 0 || (xin_next && (rep < 1 || rep > 2))) return PFD_EINVAL;
+  const long ns = (long)C * h * w;
+  if (ns > ((long)1 << 34)) return PFD_ESHAPE;
+  const long nq = (ns + 3) >> 2;
+  const bool vec = !(w & 3) && !((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_prev) |
+                                  reinterpret_cast<uintptr_t>(pred_x0)) & 15);
+  PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
+  if (vec)
+    hipLaunchKernelGGL(cfg_ddim_rng_kernel<true>, dim3(grid_for((long)B * nq, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)eps, nb, x, key, step, noise_mul, coef, x_prev, pred_x0, (half_t*)xin_next, rep,
+                       B, C, h, w);
+  else
+    hipLaunchKernelGGL(cfg_ddim_rng_kernel<false>, dim3(grid_for((long)B * nq, 256)), dim3(256), 0,
+                       (hipStream_t)stream, (const half_t*)eps, nb, x, key, step, noise_mul, coef, x_prev, pred_x0,
+                       (half_t*)xin_next, rep, B, C, h, w);
+  return pfd_check_launch("pfd_cfg_ddim_step_rng");
 }
 
 extern "C" int pfd_add_f16(const void* a, const void* b, void* y, int64_t n, pfd_stream_t stream) {

@@ -1076,6 +1076,70 @@ static void run_elementwise() {
     report("cfg_ddim pred_x0", gp0, rp0, 2e-5, 2e-5);
     report("cfg_ddim xin_next", gxin, rxin, 3e-3, 2e-3);
   }
+  {  // seeded noise (Philox4x32-10 + Box-Muller, include/pfd_hip.h) alone and inside the cfg + ddim step; host reference = the specification in fp64
+    auto philox = [](uint32_t c[4], uint32_t k0, uint32_t k1) {
+      for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+        c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+      }
+    };
+    auto normal = [&](int64_t seed, int64_t sid, int step, long e) {
+      uint32_t c[4] = {(uint32_t)(e >> 2), (uint32_t)step, (uint32_t)((uint64_t)sid & 0xffffffffu), 0u};
+      philox(c, (uint32_t)((uint64_t)seed & 0xffffffffu), (uint32_t)((uint64_t)seed >> 32));
+      const int j = (int)(e & 3);
+      const double u = ((c[j & 2] >> 8) + 1) * ldexp(1.0, -24), v = (c[(j & 2) + 1] >> 8) * ldexp(1.0, -24);
+      const double rad = sqrt(-2.0 * log(u)), ang = 2.0 * 3.14159265358979323846 * v;
+      return rad * ((j & 1) ? sin(ang) : cos(ang));
+    };
+    uint32_t kat[4] = {0x243f6a88u, 0x85a308d3u, 0x13198a2eu, 0x03707344u};
+    philox(kat, 0xa4093822u, 0x299f31d0u);
+    ++g_total;
+    if (!(kat[0] == 0xd16cfe09u && kat[1] == 0x94fdccebu && kat[2] == 0x5001e420u && kat[3] == 0x24126ea1u)) {
+      ++g_fail;
+      printf("FAIL %-58s %08x %08x %08x %08x\n", "philox4x32_10 host reference, known answer", kat[0], kat[1], kat[2], kat[3]);
+    }
+    std::vector<int64_t> key = {-1, 3, (1ll << 40) + 12345, 7};
+    Dev<int64_t> dk(key);
+    for (long ns : {7l, 4100l}) {
+      Dev<float> dz((size_t)2 * ns);
+      int rc = pfd_philox_normal_f32(dk.p, 49, dz.p, 2, ns, nullptr);
+      auto got = dz.get();
+      std::vector<double> ref(got.size());
+      for (int b = 0; b < 2; ++b) for (long e = 0; e < ns; ++e) ref[b * ns + e] = normal(key[2 * b], key[2 * b + 1], 49, e);
+      report(std::string("philox_normal n=") + std::to_string(ns) + " rc=" + std::to_string(rc), got, ref, 1e-5, 0);
+    }
+    for (int w : {6, 8}) {   // scalar path, 16-byte path
+      const int B = 2, C = 4, h = 5;
+      const long ns = (long)C * h * w;
+      const size_t n = (size_t)B * ns;
+      auto eps = rand_h(2 * n, 1.5f);
+      auto x = rand_f(n, 2.f);
+      std::vector<float> coef = {0.45f, 0.52f, 0.1f, sqrtf(1 - 0.45f), 2.0f};
+      Dev<h16> de(eps), dxin(2 * n);
+      Dev<float> dx(x), dc(coef), dxp(n), dp0(n);
+      int rc = pfd_cfg_ddim_step_rng(de.p, 2, dx.p, dk.p, 7, 0.5f, dc.p, dxp.p, dp0.p, dxin.p, 2, B, C, h, w, nullptr);
+      const int rc_null = pfd_cfg_ddim_step_rng(de.p, 2, dx.p, nullptr, 7, 0.5f, dc.p, dxp.p, dp0.p, dxin.p, 2, B, C, h, w, nullptr);
+      auto gxp = dxp.get(), gp0 = dp0.get();
+      auto gxin = dxin.get();
+      std::vector<double> rxp(n), rp0(n), rxin(2 * n);
+      for (int b = 0; b < B; ++b) for (int c = 0; c < C; ++c) for (int y = 0; y < h; ++y) for (int xx = 0; xx < w; ++xx) {
+        const long el = ((long)c * h + y) * w + xx;
+        const size_t i = (size_t)b * ns + el, ei = (((size_t)b * h + y) * w + xx) * C + c;
+        const double eu = (double)eps[ei], ec = (double)eps[n + ei], e = eu + 2.0 * (ec - eu);
+        const double p0 = (x[i] - sqrt(1 - 0.45) * e) / sqrt(0.45);
+        const double xp = sqrt(0.52) * p0 + sqrt(1 - 0.52 - 0.01) * e + 0.1 * 0.5 * normal(key[2 * b], key[2 * b + 1], 7, el);
+        rxp[i] = xp; rp0[i] = p0; rxin[ei] = xp; rxin[n + ei] = xp;
+      }
+      const std::string tag = std::string("cfg_ddim_rng w=") + std::to_string(w);
+      ++g_total;
+      if (rc_null != PFD_EINVAL) { ++g_fail; printf("FAIL %-58s rc=%d\n", (tag + " key=NULL").c_str(), rc_null); }
+      report(tag + " x_prev rc=" + std::to_string(rc), gxp, rxp, 2e-5, 2e-5);
+      report(tag + " pred_x0", gp0, rp0, 2e-5, 2e-5);
+      report(tag + " xin_next", gxin, rxin, 3e-3, 2e-3);
+    }
+  }
   {  // add, add_rowvec
     const long n = 1003;
     auto a = rand_h(n + 5), b = rand_h(n + 5);
@@ -1823,6 +1887,11 @@ int main(int argc, char** argv) {
   }
   if (argc > 1 && !strcmp(argv[1], "--image")) {   // the uint8 picture ingest only
     run_image();
+    printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
+    return g_fail;
+  }
+  if (argc > 1 && !strcmp(argv[1], "--elementwise")) {   // boundary / elementwise kernels only (the seeded noise among them)
+    run_elementwise();
     printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
     return g_fail;
   }

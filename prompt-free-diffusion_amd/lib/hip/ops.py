@@ -758,15 +758,49 @@ def timestep_embedding(t, dim, max_period=10000.0):
     return out
 
 
-def cfg_ddim_step(eps, nb, x, coef, *, noise=None, want_next=True, rep=None):
+def noise_key_rows(key, B, device):
+    """int64 [B, 2] {seed, sample_id} rows on `device` (a CPU tensor is copied: not during a stream capture)"""
+    if not (torch.is_tensor(key) and key.dtype == torch.int64 and tuple(key.shape) == (B, 2)):
+        raise ValueError(f"noise_key must be an int64 tensor [{B}, 2] of (seed, sample_id) rows")
+    return key.to(device).contiguous()
+
+
+def philox_normal(key, step, n_per_sample):
+    """fp32 [B, n_per_sample] standard normals: row b is the noise of sample key[b] = (seed, sample_id) at DDIM step
+    `step` (Philox4x32-10 + Box-Muller; lib/noise.py is the same function on the host)."""
+    if not (torch.is_tensor(key) and key.is_cuda):
+        raise RuntimeError("philox_normal: key must live on the GPU; the HIP path has no CPU fallback")
+    B = key.shape[0]
+    key = noise_key_rows(key, B, key.device)
+    out = torch.empty((B, int(n_per_sample)), dtype=torch.float32, device=key.device)
+    _b.check(_lib().pfd_philox_normal_f32(key.data_ptr(), int(step), out.data_ptr(), B, int(n_per_sample), _stream()),
+             "pfd_philox_normal_f32")
+    return out
+
+
+def cfg_ddim_step(eps, nb, x, coef, *, noise=None, want_next=True, rep=None, noise_key=None, step=None, noise_mul=1.0):
     """Fused CFG combine + DDIM update.  eps NHWC f16 [nb*B,h,w,C]; x NCHW fp32 [B,C,h,w];
     coef fp32[5] device.  Returns (x_prev fp32 NCHW, pred_x0 fp32 NCHW, xin_next f16 NHWC|None);
-    xin_next holds `rep` copies of the batch (default nb: the CFG-doubled UNet input)."""
+    xin_next holds `rep` copies of the batch (default nb: the CFG-doubled UNet input).
+    noise: fp32 NCHW tensor added as sigma * noise, or -- noise_key int64 [B,2] (seed, sample_id), step, noise_mul --
+    the seeded noise sigma * noise_mul * z(key[b], step, element) evaluated inside the kernel (philox_normal)."""
     B, Cc, h, w = x.shape
     rep = nb if rep is None else rep
+    if noise_key is not None:
+        if noise is not None:
+            raise ValueError("cfg_ddim_step: give either noise or noise_key, not both")
+        if step is None:
+            raise ValueError("cfg_ddim_step: noise_key needs the DDIM step index (step=)")
+        noise_key = noise_key_rows(noise_key, B, x.device)
     x_prev = torch.empty_like(x)
     pred_x0 = torch.empty_like(x)
     xin = torch.empty((rep * B, h, w, Cc), dtype=torch.float16, device=x.device) if want_next else None
+    if noise_key is not None:
+        rc = _lib().pfd_cfg_ddim_step_rng(eps.data_ptr(), nb, x.data_ptr(), noise_key.data_ptr(), int(step),
+                                          float(noise_mul), coef.data_ptr(), x_prev.data_ptr(), pred_x0.data_ptr(),
+                                          _ptr(xin), rep, B, Cc, h, w, _stream())
+        _b.check(rc, "pfd_cfg_ddim_step_rng")
+        return x_prev, pred_x0, xin
     rc = _lib().pfd_cfg_ddim_step(eps.data_ptr(), nb, x.data_ptr(), _ptr(noise), coef.data_ptr(), x_prev.data_ptr(),
                                   pred_x0.data_ptr(), _ptr(xin), rep, B, Cc, h, w, _stream())
     _b.check(rc, "pfd_cfg_ddim_step")

@@ -17,6 +17,12 @@ MI355X-first differences (results identical up to fp16 rounding):
 The x_T draw is `torch.randn(shape, device, dtype)` as in the reference (:105); a caller-provided
 x_info['xt'] tensor is honoured (the reference's own 'xt' branch calls Tensor.astype and cannot
 run, :94-96).
+
+Seeded on-device noise (opt-in): x_info['noise_key'], int64 [B, 2] rows (seed, sample_id) on any device, makes
+the per-step noise of eta > 0 (:166) a function of (key row, step index, element) evaluated inside the step kernel
+(pfd_cfg_ddim_step_rng, lib/noise.py) instead of a draw from the global generator: such a schedule is captured
+and replayed as a hipGraph like eta = 0, and a sample's result does not depend on the batch it rides in.
+Without the key every path is the reference's: `noise_like` from the global generator, eager launches.
 """
 import numpy as np
 import torch
@@ -134,13 +140,19 @@ class DDIMSampler(object):
         t_col = torch.as_tensor(np.array(time_range).copy(), device=device).long()[:, None]
         x_type, c_type = x_info['type'], c_info['type']
         stochastic = bool(np.any(np.asarray(self.ddim_sigmas) != 0.))
+        nkey = x_info.get('noise_key', None)
+        if nkey is not None:
+            if noise_dropout > 0.:
+                raise ValueError("noise_dropout > 0 is not available with x_info['noise_key'] (dropout draws from the "
+                                 "global generator: leave the key out)")
+            nkey = ops.noise_key_rows(nkey, bs, device)
 
         def make_loop(n):
             """the whole trajectory of n samples as a pure function of device tensors (capturable as one hipGraph)"""
             t_table = t_col.repeat(1, nb * n)
             zl = n if zero_lead else 0
 
-            def run_loop(x, c_in, hint):
+            def run_loop(x, c_in, hint, nkey=None):
                 from .controlnet import PreparedHint
                 ctx = model.prepare_context(c_in)
                 ctx.zero_lead = zl
@@ -160,12 +172,18 @@ class DDIMSampler(object):
                     eps = model.apply_model_nhwc(x_type, xin, t_table[i], c_type, ctx, control=ctl,
                                                  emb_table=emb_all[i:i + 1], cfg_pair=pair)
                     noise = None
-                    if self.ddim_sigmas[index] != 0.:
+                    keyed = nkey is not None and self.ddim_sigmas[index] != 0.
+                    if self.ddim_sigmas[index] != 0. and not keyed:
                         noise = noise_like(x) * temperature
                         if noise_dropout > 0.:
                             noise = torch.nn.functional.dropout(noise, p=noise_dropout)
                         noise = noise.contiguous()
-                    x, pred_x0, xin = ops.cfg_ddim_step(eps, nb, x, coef[index], noise=noise, want_next=True, rep=rep)
+                    if keyed:     # sigma * temperature * z(key row, index, element), drawn inside the kernel
+                        x, pred_x0, xin = ops.cfg_ddim_step(eps, nb, x, coef[index], want_next=True, rep=rep,
+                                                            noise_key=nkey, step=index, noise_mul=temperature)
+                    else:
+                        x, pred_x0, xin = ops.cfg_ddim_step(eps, nb, x, coef[index], noise=noise, want_next=True,
+                                                            rep=rep)
                     if index % log_every_t == 0 or index == total_steps - 1:
                         inter_xt.append(x)
                         inter_x0.append(pred_x0)
@@ -174,34 +192,38 @@ class DDIMSampler(object):
                 return x, inter_xt, inter_x0
             return run_loop, t_table
 
-        use_graph = self.use_graph and not stochastic and callback is None and x.is_cuda
+        # a keyed schedule draws nothing from a generator: capturable whatever eta is
+        use_graph = self.use_graph and (not stochastic or nkey is not None) and callback is None and x.is_cuda
         if use_graph:
             # one hipGraph per (shape, schedule, weights version, flags); static input buffers, replayed per request.
             # (Round 4 also cut the batch into concurrent sub-batch graphs on their own streams: 520 -> 646 ms per batch at
             #  C2, profiles/r04_lanes_ab.log -- removed in round 5.)
             key = (tuple(x.shape), tuple(c_in.shape), None if hint is None else tuple(hint.shape), total_steps,
                    float(scale), nb, x_type, c_type, int(log_every_t), zero_lead,
-                   bool(self.share_cfg_prefix), hash(np.asarray(timesteps).tobytes()), self._weights_signature())
+                   bool(self.share_cfg_prefix), hash(np.asarray(timesteps).tobytes()), self._weights_signature(),
+                   None if nkey is None else (float(temperature), hash(np.asarray(self.ddim_sigmas).tobytes())))
             ent = self._graphs.pop(key, None)
             if ent is None:
                 while len(self._graphs) >= self.max_graphs:
                     torch.cuda.synchronize()   # never drop a graph whose replay may still be in flight
                     self._graphs.pop(next(iter(self._graphs)))   # least recently used (a server varies batch size and
                 run_loop, t_table = make_loop(bs)                 # scale per request: keep the others)
-                ent = self._capture(run_loop, x, c_in, hint, (coef, t_table))
+                ent = self._capture(run_loop, x, c_in, hint, (coef, t_table), nkey)
             self._graphs[key] = ent            # (re-)inserted last = most recently used
-            g, sx, sc, sh, outs, _keep = ent
+            g, sx, sc, sh, outs, _keep, sk = ent
             sx.copy_(x)
             sc.copy_(c_in)
             if sh is not None:
                 sh.copy_(hint)
+            if sk is not None:
+                sk.copy_(nkey)
             g.replay()
             xf = outs[0].clone()               # static output buffers of the graph
             ixt = [t.clone() for t in outs[1]]
             ix0 = [t.clone() for t in outs[2]]
         else:
             run_loop, _ = make_loop(bs)
-            xf, ixt, ix0 = run_loop(x, c_in, hint)
+            xf, ixt, ix0 = run_loop(x, c_in, hint, nkey)
         intermediates = {'pred_xt': [t.to(dtype) for t in ixt], 'pred_x0': [t.to(dtype) for t in ix0]}
         out = xf.to(dtype)
         x_info['x'] = out
@@ -298,6 +320,13 @@ class DDIMSampler(object):
         coef = self._coef_table(scale, use_original_steps)[index]
         noise = None
         sig = (self.ddim_sigmas_for_original_num_steps if use_original_steps else self.ddim_sigmas)[index]
+        nkey = x_info.get('noise_key', None)
+        if nkey is not None and noise_dropout > 0.:
+            raise ValueError("noise_dropout > 0 is not available with x_info['noise_key']")
+        if nkey is not None and float(sig) != 0.:
+            x_prev, pred_x0, _ = ops.cfg_ddim_step(eps, nb, xf, coef, want_next=False, noise_key=nkey, step=index,
+                                                   noise_mul=temperature)
+            return x_prev.to(x.dtype), pred_x0.to(x.dtype)
         if float(sig) != 0.:
             noise = (noise_like(xf, repeat_noise) * temperature).contiguous()
             if noise_dropout > 0.:
@@ -313,7 +342,8 @@ class DDIMSampler(object):
     share_cfg_prefix = True
 
     def enable_graph(self, on=True):
-        """Replay the whole DDIM trajectory as one captured hipGraph (eta = 0 only).  The graph is
+        """Replay the whole DDIM trajectory as one captured hipGraph (eta = 0, or any eta with the seeded noise of
+        x_info['noise_key']).  The graph is
         keyed by shapes / step count / guidance scale / the identity+version of every model
         parameter, so a weight hot-swap (app.py:139-177) re-captures instead of replaying stale
         packed weights.  Static input buffers are owned by the sampler."""
@@ -325,21 +355,22 @@ class DDIMSampler(object):
         from ..hip.layers import generation
         return hash((generation(),) + tuple((p.data_ptr(), p._version) for p in self.model.parameters()))
 
-    def _capture(self, run_loop, x, c_in, hint, keep):
+    def _capture(self, run_loop, x, c_in, hint, keep, nkey=None):
         from ..hip import binding
         binding.prof_enable(False)  # event timing cannot be captured
         sx, sc = x.clone(), c_in.clone()
         sh = hint.clone() if hint is not None else None
+        sk = nkey.clone() if nkey is not None else None
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):     # warm-up outside capture: packs weights, sizes the allocator
-            run_loop(sx, sc, sh)
+            run_loop(sx, sc, sh, sk)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            outs = run_loop(sx, sc, sh)
-        return g, sx, sc, sh, outs, keep
+            outs = run_loop(sx, sc, sh, sk)
+        return g, sx, sc, sh, outs, keep, sk
 
     @ops.serialised
     @torch.no_grad()
@@ -369,6 +400,13 @@ class DDIMSampler(object):
         coef = self._coef_table(scale, use_original_steps)[index]
         noise = None
         sig = (self.ddim_sigmas_for_original_num_steps if use_original_steps else self.ddim_sigmas)[index]
+        nkey = x_info.get('noise_key', None)
+        if nkey is not None and noise_dropout > 0.:
+            raise ValueError("noise_dropout > 0 is not available with x_info['noise_key']")
+        if nkey is not None and float(sig) != 0.:
+            x_prev, pred_x0, _ = ops.cfg_ddim_step(eps, nb, xf, coef, want_next=False, noise_key=nkey, step=index,
+                                                   noise_mul=temperature)
+            return x_prev.to(x.dtype), pred_x0.to(x.dtype)
         if float(sig) != 0.:
             noise = (noise_like(xf, repeat_noise) * temperature).contiguous()
             if noise_dropout > 0.:

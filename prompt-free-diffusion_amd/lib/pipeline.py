@@ -58,6 +58,15 @@ def shard_xT(n_global, height, width, seed, rank, world_size):
     return torch.randn([n_global, 4, height // 8, width // 8], generator=g)[rank * n:(rank + 1) * n]
 
 
+def shard_noise_keys(n_global, seed, rank, world_size):
+    """rank's rows of the seeded-noise keys of the GLOBAL batch: sample j gets (seed, j) whatever P is (lib/noise.py),
+    int64 [n_local, 2] on the CPU"""
+    assert n_global % world_size == 0, "global batch must divide over the ranks"
+    from .noise import sample_keys
+    n = n_global // world_size
+    return torch.from_numpy(sample_keys(seed, rank * n, n))
+
+
 def force_collective():
     """PFD_FORCE_COLLECTIVE=1 with an initialised process group: the collectives run even at world size 1 -- the
     one-GPU RCCL smoke (tests/test_hip_parity.py::test_rccl_one_rank_collectives, `bench.py --gpus 1` under that
@@ -206,13 +215,17 @@ class PromptFreePipeline:
     @serialised
     @torch.no_grad()
     def generate(self, image, n_global, height, width, steps=50, scale=2.0, eta=0.0, seed=20, control=None,
-                 uncond=None, decode=True, gather=False, verbose=False, timings=None, as_uint8=False):
+                 uncond=None, decode=True, gather=False, verbose=False, timings=None, as_uint8=False,
+                 device_noise=False):
         """returns (images, latents [n_local,4,h,w]); images = [n_local | n_global (gather), 3, H, W] in [0,1]
         in the model dtype, or -- as_uint8 -- packed uint8 [n, H, W, 3] (the bytes ToPILImage would produce,
         app.py:273-275; 4x fewer bytes through the all-gather); decode=False returns the latents twice.
         `image` and `control` may each be a uint8 HWC picture of any size instead of a float tensor (`ingest`): the
         reference picture is converted as it is and shared by all samples, the control picture is resized to
-        (height, width) first"""
+        (height, width) first.
+        device_noise: the per-step noise of eta > 0 is the seeded counter-based noise of lib/noise.py, sample j of the
+        GLOBAL batch keyed (seed, j), evaluated inside the DDIM step kernel: the result does not depend on the world
+        size (like x_T) and the loop replays as a hipGraph.  False: the reference's draw from the global generator."""
         P, r = self.world_size, self.rank
         dev = self.net.device
         u8_image, u8_control = image_io.wants_ingest(image), control is not None and image_io.wants_ingest(control)
@@ -241,6 +254,8 @@ class PromptFreePipeline:
         if mk:
             mk.mark()
         x_info = {'type': 'image', 'xt': xT.to(dev)}
+        if device_noise:
+            x_info['noise_key'] = shard_noise_keys(n_global, seed, r, P).to(dev)
         c_info = {'type': 'image', 'conditioning': cond, 'unconditional_conditioning': uncond,
                   'unconditional_guidance_scale': scale}
         if control is not None:

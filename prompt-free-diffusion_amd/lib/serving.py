@@ -4,8 +4,8 @@ The reference serves requests by letting Gradio's worker threads call `action_in
 model with no lock and one request = one `sampler.sample` of `n_sample_image` samples (app.py:229-277,
 405-410).  Here every request goes through a FIFO; one worker thread owns the device and
 
-  * coalesces compatible queued requests (same output size, step count, guidance scale, eta, control /
-    unconditional-context kind) into ONE DDIM batch: samples are independent on this path, every sample
+  * coalesces compatible queued requests (same output size, step count, guidance scale, eta, noise kind, control /
+    unconditional-context kind) into ONE DDIM batch (eta > 0 only with `device_noise=True`, see `shareable`): samples are independent on this path, every sample
     carries its own SeeCoder context in the cross-attention K / V^T cache, so four single-image requests
     cost one batch-4 loop instead of four batch-1 loops (the UNet at batch 2 fills 1/4 of the chip);
   * applies weight hot swaps (`load`, the per-request tag switches of app.py:217-222) strictly in queue
@@ -21,12 +21,12 @@ from concurrent.futures import Future
 import torch
 
 from . import image_io
-from .pipeline import PromptFreePipeline, shard_xT
+from .pipeline import PromptFreePipeline, shard_noise_keys, shard_xT
 
 
 class _Request:
     __slots__ = ("image", "n", "height", "width", "steps", "scale", "eta", "seed", "control", "uncond", "as_uint8",
-                 "future")
+                 "device_noise", "future")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -35,12 +35,14 @@ class _Request:
     def key(self):
         """requests with equal keys can share one DDIM batch"""
         return (self.height, self.width, self.steps, float(self.scale), float(self.eta), self.control is None,
-                self.uncond is None, bool(self.as_uint8))
+                self.uncond is None, bool(self.as_uint8), bool(self.device_noise))
 
     def shareable(self):
-        """eta > 0 draws its noise from the global RNG inside the loop (ddim.py:166): batched with other requests the
-        draw -- and so the result for a given seed -- would depend on the company; such requests run alone, seeded"""
-        return float(self.eta) == 0.0 and self.control is None
+        """eta > 0 WITHOUT device_noise draws its noise from the global RNG inside the loop (ddim.py:166): batched with
+        other requests the draw -- and so the result for a given seed -- would depend on the company; such requests run
+        alone, seeded.  With device_noise the noise of sample j is a function of (request seed, j, step, element)
+        (lib/noise.py), whatever it is batched with: shareable at any eta.  ControlNet requests always run alone."""
+        return (float(self.eta) == 0.0 or bool(self.device_noise)) and self.control is None
 
 
 class PromptFreeServer:
@@ -57,11 +59,14 @@ class PromptFreeServer:
 
     # ---- client side (any thread) -------------------------------------------------------------------
     def submit(self, image, n_samples=1, height=512, width=512, steps=50, scale=2.0, eta=0.0, seed=20,
-               control=None, uncond=None, as_uint8=True):
+               control=None, uncond=None, as_uint8=True, device_noise=False):
         """image [1,3,h,w] in [0,1] (any size); control [1,3,H,W] or None; uncond [1,148,768] or None (zeros).
         image and control may each be a uint8 HWC picture [h,w,3] (torch or numpy, any size; the reference picture
         at least 32 a side) instead: the request carries the bytes and the worker converts them on the device
         (PromptFreePipeline.ingest), the control picture resized to (height, width) as app.py:232 does.
+        device_noise: with eta > 0, sample j of the request draws the seeded noise keyed (seed, j) inside the step kernel
+        (lib/noise.py) instead of the global generator: its images do not depend on what it was batched with, so such
+        requests are coalesced like eta = 0 ones.
         -> Future of uint8 [n,H,W,3] (as_uint8) or float [n,3,H,W] images"""
         if self._stop:
             raise RuntimeError("server is closed")
@@ -88,7 +93,7 @@ class PromptFreeServer:
             raise ValueError(f"control must be a float tensor [1, 3, {height}, {width}] or a uint8 picture [h, w, 3]")
         r = _Request(image=image, n=int(n_samples), height=int(height), width=int(width), steps=int(steps),
                      scale=scale, eta=eta, seed=int(seed), control=control, uncond=uncond, as_uint8=as_uint8,
-                     future=Future())
+                     device_noise=bool(device_noise), future=Future())
         self._q.put(r)
         return r.future
 
@@ -181,23 +186,27 @@ class PromptFreeServer:
         r0 = batch[0]
         dev = self.net.device
         with DEVICE_LOCK:
-            if float(r0.eta) != 0.0:       # runs alone (shareable()): its noise stream is a function of ITS seed only
-                torch.manual_seed(r0.seed)
-            conds, xts, unconds = [], [], []
+            if float(r0.eta) != 0.0 and not r0.device_noise:   # runs alone (shareable()): its noise stream is a function
+                torch.manual_seed(r0.seed)                      # of ITS seed only
+            conds, xts, unconds, keys = [], [], [], []
             for r in batch:
                 img = self.pipe.ingest(r.image) if image_io.wants_ingest(r.image) else r.image.to(dev)
                 c, z = self.pipe.encode_reference(img, r.n)
                 conds.append(c)
                 unconds.append(z if r.uncond is None else r.uncond.to(dev).to(c.dtype).expand(r.n, -1, -1))
                 xts.append(shard_xT(r.n, r.height, r.width, r.seed, 0, 1))      # each request keeps ITS x_T stream
+                keys.append(shard_noise_keys(r.n, r.seed, 0, 1))                # ... and ITS noise keys (seed, j)
             cond, uncond, xT = torch.cat(conds), torch.cat(unconds), torch.cat(xts).to(dev)
             c_info = {'type': 'image', 'conditioning': cond, 'unconditional_conditioning': uncond,
                       'unconditional_guidance_scale': r0.scale}
             if r0.control is not None:
                 c_info['control'] = (self.pipe.ingest(r0.control, (r0.height, r0.width), 'control')
                                      if image_io.wants_ingest(r0.control) else r0.control.to(dev))
-            x, _ = self.pipe.sampler.sample(steps=r0.steps, shape=list(xT.shape), x_info={'type': 'image', 'xt': xT},
-                                            c_info=c_info, eta=r0.eta, verbose=False)
+            x_info = {'type': 'image', 'xt': xT}
+            if r0.device_noise:
+                x_info['noise_key'] = torch.cat(keys).to(dev)
+            x, _ = self.pipe.sampler.sample(steps=r0.steps, shape=list(xT.shape), x_info=x_info, c_info=c_info,
+                                            eta=r0.eta, verbose=False)
             img = self.net.vae_decode(x, 'image', out_uint8=True) if r0.as_uint8 else self.net.vae_decode(x, 'image')
             self.batches.append(int(xT.shape[0]))
         outs, off = [], 0
