@@ -541,15 +541,23 @@ def attention(q, k, vt, B, H, Nq, Nk, D, scale, *, ldq, ldk, ldvt, q_bs, k_bs, v
     return out
 
 
-def swin_window_attention(qkv, qkv_bias, rpb, B, H, W_, Cdim, nH, ws, shift, scale):
+def swin_window_attention(qkv, qkv_bias, rpb, B, H, W_, Cdim, nH, ws, shift, scale, out=None):
+    """qkv [B*H*W, 3C] token-major (dense), qkv_bias [3C], rpb [(2 ws - 1)^2, nH] -> out [B*H*W, C] (dense); see
+    pfd_swin_window_attention_f16"""
     _chk16(qkv, "swin qkv")
-    out = torch.empty((B * H * W_, Cdim), dtype=torch.float16, device=qkv.device)
+    if out is None:
+        out = torch.empty((B * H * W_, Cdim), dtype=torch.float16, device=qkv.device)
+    else:
+        _chk16(out, "swin out")
+        if out.device != qkv.device or tuple(out.shape) != (B * H * W_, Cdim) or not out.is_contiguous():
+            raise ValueError(f"swin_window_attention: out {tuple(out.shape)} on {out.device} is not a dense "
+                             f"[{B * H * W_}, {Cdim}] on {qkv.device}")
     d = _b.PfdSwinAttnDesc()
     d.qkv, d.qkv_bias, d.rpb, d.out = qkv.data_ptr(), qkv_bias.data_ptr(), rpb.data_ptr(), out.data_ptr()
     d.B, d.H, d.W, d.C, d.nH, d.ws, d.shift = B, H, W_, Cdim, nH, ws, shift
     d.scale = scale
     _b.check(_lib().pfd_swin_window_attention_f16(_byref(d), _stream()), "pfd_swin_window_attention_f16")
-    return out
+    return _written(out)
 
 
 # ----------------------------------------------------------------------------------------------
