@@ -528,9 +528,18 @@ def conv_narrow(x, w, ksize, *, stride=1, pad=None, bias=None, rowvec=None, res=
 # attention
 # ----------------------------------------------------------------------------------------------
 def attention(q, k, vt, B, H, Nq, Nk, D, scale, *, ldq, ldk, ldvt, q_bs, k_bs, vt_bs, out=None):
-    """Fused attention; see pfd_attention_f16.  q/k/vt may be views into wider buffers."""
+    """Fused attention; see pfd_attention_f16.  q/k/vt may be views into wider buffers; out (optional): [>= B*Nq, >= H*D]
+    rows of stride % 8 == 0 (a column slice of a wider matrix is fine), the first B*Nq rows and H*D columns are written."""
+    _chk16(q, "attention q")
+    _chk16(k, "attention k")
+    _chk16(vt, "attention vt")
     if out is None:
         out = torch.empty((B * Nq, H * D), dtype=torch.float16, device=q.device)
+    else:
+        _chk16(out, "attention out")
+        if out.device != q.device or out.dim() != 2 or out.shape[0] < B * Nq or out.shape[1] < H * D or out.stride(-2) % 8:
+            raise ValueError(f"attention: out {tuple(out.shape)} strides {out.stride()} on {out.device} is not a matrix of at "
+                             f"least [{B * Nq}, {H * D}] with a row stride that is a multiple of 8 on {q.device}")
     d = _b.PfdAttnDesc()
     d.Q, d.K, d.Vt, d.O = q.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr()
     d.ldq, d.ldk, d.ldvt, d.ldo = ldq, ldk, ldvt, out.stride(-2)

@@ -1,6 +1,7 @@
-"""Plain fp64 references of single kernels of the SeeCoder side of the library, and the seeded operands the kernel-level
-tests run them on (tests/test_encoder_kernels_cpu.py pins the references to the oracle, tests/test_encoder_kernels_gpu.py
-compares the HIP kernels with them).  Everything here is torch on whatever device the operands live on; nothing imports the
+"""Plain fp64 references of single kernels of the library, and the seeded operands the kernel-level tests run them on: the
+SeeCoder side (tests/test_encoder_kernels_cpu.py pins the references to the oracle, tests/test_encoder_kernels_gpu.py
+compares the HIP kernels with them) and the fused attention family (tests/test_attention_kernels_{cpu,gpu}.py, the last
+section).  Everything here is torch on whatever device the operands live on; nothing imports the
 native library.  A plain module, not a conftest: the two test files import it by name."""
 import functools
 
@@ -212,3 +213,262 @@ def bound_ratio(got, ref, a):
     err = (got - ref).abs()
     used = float(((err - round_once_bound(ref, a) + a) / a).clamp_min(0).max())
     return float((err / round_once_bound(ref, a)).max()), used
+
+
+# ------------------------------------------------------------------------------------------------
+# fused attention (pfd_attention_f16): references, the dispatcher restated, cases and operands
+# (tests/test_attention_kernels_cpu.py pins and qualifies them, tests/test_attention_kernels_gpu.py uses them)
+# ------------------------------------------------------------------------------------------------
+LOG2E = 1.4426950408889634
+ATTN_MUTANTS = ("last_key_dropped", "masked_keys_score_zero", "vt_batch0", "k_batch0", "v_pad_column_read")
+ATTN_CLASSES = ("w4", "w8", "a3", "d80", "d96", "d160", "d512_2", "d512_4")
+ATTN_FOLDED = ("w8", "a3")          # Q' = fp16(q * scale * log2 e), softmax as exp2 of the raw products
+
+
+def attention_kernel_class(B, H, Nq, Nk, D, slices=2):
+    """which kernel pfd_attention_f16 launches: csrc/attention.hip launch<D>() (the `big` / `w8` lines), launch512() and the
+    switch of pfd_attention_f16, and pfd_attention3_takes() at the end of csrc/attention3_kernel.h, restated without the
+    process-static test hooks.  None: PFD_ESHAPE."""
+    if D == 512:
+        return f"d512_{4 if slices == 4 else 2}" if H == 1 and Nk % 32 == 0 else None
+    if D in (80, 96, 160):
+        return f"d{D}"
+    if D != 40:
+        return None
+    blocks = B * H * ((Nq + 255) // 256)
+    if Nk % 64 == 0 and Nk >= 128 and Nq >= 256 and blocks >= 256:
+        return "a3"
+    if Nq >= 1024 and blocks >= 512:
+        return "w8"
+    return "w4"
+
+
+# (B, H, Nq, Nk, D, layout, spike); layouts: dense | fused_qk | vt_offset | shared_kv (attention_problem)
+ATTN_CASES = [
+    # w4: attention2_kernel<40, 4, false>
+    (2, 2, 77, 64, 40, "fused_qk", 0),          # exactly one full tile
+    (1, 2, 300, 148, 40, "dense", 0),
+    (1, 1, 33, 1, 40, "dense", 0),              # one key
+    (1, 1, 1, 7, 40, "dense", 0),               # one query, Nk below 8: v_last = 0
+    (1, 1, 256, 65, 40, "dense", 0),            # one key in the peeled tile
+    (1, 2, 130, 127, 40, "dense", 0),
+    (1, 2, 130, 129, 40, "vt_offset", 0),
+    (3, 2, 64, 148, 40, "shared_kv", 0),
+    (1, 2, 300, 148, 40, "dense", 140),         # spike inside the peeled tile
+    # w8: attention2_kernel<40, 8, true, true>
+    (16, 8, 1024, 148, 40, "vt_offset", 0),
+    (13, 8, 1030, 77, 40, "dense", 0),          # ragged last query block, 520 blocks
+    (16, 8, 1024, 64, 40, "dense", 0),          # one full tile (a3 declines below 128 keys)
+    (16, 8, 1024, 8, 40, "dense", 0),
+    (16, 8, 1024, 200, 40, "dense", 0),
+    (16, 8, 1024, 200, 40, "dense", 130),
+    (16, 8, 1024, 148, 40, "vt_offset", 140),
+    # a3: attention3_kernel; 2, 3, 4, 5, 9 key tiles around the ring depths (5 / 4) and the pair parity
+    (32, 8, 256, 128, 40, "dense", 0),
+    (32, 8, 256, 192, 40, "fused_qk", 0),
+    (32, 8, 256, 256, 40, "dense", 0),
+    (32, 8, 256, 320, 40, "fused_qk", 0),
+    (32, 8, 256, 576, 40, "dense", 0),
+    (16, 8, 300, 192, 40, "dense", 0),          # second block: 44 valid queries, whole sub-blocks and waves past Nq
+    (8, 8, 1024, 1024, 40, "fused_qk", 0),
+    (32, 8, 256, 320, 40, "fused_qk", 200),
+    (32, 8, 256, 256, 40, "dense", 100),
+    (8, 8, 1024, 1024, 40, "fused_qk", 700),
+    # d80 / d96 / d160: attention2_kernel<D, 4, false>
+    (2, 2, 64, 64, 80, "dense", 0), (1, 2, 150, 148, 80, "dense", 0), (1, 1, 40, 1, 80, "dense", 0),
+    (1, 2, 150, 148, 80, "dense", 100),
+    (1, 8, 144, 256, 96, "dense", 0), (1, 3, 148, 148, 96, "dense", 0), (1, 2, 144, 200, 96, "dense", 0),
+    (2, 2, 64, 148, 160, "dense", 0), (1, 1, 256, 320, 160, "fused_qk", 0), (1, 2, 70, 8, 160, "dense", 0),
+    # d512: attention512_kernel<2 / 4> (the GPU file runs each with PFD_ATTN512_SLICES = 2 and 4)
+    (1, 1, 128, 32, 512, "dense", 0),           # one key tile
+    (1, 1, 200, 96, 512, "dense", 0),           # ragged query tile
+    (2, 1, 128, 512, 512, "fused_qk", 0),
+    (1, 1, 128, 512, 512, "dense", 300),
+]
+# operand variants on top of a case (attention_problem(case, variant))
+ATTN_STAIRCASE = [(16, 8, 1024, 200, 40, "dense", 0), (32, 8, 256, 320, 40, "fused_qk", 0)]       # w8, a3
+ATTN_PEAKED = [(1, 2, 300, 148, 40, "dense", 0), (16, 8, 1024, 200, 40, "dense", 0), (32, 8, 256, 320, 40, "fused_qk", 0),
+               (1, 2, 150, 148, 80, "dense", 0), (1, 3, 148, 148, 96, "dense", 0), (2, 2, 64, 148, 160, "dense", 0),
+               (1, 1, 200, 96, 512, "dense", 0)]                                                    # one per class
+
+
+def attn_case_id(case):
+    B, H, Nq, Nk, D, layout, spike = case
+    return f"B{B}H{H}q{Nq}k{Nk}d{D}-{layout}" + (f"-spike{spike}" if spike else "")
+
+
+def _attn_views(q, k, vt, B, H, Nq, Nk, D, ldq, ldk, ldvt, q_bs, k_bs, vt_bs, q_off, k_off, vt_off):
+    """[B, H, N, D] views of the three flat buffers by the address formulas of include/pfd_hip.h (PfdAttnDesc)"""
+    Q = q.as_strided((B, H, Nq, D), (q_bs, D, ldq, 1), q.storage_offset() + q_off)
+    K = k.as_strided((B, H, Nk, D), (k_bs, D, ldk, 1), k.storage_offset() + k_off)
+    V = vt.as_strided((B, H, Nk, D), (vt_bs, D * ldvt, 1, ldvt), vt.storage_offset() + vt_off)
+    return Q, K, V
+
+
+def _attention(q, k, vt, B, H, Nq, Nk, D, scale, ldq, ldk, ldvt, q_bs, k_bs, vt_bs, q_off, k_off, vt_off, mutant, folded,
+               dtype=torch.float64):
+    assert mutant is None or mutant in ATTN_MUTANTS
+    if mutant == "vt_batch0":
+        vt_bs = 0
+    if mutant == "k_batch0":
+        k_bs = 0
+    nk = Nk - 1 if mutant == "last_key_dropped" and Nk > 1 else Nk
+    Nkp = (Nk + 7) // 8 * 8
+    if mutant == "v_pad_column_read":        # key j reads the column of key j + (Nkp - Nk): the last ones read the pad
+        Q, K, V = _attn_views(q, k, vt, B, H, Nq, Nk, D, ldq, ldk, ldvt, q_bs, k_bs, vt_bs, q_off, k_off, vt_off + Nkp - Nk)
+    else:
+        Q, K, V = _attn_views(q, k, vt, B, H, Nq, nk, D, ldq, ldk, ldvt, q_bs, k_bs, vt_bs, q_off, k_off, vt_off)
+    npad = (-Nk) % 64 if mutant == "masked_keys_score_zero" else 0
+    # the kernels' factor: the fp32 product of fp32(scale) and fp32(log2 e) (pfd_attention_f16: d->scale * 1.4426950408889634f)
+    c32 = float(torch.tensor(scale, dtype=torch.float32) * torch.tensor(LOG2E, dtype=torch.float32))
+    out = torch.empty((B, Nq, H * D), dtype=dtype, device=q.device)
+    hc = max(1, min(H, (256 << 20) // (8 * Nq * (Nk + npad))))            # heads per chunk: scores below about 256 MB
+    for b in range(B):
+        for h0 in range(0, H, hc):
+            qc, kc, vc = Q[b, h0:h0 + hc], K[b, h0:h0 + hc].to(dtype), V[b, h0:h0 + hc].to(dtype)
+            if folded:      # the kernels' operand: fp16(fp32(q) * fp32(scale * log2 e)); scores in log2 units
+                qc = (qc.float() * c32).half().to(dtype)
+                s = qc @ kc.transpose(-1, -2)
+            else:
+                s = (qc.to(dtype) @ kc.transpose(-1, -2)) * scale
+            if npad:
+                s = torch.cat([s, s.new_zeros(s.shape[:-1] + (npad,))], -1)
+                vc = torch.cat([vc, vc.new_zeros(vc.shape[:-2] + (npad, D))], -2)
+            if folded:
+                p = torch.exp2(s - s.amax(-1, keepdim=True))
+                p = p / p.sum(-1, keepdim=True)
+            else:
+                p = s.softmax(-1)
+            out[b, :, h0 * D:(h0 + len(qc)) * D] = (p @ vc).transpose(0, 1).reshape(Nq, -1)
+    return out
+
+
+def attention_ref(q, k, vt, B, H, Nq, Nk, D, scale, *, ldq, ldk, ldvt, q_bs, k_bs, vt_bs, q_off=0, k_off=0, vt_off=0,
+                  mutant=None, dtype=torch.float64):
+    """softmax_j(scale <Q[b,i,h], K[b,j,h]>) . V[b,j,h] in fp64 -> [B, Nq, H * D].  q / k / vt are the flat fp16 buffers (or
+    views into them; *_off are further element offsets), indexed by the address formulas of include/pfd_hip.h with
+    as_strided -- the strides are part of what is under test.  mutant: one of ATTN_MUTANTS, a deliberately wrong variant."""
+    return _attention(q, k, vt, B, H, Nq, Nk, D, scale, ldq, ldk, ldvt, q_bs, k_bs, vt_bs, q_off, k_off, vt_off, mutant, False,
+                      dtype)
+
+
+def attention_ref_folded(q, k, vt, B, H, Nq, Nk, D, scale, *, ldq, ldk, ldvt, q_bs, k_bs, vt_bs, q_off=0, k_off=0, vt_off=0,
+                         mutant=None):
+    """the same with the operand quantisation of the folded-maximum kernels (csrc/attention.hip, the FOLD comment and the
+    query fragment load): Q' = fp16(fp32(q) * fp32(scale * log2 e)), p = exp2(<Q', K> - max); every other step in fp64"""
+    return _attention(q, k, vt, B, H, Nq, Nk, D, scale, ldq, ldk, ldvt, q_bs, k_bs, vt_bs, q_off, k_off, vt_off, mutant, True)
+
+
+def attention_fold_amplitude(q, k, B, H, Nq, Nk, D, scale, *, ldq, ldk, q_bs, k_bs, q_off=0, k_off=0, **_):
+    """A = max over the launch of sum_e |q'_e k_e|, q' = q * scale * log2 e, in fp64: the worst case of rounding Q' to fp16 is
+    a score error of 2^-11 A (log2 units)"""
+    Q = q.as_strided((B, H, Nq, D), (q_bs, D, ldq, 1), q.storage_offset() + q_off)
+    K = k.as_strided((B, H, Nk, D), (k_bs, D, ldk, 1), k.storage_offset() + k_off)
+    a = 0.0
+    for b in range(B):
+        a = max(a, float((Q[b].double().abs() @ K[b].double().abs().transpose(-1, -2)).max()))
+    return a * scale * LOG2E
+
+
+# The GPU bound, per element, relative to vmax = the largest |V| among the valid keys of the launch (the output is a convex
+# combination of V values):
+#   2^-11   P = exp2(s - m) is rounded to fp16 once; every p_j is off by at most 2^-11 relative, so the numerator
+#           sum_j p_j v_j moves by at most 2^-11 vmax sum_j p_j
+#   2^-11   the row sum carries the same rounding (the ones row sums the rounded P; the register sum the unrounded one)
+#   2^-11   the result is rounded to fp16 once (half an ulp of a value <= vmax)
+#   Nk 2^-25  a P value below 2^-14 is subnormal in fp16 and loses up to 2^-25 absolutely, against a row sum >= 1
+#   2^-16   fp32 score accumulation, the fma in front of v_exp_f32 and v_exp_f32 itself (1 ulp)
+# The folded kernels round Q' = q scale log2(e) to fp16: a score moves by at most 2^-11 sum_e |q'_e k_e| <= 2^-11 A (log2
+# units), a probability by the factor 2^(+-2^-11 A), numerator against denominator by twice that: 2 ln2 2^-11 A vmax.
+def attention_bound(Nk, vmax, A=0.0):
+    return (3 * 2.0 ** -11 + Nk * 2.0 ** -25 + 2.0 ** -16 + 2 * 0.6931471805599453 * 2.0 ** -11 * A) * vmax
+
+
+_POISON = torch.tensor([0x7E00, -0x0200, 0x7C01, 0x7FFF], dtype=torch.int16)     # fp16 NaNs: quiet, negative, signalling, all ones
+
+
+def _poisoned(n):
+    return _POISON.repeat(-(-n // 4))[:n].clone().view(torch.float16)
+
+
+@functools.lru_cache(maxsize=None)
+def attention_problem(case, variant=None):
+    """the fp16 operands of one case (CPU; seeded from the case; Q, K = 1.5 randn, V = randn: csrc/selftest.cpp's
+    distributions) as flat buffers `q`, `k`, `vt` plus `desc`, the keyword arguments of ops.attention / attention_ref.
+    Every element a launch may read but must not use is an fp16 NaN: V^T columns Nk .. Nkp, K pad rows, the rows of a fused
+    [B N, 2C] matrix beyond Nq (Q half) / Nk (K half), the skipped leading sample; `*_valid` are the masks of the rest.
+    variant: None | "peaked" (four query rows x 6) | "staircase" (the tile maximum rises by 5 log2 units per 64-key tile).
+    Do not modify the result."""
+    B, H, Nq, Nk, D, layout, spike = case
+    C, Nkp, scale = H * D, (Nk + 7) // 8 * 8, D ** -0.5
+    g = torch.Generator().manual_seed(((((B * 131 + H) * 131 + Nq) * 131 + Nk) * 131 + D) * 7 + spike + 1000003 * len(layout))
+    Q = 1.5 * torch.randn((B, Nq, C), generator=g)
+    Bk = 1 if layout == "shared_kv" else B
+    K = 1.5 * torch.randn((Bk, Nk, C), generator=g)
+    V = torch.randn((Bk, Nk, C), generator=g)
+    if variant == "peaked":
+        Q[:, sorted({0, min(17, Nq - 1), Nq // 2, Nq - 1})] *= 6.0
+    if variant == "staircase":
+        # every query and key of a head along one sign vector u (|u|^2 = D): s' = beta_i alpha_j D c, c = scale log2 e.
+        # alpha_j puts key j of tile t at 5 t - (0 .. 3) log2 units for beta = 1; beta within 2 % of 1, so an odd tile tops
+        # out at +5.1 above the folded maximum (no rescale, P up to 2^5.1) and an even tile at +10.2 (rescale)
+        u = torch.sign(torch.randn((1, 1, C), generator=g))
+        beta = 1 + 0.02 * (2 * torch.rand((B, Nq, 1), generator=g) - 1)
+        j = torch.arange(Nk)
+        target = 5.0 * (j // 64) - 3.0 * torch.rand((Bk, Nk), generator=g)
+        target[:, j % 64 == 0] = 5.0 * (j // 64)[j % 64 == 0]                # the first key of a tile is its top
+        Q, K = beta * u, (target / (D * scale * LOG2E))[:, :, None] * u
+    Q, K, V = Q.half(), K.half(), V.half()
+    if spike:
+        assert Bk == B
+        K[:, spike] = (4.0 * Q[:, spike % Nq].float()).half()
+    vmax = float(V.abs().max())
+    desc = dict(ldq=C, ldk=C, ldvt=Bk * Nkp, q_bs=Nq * C, k_bs=Nk * C, vt_bs=Nkp, q_off=0, k_off=0, vt_off=0)
+    z = 1 if layout == "vt_offset" else 0                                   # skipped leading samples of K and V^T
+    vt = _poisoned(C * (Bk + z) * Nkp).view(C, Bk + z, Nkp)
+    vt_valid = torch.zeros(vt.shape, dtype=torch.bool)
+    vt[:, z:, :Nk] = V.permute(2, 0, 1)
+    vt_valid[:, z:, :Nk] = True
+    if layout == "fused_qk":
+        N = max(Nq, Nk)
+        qk = _poisoned(B * N * 2 * C).view(B, N, 2 * C)
+        qk_valid = torch.zeros(qk.shape, dtype=torch.bool)
+        qk[:, :Nq, :C], qk[:, :Nk, C:] = Q, K
+        qk_valid[:, :Nq, :C] = True
+        qk_valid[:, :Nk, C:] = True
+        q = k = qk.reshape(-1)
+        q_valid = k_valid = qk_valid.reshape(-1)
+        desc.update(ldq=2 * C, ldk=2 * C, q_bs=N * 2 * C, k_bs=N * 2 * C, k_off=C)
+    else:
+        q, q_valid = Q.reshape(-1).clone(), torch.ones(B * Nq * C, dtype=torch.bool)
+        if layout == "vt_offset":
+            kb = _poisoned((B + 1) * Nkp * C).view(B + 1, Nkp, C)
+            kv = torch.zeros(kb.shape, dtype=torch.bool)
+            kb[1:, :Nk] = K
+            kv[1:, :Nk] = True
+            k, k_valid = kb.reshape(-1), kv.reshape(-1)
+            desc.update(k_bs=Nkp * C, k_off=Nkp * C, ldvt=(B + 1) * Nkp, vt_off=Nkp)
+        else:
+            k, k_valid = K.reshape(-1).clone(), torch.ones(Bk * Nk * C, dtype=torch.bool)
+            if layout == "shared_kv":
+                assert B > 1
+                desc.update(k_bs=0, vt_bs=0)
+            else:
+                assert layout == "dense", layout
+    return dict(q=q, k=k, vt=vt.reshape(-1), q_valid=q_valid, k_valid=k_valid, vt_valid=vt_valid.reshape(-1), desc=desc,
+                scale=scale, vmax=vmax, dims=(B, H, Nq, Nk, D))
+
+
+def attention_densified(p):
+    """the same problem as contiguous [B, Nq, C] / [B, Nk, C] / [C, B, Nk8] operands with the dense descriptor (copies taken
+    element by element through the address formulas)"""
+    B, H, Nq, Nk, D = p["dims"]
+    d = p["desc"]
+    C, Nkp = H * D, (Nk + 7) // 8 * 8
+    Q, K, V = _attn_views(p["q"], p["k"], p["vt"], B, H, Nq, Nk, D, d["ldq"], d["ldk"], d["ldvt"], d["q_bs"], d["k_bs"], d["vt_bs"],
+                          d["q_off"], d["k_off"], d["vt_off"])
+    q = Q.permute(0, 2, 1, 3).reshape(-1)
+    k = K.permute(0, 2, 1, 3).reshape(-1)
+    vt = torch.zeros((C, B, Nkp), dtype=torch.float16)
+    vt[:, :, :Nk] = V.permute(1, 3, 0, 2).reshape(C, B, Nk)
+    return q, k, vt.reshape(-1), dict(ldq=C, ldk=C, ldvt=B * Nkp, q_bs=Nq * C, k_bs=Nk * C, vt_bs=Nkp)
