@@ -444,7 +444,7 @@ extern "C" int pfd_gemm_f16_ex(const PfdGemmDesc* d, int32_t tile, pfd_stream_t 
   if (!d || !d->A || !d->W || !d->C) return PFD_EINVAL;
   if (d->M <= 0 || d->N <= 0 || d->K <= 0) return PFD_EINVAL;
   if ((d->lda & 7) || (d->ldw & 7)) return PFD_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(d->A) & 15) || (reinterpret_cast<uintptr_t>(d->W) & 15)) return PFD_EINVAL;
+  if (!aligned16(d->A) || !aligned16(d->W)) return PFD_EINVAL;
   if (d->K % BK) return PFD_ESHAPE;
   if (d->rowvec && d->rows_per_rv < 1) return PFD_EINVAL;
   if (d->act < PFD_ACT_NONE || d->act > PFD_ACT_GEGLU) return PFD_EINVAL;
@@ -507,13 +507,7 @@ extern "C" int pfd_gemm_f16_ex(const PfdGemmDesc* d, int32_t tile, pfd_stream_t 
   p.ksize = d->ksize; p.stride = d->stride; p.pad = d->pad; p.ups = d->ups;
   p.B = d->B; p.H = d->H; p.Wd = d->Wd; p.Cin = d->Cin; p.Ho = d->Ho; p.Wo = d->Wo;
   p.tiles_m = p.tiles_n = 0;
-  if (p.ksize > 0) {
-    if (p.Cin % BK) return PFD_ESHAPE;
-    if (p.K != p.ksize * p.ksize * p.Cin) return PFD_EINVAL;
-    if ((long)p.B * p.Ho * p.Wo != p.M) return PFD_EINVAL;
-    if (p.stride < 1) return PFD_EINVAL;
-  }
-  if (p.act < PFD_ACT_NONE || p.act > PFD_ACT_GEGLU) return PFD_EINVAL;
+  if (p.ksize > 0 && (p.Cin % BK)) return PFD_ESHAPE;   // (K, M, stride and act were checked at the entry)
   hipStream_t s = (hipStream_t)stream;
   if (tile == 0 && narrow_conv_takes(p)) return launch_narrow_conv(p, s);
   if (p.act == PFD_ACT_GEGLU) {

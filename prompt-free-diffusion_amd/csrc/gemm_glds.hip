@@ -1981,24 +1981,20 @@ __global__ __launch_bounds__(GNF_T) void splitk_reduce_gnorm_kernel(const G160Pa
   }
 }
 
-// the fused GroupNorm request of the launch being dispatched on this thread (set by pfd_gemm160_try, consumed by
-// launch_splitk_reduce): kept out of G160Params so that the kernel-argument block of every other kernel -- and with it
-// their hardware-validated instruction streams -- stays what it was
-thread_local GnFuse t_gnf = {nullptr, nullptr, nullptr, 0, 0.f, 0, 0, 0};
-
-// launches the reduction of a split-K launch (plain, or the statistics-emitting form) and the LayerNorm fallback statistics
-inline void launch_splitk_reduce(const G160Params& p, hipStream_t s) {
+// launches the reduction of a split-K launch (plain, the statistics-emitting form, or -- gnf: the fused GroupNorm request of
+// this launch, an argument of its own so that the kernel-argument block of every other kernel stays what it was -- the
+// normalising form) and the LayerNorm fallback statistics
+inline void launch_splitk_reduce(const G160Params& p, const GnFuse* gnf, hipStream_t s) {
   // Round 6: the reduction is timed as its own bucket (it is HBM-bound glue, not part of the GEMM's MFMA time): the caller's
   // event pair is closed here and a new one covers the reduction launch(es); the caller's pfd_prof_end then closes this one.
   // Algorithmic bytes: the fp32 slabs once + the f16 result (+ residual, + the normalised copy of the fused GroupNorm form).
   if (pfd_prof_on()) {
     pfd_prof_end(s);
     const double mn = (double)p.M * p.N;
-    pfd_prof_begin(21, 0.0, 2.0 * p.splits * mn + 2.0 * mn * (1 + (p.R ? 1 : 0) + (t_gnf.y ? 1 : 0)), s);
+    pfd_prof_begin(21, 0.0, 2.0 * p.splits * mn + 2.0 * mn * (1 + (p.R ? 1 : 0) + (gnf ? 1 : 0)), s);
   }
-  if (t_gnf.y) {   // (host: no gn_out / ln_out with it)
-    const GnFuse f = t_gnf;
-    hipLaunchKernelGGL(splitk_reduce_gnorm_kernel, dim3(32 * (p.M / f.rows)), dim3(GNF_T), 0, s, p, f);
+  if (gnf) {   // (host: no gn_out / ln_out with it)
+    hipLaunchKernelGGL(splitk_reduce_gnorm_kernel, dim3(32 * (p.M / gnf->rows)), dim3(GNF_T), 0, s, p, *gnf);
     return;
   }
   if (p.gn_out) {
@@ -2029,86 +2025,93 @@ inline int pick_nmajor(const G160Params& p) {
   return (p.tiles_n >= 2 && p.tiles_m >= 2 && w_bytes > a_bytes) ? 1 : 0;
 }
 
-template <int WAVES_M, int WMB, int NBUF = 2, int NT = 5>
-int launch160(G160Params& p, int bucket, hipStream_t s) {
-  constexpr int BM = WAVES_M * WMB * 16;
-  p.tiles_m = (p.M + BM - 1) / BM;
-  p.tiles_n = p.N / (32 * NT);
+// splits that will really launch: the request turned into whole K tiles per split
+inline int real_splits(int nk, int splits) {
+  const int per = (nk + splits - 1) / splits;
+  return (nk + per - 1) / per;
+}
+
+// What every wide-tile launch shares: tile counts, tile order, the split normalisation, the profiling pair, the split-K
+// reduction and the launch check; `launch(grid)` issues the kernel.  nk: the steps a split divides -- K tiles, or channel
+// blocks (Cin / BK) for the patch kernels, whose splits cut the channel range of every tap.
+template <class Launch>
+int launch_tiles(G160Params& p, int bm, int bn, int nk, int bucket, const char* what, const GnFuse* gnf, hipStream_t s, Launch launch) {
+  p.tiles_m = (p.M + bm - 1) / bm;
+  p.tiles_n = p.N / bn;
   p.nmajor = pick_nmajor(p);
   p.krot = 0;
-  const int nk = p.K / BK;
   p.kt_per_split = (nk + p.splits - 1) / p.splits;
-  p.splits = (nk + p.kt_per_split - 1) / p.kt_per_split;
-  dim3 grid(p.tiles_m * p.tiles_n, 1, p.splits);
+  p.splits = real_splits(nk, p.splits);
   const bool prof = pfd_prof_on();
   if (prof) {
     const double a_bytes = p.ksize > 0 ? 2.0 * p.B * p.H * p.Wd * p.Cin : 2.0 * p.M * p.K;
     const double n_out = p.act == PFD_ACT_GEGLU ? p.N / 2 : p.N;
     pfd_prof_begin(bucket, 2.0 * p.M * p.N * p.K, a_bytes + 2.0 * p.N * p.K + 2.0 * p.M * n_out * (p.R ? 2 : 1), s);
   }
-  if (p.ksize > 0)
-    hipLaunchKernelGGL((gemm160_kernel<WAVES_M, WMB, true, NBUF, NT>), grid, dim3(WAVES_M * 128), 0, s, p);
-  else
-    hipLaunchKernelGGL((gemm160_kernel<WAVES_M, WMB, false, NBUF, NT>), grid, dim3(WAVES_M * 128), 0, s, p);
-  if (p.splits > 1) launch_splitk_reduce(p, s);
+  launch(dim3(p.tiles_m * p.tiles_n, 1, p.splits));
+  if (p.splits > 1) launch_splitk_reduce(p, gnf, s);
   if (prof) pfd_prof_end(s);
-  return pfd_check_launch("pfd_gemm_f16(wide)");
+  return pfd_check_launch(what);
+}
+
+template <int WAVES_M, int WMB, int NBUF = 2, int NT = 5>
+int launch160(G160Params& p, int bucket, const GnFuse* gnf, hipStream_t s) {
+  return launch_tiles(p, WAVES_M * WMB * 16, 32 * NT, p.K / BK, bucket, "pfd_gemm_f16(wide)", gnf, s, [&](dim3 grid) {
+    if (p.ksize > 0)
+      hipLaunchKernelGGL((gemm160_kernel<WAVES_M, WMB, true, NBUF, NT>), grid, dim3(WAVES_M * 128), 0, s, p);
+    else
+      hipLaunchKernelGGL((gemm160_kernel<WAVES_M, WMB, false, NBUF, NT>), grid, dim3(WAVES_M * 128), 0, s, p);
+  });
 }
 
 template <int NT>
 // mode: 0 = two stages, 2 = 3-stage ring
-int launch160ws(G160Params& p, int bucket, hipStream_t s, int pp) {
-  p.tiles_m = (p.M + 255) / 256;
-  p.tiles_n = p.N / (32 * NT);
-  p.nmajor = pick_nmajor(p);
-  p.krot = 0;
-  const int nk = p.K / BK;
-  p.kt_per_split = (nk + p.splits - 1) / p.splits;
-  p.splits = (nk + p.kt_per_split - 1) / p.kt_per_split;
-  dim3 grid(p.tiles_m * p.tiles_n, 1, p.splits);
-  const bool prof = pfd_prof_on();
-  if (prof) {
-    const double a_bytes = p.ksize > 0 ? 2.0 * p.B * p.H * p.Wd * p.Cin : 2.0 * p.M * p.K;
-    const double n_out = p.act == PFD_ACT_GEGLU ? p.N / 2 : p.N;
-    pfd_prof_begin(bucket, 2.0 * p.M * p.N * p.K, a_bytes + 2.0 * p.N * p.K + 2.0 * p.M * n_out * (p.R ? 2 : 1), s);
-  }
-  if (p.ksize > 0 && p.ups == 2) {
-    if (pp == 2) hipLaunchKernelGGL((gemm160ws_kernel<true, NT, 3, true>), grid, dim3(768), 0, s, p);
-    else hipLaunchKernelGGL((gemm160ws_kernel<true, NT, 2, true>), grid, dim3(768), 0, s, p);
-  } else if (p.ksize > 0) {
-    if (pp == 2) hipLaunchKernelGGL((gemm160ws_kernel<true, NT, 3>), grid, dim3(768), 0, s, p);
-    else hipLaunchKernelGGL((gemm160ws_kernel<true, NT>), grid, dim3(768), 0, s, p);
-  } else {
-    if (pp == 2) hipLaunchKernelGGL((gemm160ws_kernel<false, NT, 3>), grid, dim3(768), 0, s, p);
-    else hipLaunchKernelGGL((gemm160ws_kernel<false, NT>), grid, dim3(768), 0, s, p);
-  }
-  if (p.splits > 1) launch_splitk_reduce(p, s);
-  if (prof) pfd_prof_end(s);
-  return pfd_check_launch("pfd_gemm_f16(wave-specialised)");
+int launch160ws(G160Params& p, int bucket, const GnFuse* gnf, hipStream_t s, int pp) {
+  return launch_tiles(p, 256, 32 * NT, p.K / BK, bucket, "pfd_gemm_f16(wave-specialised)", gnf, s, [&](dim3 grid) {
+    if (p.ksize > 0 && p.ups == 2) {
+      if (pp == 2) hipLaunchKernelGGL((gemm160ws_kernel<true, NT, 3, true>), grid, dim3(768), 0, s, p);
+      else hipLaunchKernelGGL((gemm160ws_kernel<true, NT, 2, true>), grid, dim3(768), 0, s, p);
+    } else if (p.ksize > 0) {
+      if (pp == 2) hipLaunchKernelGGL((gemm160ws_kernel<true, NT, 3>), grid, dim3(768), 0, s, p);
+      else hipLaunchKernelGGL((gemm160ws_kernel<true, NT>), grid, dim3(768), 0, s, p);
+    } else {
+      if (pp == 2) hipLaunchKernelGGL((gemm160ws_kernel<false, NT, 3>), grid, dim3(768), 0, s, p);
+      else hipLaunchKernelGGL((gemm160ws_kernel<false, NT>), grid, dim3(768), 0, s, p);
+    }
+  });
 }
 
 // ws: 0 = 8-wave kernel, 1 = + 4 loader waves (two weight stages), 3 = loader waves + 3-stage weight ring (the default)
-int launch_patch(G160Params& p, hipStream_t s, int ws) {
-  p.tiles_m = p.M / 256;
-  p.tiles_n = p.N / BN;
-  p.nmajor = pick_nmajor(p);
-  p.krot = 0;
-  const int ncb = p.Cin / BK;
-  p.kt_per_split = (ncb + p.splits - 1) / p.splits;   // channel blocks per split
-  p.splits = (ncb + p.kt_per_split - 1) / p.kt_per_split;
-  dim3 grid(p.tiles_m * p.tiles_n, 1, p.splits);
-  const bool prof = pfd_prof_on();
-  if (prof)
-    pfd_prof_begin(19, 2.0 * p.M * p.N * p.K,
-                   2.0 * p.B * p.H * p.Wd * p.Cin + 2.0 * p.N * p.K + 2.0 * p.M * p.N * (p.R ? 2 : 1), s);
-  if (p.gn_table && p.gn_act == PFD_ACT_SILU) hipLaunchKernelGGL((conv3x3_patch_ws_kernel<2>), grid, dim3(768), 0, s, p);
-  else if (p.gn_table) hipLaunchKernelGGL((conv3x3_patch_ws_kernel<1>), grid, dim3(768), 0, s, p);
-  else if (ws == 3) hipLaunchKernelGGL((conv3x3_patch_ws_kernel<0, 3>), grid, dim3(768), 0, s, p);
-  else if (ws) hipLaunchKernelGGL((conv3x3_patch_ws_kernel<0>), grid, dim3(768), 0, s, p);
-  else hipLaunchKernelGGL(conv3x3_patch_kernel, grid, dim3(512), 0, s, p);
-  if (p.splits > 1) launch_splitk_reduce(p, s);
-  if (prof) pfd_prof_end(s);
-  return pfd_check_launch("pfd_gemm_f16(conv3x3 patch)");
+int launch_patch(G160Params& p, const GnFuse* gnf, hipStream_t s, int ws) {
+  return launch_tiles(p, 256, BN, p.Cin / BK, 19, "pfd_gemm_f16(conv3x3 patch)", gnf, s, [&](dim3 grid) {   // (channel blocks per split)
+    if (p.gn_table && p.gn_act == PFD_ACT_SILU) hipLaunchKernelGGL((conv3x3_patch_ws_kernel<2>), grid, dim3(768), 0, s, p);
+    else if (p.gn_table) hipLaunchKernelGGL((conv3x3_patch_ws_kernel<1>), grid, dim3(768), 0, s, p);
+    else if (ws == 3) hipLaunchKernelGGL((conv3x3_patch_ws_kernel<0, 3>), grid, dim3(768), 0, s, p);
+    else if (ws) hipLaunchKernelGGL((conv3x3_patch_ws_kernel<0>), grid, dim3(768), 0, s, p);
+    else hipLaunchKernelGGL(conv3x3_patch_kernel, grid, dim3(512), 0, s, p);
+  });
+}
+
+// The forced-variant codes of pfd_gemm_f16_ex (include/pfd_hip.h: these numbers are the ABI) and what each one is
+enum Variant {
+  V_AUTO = 0,
+  V22_64 = 22, V23_64_RING = 23, V24_128 = 24, V25_128_RING = 25,                  // 64- / 128-row tiles on four waves
+  V41_64_W8 = 41, V43_64_W8_RING = 43, V82_128_W8 = 82, V83_128_W8_RING = 83,      // the same tiles on eight waves
+  V44_256 = 44, V47_256_LW_RING = 47, V48_256_LW = 48, V84_256_GEGLU = 84,         // 256 rows: 8 waves, + 4 loader waves, the 256 x 320 tile
+  V96_PATCH_RING = 96, V98_PATCH_LW = 98, V99_PATCH_W8 = 99                        // the 3x3 patch kernel
+};
+// tile rows, MFMA waves, operand (patch: weight) stages, loader waves.  The dispatcher reads rows and loader_waves; waves and
+// stages describe the template arguments of the variant switches at the end of pfd_gemm160_try (WAVES_M * 2 waves, NBUF stages)
+struct VariantInfo { int code, rows, waves, stages, loader_waves; };
+constexpr VariantInfo kVariantTable[] = {
+    {V22_64, 64, 4, 2, 0},     {V23_64_RING, 64, 4, 4, 0},     {V24_128, 128, 4, 2, 0},     {V25_128_RING, 128, 4, 3, 0},
+    {V41_64_W8, 64, 8, 2, 0},  {V43_64_W8_RING, 64, 8, 4, 0},  {V82_128_W8, 128, 8, 2, 0},  {V83_128_W8_RING, 128, 8, 3, 0},
+    {V44_256, 256, 8, 2, 0},   {V47_256_LW_RING, 256, 8, 3, 4}, {V48_256_LW, 256, 8, 2, 4}, {V84_256_GEGLU, 256, 8, 2, 0},
+    {V96_PATCH_RING, 256, 8, 3, 4}, {V98_PATCH_LW, 256, 8, 2, 4}, {V99_PATCH_W8, 256, 8, 2, 0}};
+inline const VariantInfo* find_variant(int code) {
+  for (const auto& v : kVariantTable)
+    if (v.code == code) return &v;
+  return nullptr;
 }
 
 }  // namespace
@@ -2119,17 +2122,19 @@ int launch_patch(G160Params& p, hipStream_t s, int ws) {
 // kernel with 128-wide tiles (wave tile x 64: the VAE's 128/256/512 channels, Swin / SeeCoder widths).
 int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s) {
   const int bn = d->N % 160 == 0 ? 160 : 128;
+  const VariantInfo* const forced = find_variant(variant);   // nullptr: the heuristic, or a code the table does not know
+  const bool forced_lw = forced && forced->loader_waves;     // the loader-wave kernels serve convolutions
   if (d->N % bn || d->bias_per_row || d->K % BK) return 1;
   if (bn == 128 && d->act == PFD_ACT_GEGLU) return 1;   // GEGLU packing is defined per serving kernel (pfd_hip.h)
   if (d->ksize > 0 && (d->Cin % BK)) return 1;
   if (d->act == PFD_ACT_GEGLU && (d->rowvec || d->R)) return 1;
-  if ((d->ldc & 7) || (reinterpret_cast<uintptr_t>(d->C) & 15)) return 1;
-  if (d->bias && (reinterpret_cast<uintptr_t>(d->bias) & 15)) return 1;
-  if (d->R && ((d->ldr & 7) || (reinterpret_cast<uintptr_t>(d->R) & 15))) return 1;
-  if (d->rowvec && ((d->ldrv & 7) || (reinterpret_cast<uintptr_t>(d->rowvec) & 15))) return 1;
+  if ((d->ldc & 7) || !aligned16(d->C)) return 1;
+  if (d->bias && !aligned16(d->bias)) return 1;
+  if (d->R && ((d->ldr & 7) || !aligned16(d->R))) return 1;
+  if (d->rowvec && ((d->ldrv & 7) || !aligned16(d->rowvec))) return 1;
   if (d->Ct) {  // transposed tail: validated by the caller to be a plain, epilogue-free GEMM
     if (d->ksize > 0 || d->n_split <= 0 || d->n_split >= d->N || d->n_split % bn || (d->ldct & 7) ||
-        (reinterpret_cast<uintptr_t>(d->Ct) & 15))
+        !aligned16(d->Ct))
       return 1;
     splits = 1;
   }
@@ -2157,32 +2162,25 @@ int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s
   p.gn_out = (float2*)d->gn_out;
   if (p.gn_out) {
     if (bn != 160 || (d->N % 32) || d->N / 32 < 8 || (160 % (d->N / 32)) || (d->M % GN_SLAB) || d->act == PFD_ACT_GEGLU || d->Ct ||
-        d->ln_out || d->bias_per_row || (reinterpret_cast<uintptr_t>(p.gn_out) & 7))
+        d->ln_out || d->bias_per_row || !aligned8(p.gn_out))
       return 1;
     if (d->ksize > 0 && ((long)d->Ho * d->Wo) % GN_SLAB) return 1;   // a slab must not straddle two samples
   }
-  // GroupNorm fused into the split-K reduction (ABI 9): validated here, armed once the split count is known (gnf_arm below)
-  t_gnf.y = nullptr;
-  const bool gnf = d->gnf_y != nullptr;
+  // GroupNorm fused into the split-K reduction (ABI 9): validated here, served once the split count is known to be > 1
+  const GnFuse fuse = {(const half_t*)d->gnf_gamma, (const half_t*)d->gnf_beta, (half_t*)d->gnf_y, (long)d->gnf_ldy, d->gnf_eps,
+                       d->gnf_act, d->gnf_rows, d->gnf_skip_raw};
+  const GnFuse* const gnf = d->gnf_y ? &fuse : nullptr;
   if (gnf) {
     const int cpg = d->N / 32;
     if (bn != 160 || (d->N % 32) || (cpg % 4) || cpg < 20 || cpg > 256 || d->gnf_rows <= 0 || (d->M % d->gnf_rows) ||
         (long)d->gnf_rows * (cpg / 4) > (long)GNF_T * GNF_MAX || (long)(d->M / d->gnf_rows) * 32 < 128 || !d->gnf_gamma || !d->gnf_beta ||
-        (d->gnf_ldy & 3) || (reinterpret_cast<uintptr_t>(d->gnf_y) & 7) || d->act == PFD_ACT_GEGLU || d->Ct || d->ln_stats ||
+        (d->gnf_ldy & 3) || !aligned8(d->gnf_y) || d->act == PFD_ACT_GEGLU || d->Ct || d->ln_stats ||
         d->ln_out || d->gn_out || d->bias_per_row || !d->ws ||
         (d->gnf_act != PFD_ACT_NONE && d->gnf_act != PFD_ACT_SILU))
       return 1;
     const int rpr = d->rows_per_rv > 0 ? d->rows_per_rv : 1;
     if (d->rowvec && (rpr % d->gnf_rows) && rpr < d->M) return 1;   // one row vector per sample
   }
-  auto gnf_arm = [&](int nsplits) -> bool {   // false: the problem is not split -> not served (nothing launched yet)
-    if (!gnf) return true;
-    if (nsplits <= 1) return false;
-    t_gnf = GnFuse{(const half_t*)d->gnf_gamma, (const half_t*)d->gnf_beta, (half_t*)d->gnf_y, (long)d->gnf_ldy, d->gnf_eps,
-                   d->gnf_act, d->gnf_rows, d->gnf_skip_raw};
-    return true;
-  };
-  struct GnfDisarm { ~GnfDisarm() { t_gnf.y = nullptr; } } gnf_disarm;
   // two-source contraction / zero rows (ABI 8): the 8-wave / 4-wave linear kernels only
   // residual stored once for a doubled batch (ABI 9): one wrap at most, whole rows; not with the fused GroupNorm reduction
   p.r_wrap = 0x7fffffff;
@@ -2194,9 +2192,9 @@ int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s
   if (d->k_split > 0 || d->zero_rows > 0) {
     if (d->ksize > 0 || d->gn_table || d->bias_per_row || d->Ct) return 1;
     if (d->zero_rows < 0 || d->zero_rows >= d->M || (d->zero_rows > 0 && d->ln_stats)) return 1;
-    if (variant == 47 || variant == 48 || variant == 84) return 1;
+    if (forced_lw || variant == V84_256_GEGLU) return 1;
     if (d->k_split > 0) {
-      if (d->k_split >= d->K || (d->k_split % BK) || !d->A2 || (d->lda2 & 7) || (reinterpret_cast<uintptr_t>(d->A2) & 15)) return 1;
+      if (d->k_split >= d->K || (d->k_split % BK) || !d->A2 || (d->lda2 & 7) || !aligned16(d->A2)) return 1;
       p.k_split = d->k_split;
     }
     p.zero_rows = d->zero_rows;
@@ -2207,28 +2205,28 @@ int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s
   if (d->ksize > 0 && d->ups == 2) {
     if (d->ksize != 3 || d->stride != 1 || d->pad != 1 || d->K != 4 * d->Cin || d->Ho != 2 * d->H || d->Wo != 2 * d->Wd ||
         ((long)d->H * d->Wd) % 256 || d->R || d->rowvec || d->Ct || d->gn_table || d->gnf_y || d->ln_stats || d->ln_out ||
-        d->k_split > 0 || d->zero_rows > 0 || d->act == PFD_ACT_GEGLU || (variant != 0 && variant != 47 && variant != 48) || splits > 1)
+        d->k_split > 0 || d->zero_rows > 0 || d->act == PFD_ACT_GEGLU || splits > 1)
       return 1;
+    if (variant != V_AUTO && variant != V47_256_LW_RING && variant != V48_256_LW) return 1;
     p.splits = 1;
-    const int mode = variant == 48 ? 0 : 2;   // the 3-stage ring unless the two-stage form is forced
-    if (bn == 128) return launch160ws<4>(p, 16, s, mode) < 0 ? PFD_ELAUNCH : 0;
-    return launch160ws<5>(p, 16, s, mode) < 0 ? PFD_ELAUNCH : 0;
+    const int mode = variant == V48_256_LW ? 0 : 2;   // the 3-stage ring unless the two-stage form is forced
+    if (bn == 128) return launch160ws<4>(p, 16, gnf, s, mode);
+    return launch160ws<5>(p, 16, gnf, s, mode);
   }
   if (p.ln_in) {   // LayerNorm fold: plain linear, statistics over K = ln_parts slices of 160 columns
     if (d->ksize > 0 || !p.ln_cs || p.ln_P < 1 || p.ln_P > 8 || p.ln_P * 160 != d->K) return 1;
-    if ((reinterpret_cast<uintptr_t>(p.ln_in) & 7) || (reinterpret_cast<uintptr_t>(p.ln_cs) & 15)) return 1;
-    if (variant == 47 || variant == 48) return 1;   // the loader-wave kernels serve convolutions
+    if (!aligned8(p.ln_in) || !aligned16(p.ln_cs)) return 1;
+    if (forced_lw) return 1;
   }
   if (p.ln_out) {  // statistics of the output rows for the consumer's fold
-    if (bn != 160 || d->ksize > 0 || d->act == PFD_ACT_GEGLU || d->Ct || (reinterpret_cast<uintptr_t>(p.ln_out) & 7)) return 1;
-    if (variant == 47 || variant == 48) return 1;
+    if (bn != 160 || d->ksize > 0 || d->act == PFD_ACT_GEGLU || d->Ct || !aligned8(p.ln_out)) return 1;
+    if (forced_lw) return 1;
   }
   if (p.gn_table) {   // GroupNorm prologue: patch kernel or nothing (validated here, PFD_ESHAPE by the caller otherwise)
-    if (bn != 160 || (variant != 0 && variant != 98)) return 1;
-    variant = 98;   // loader waves with two weight stages (the form the prologue instances are built on)
+    if (bn != 160 || (variant != V_AUTO && variant != V98_PATCH_LW)) return 1;
+    variant = V98_PATCH_LW;   // loader waves with two weight stages (the form the prologue instances are built on)
     if (p.gn_c1 <= 0 || p.gn_c1 > p.Cin || (p.gn_c1 % BK) || (p.gn_c1 < p.Cin && !p.A2)) return 1;
-    if ((p.lda2 & 7) || (reinterpret_cast<uintptr_t>(p.A2) & 15) || (reinterpret_cast<uintptr_t>(p.gn_table) & 15))
-      return 1;
+    if ((p.lda2 & 7) || !aligned16(p.A2) || !aligned16(p.gn_table)) return 1;
     if (p.gn_act != PFD_ACT_NONE && p.gn_act != PFD_ACT_SILU) return 1;
     if (p.gn_c1 == p.Cin) { p.A2 = p.A; p.lda2 = p.lda; }
   }
@@ -2243,7 +2241,8 @@ int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s
     else if (p.Wd % 16 == 0 && p.H % 16 == 0) pt_w = 16;
   }
   const bool patch_w = p.Wd == 16 || p.Wd == 32 || p.Wd == 64 || pt_w != 0;
-  if (bn == 160 && (variant == 0 || variant == 99 || variant == 98 || variant == 96) && p.ksize == 3 && p.stride == 1 && p.pad == 1 && !p.ups &&
+  const bool patch_variant = variant == V99_PATCH_W8 || variant == V98_PATCH_LW || variant == V96_PATCH_RING;
+  if (bn == 160 && (variant == V_AUTO || patch_variant) && p.ksize == 3 && p.stride == 1 && p.pad == 1 && !p.ups &&
       patch_w && p.Ho == p.H && p.Wo == p.Wd && (pt_w != 0 || p.H % (256 / p.Wd) == 0) &&
       p.M % 256 == 0 && ((long)p.H * p.Wd) % 256 == 0 && p.act != PFD_ACT_GEGLU) {
     p.pt_w = pt_w;
@@ -2265,19 +2264,16 @@ int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s
     }
     if (splits > 1 && (!d->ws || (size_t)splits * p.M * p.N * 4 > d->ws_bytes)) splits = 1;
     p.splits = splits;
-    {   // (launch_patch turns the request into channel blocks per split: the count it will really launch)
-      const int kps = (ncb + splits - 1) / splits;
-      if (!gnf_arm((ncb + kps - 1) / kps)) return 1;
-    }
+    if (gnf && real_splits(ncb, splits) <= 1) return 1;   // the problem is not split -> not served (nothing launched yet)
     // default: the wave-specialised form (4 loader waves; +4 ... 13 % on every patch-eligible conv of the UNet, most on the
     // long-K ones, profiles/r02_patch_ws_ab.log) with the 3-stage weight ring (two taps of weights in flight, counted vmcnt;
     // round 4, -4.6 ms per batch); 99 forces the 8-wave form, 98 the loader-wave form with two weight stages (the
     // GroupNorm-prologue instances are built on it)
-    const int ws = variant == 99 ? 0 : variant == 98 ? 1 : 3;   // 96 forces what is the default anyway
-    return launch_patch(p, s, ws) < 0 ? PFD_ELAUNCH : 0;
+    const int ws = variant == V99_PATCH_W8 ? 0 : variant == V98_PATCH_LW ? 1 : 3;   // 96 forces what is the default anyway
+    return launch_patch(p, gnf, s, ws);
   }
-  if (variant == 99 || variant == 98 || variant == 96 || p.gn_table) return 1;
-  const bool auto_variant = variant == 0;
+  if (patch_variant || p.gn_table) return 1;
+  const bool auto_variant = variant == V_AUTO;
   const int nk_all = p.K / BK;
   if (auto_variant) {
     // measured on MI355X: every GEMM/conv of a UNet pass replayed with COLD weights (the 1.7 GB of other
@@ -2289,21 +2285,21 @@ int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s
     //  the real loop it lost: 664 vs 661 ms per batch.)
     const long t128 = tiles(128);
     const bool few = nk_all >= 16 ? t128 < 256 : t128 < 384;
-    variant = tiles(256) >= 200 ? 44 : (nk_all <= 24 && few) ? 22 : 24;
+    variant = tiles(256) >= 200 ? V44_256 : (nk_all <= 24 && few) ? V22_64 : V24_128;
     // round 2 (coalesced epilogue, cold replay of the sampler's launch list, profiles/r02_gemm_replay_variants.log):
     // short-K linears on >= 8192 rows are epilogue / HBM bound: two co-resident 128-row blocks overlap one
     // block's store pass with the other's K loop (GEGLU 32768x2560x320: 87 -> 79 us, qkv 8192x1920x640: 42 -> 35);
     // mid-K problems with <= 256 tiles of 128 rows take 64-row tiles (8192x640x2560: 54 -> 46 us)
         // (nk_all <= 40 since round 5, end to end -0.25 %; <= 20 came from the cold replay)
-    if (p.ksize == 0 && variant == 44 && p.M >= 8192 && nk_all <= 40) variant = 24;
+    if (p.ksize == 0 && variant == V44_256 && p.M >= 8192 && nk_all <= 40) variant = V24_128;
     // 128-row tiles that fill the chip at most once run the 3-stage ring (one 110 KB block per CU is no loss
     // there): 8192x640x2560 46 -> 38 us, 8192x640x1280 25 -> 24 (profiles/r02_ring_replay.log)
-    if (bn == 160 && p.ksize == 0 && variant == 24 && t128 <= 256 && nk_all >= 16) variant = 25;
-    if (p.ksize == 0 && variant == 24 && nk_all <= 40 && t128 <= 256 && tiles(64) >= 384) variant = 22;
+    if (bn == 160 && p.ksize == 0 && variant == V24_128 && t128 <= 256 && nk_all >= 16) variant = V25_128_RING;
+    if (p.ksize == 0 && variant == V24_128 && nk_all <= 40 && t128 <= 256 && tiles(64) >= 384) variant = V22_64;
     // implicit-GEMM convolutions (stride 2, fused upsample, widths the patch kernel does not take) run long K loops
     // of 53 KB stages: with the DMA pieces on four dedicated loader waves they gain 5-17 % (32768 x 640 x 5760
     // upsample conv: 225 -> 192 us = 1260 TF); the short-K linears do not (profiles/r02_wave_specialised_ab.log)
-    if (variant == 44 && p.ksize > 0) variant = 47;
+    if (variant == V44_256 && p.ksize > 0) variant = V47_256_LW_RING;
     // round 3 (cold replay under every forced variant, profiles/r03_tile_variants_replay.log): the 128-row tile on EIGHT
     // waves (4 x 2 wave layout, wave tile 32 x 80; variants 82 / 83) instead of four beats the 4-wave form wherever
     // that was chosen (qkv 8192 x 1920 x 640: 32.5 -> 27.3 us, 32768 x 960 x 320: 34.3 -> 31.8, ff-out 8192 x 640 x 2560
@@ -2313,28 +2309,32 @@ int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s
     // 5120 55 -> 48 us, 2048 x 640 x 5760 / s2 52 -> 37, 8192 x 320 x 2880 / s2 38.5 -> 30.7).
     if (bn == 160) {
       // (nk_all >= 5 since round 5 -- the 64^2 GEGLU projection, K = 320, too: -0.3 % end to end; >= 10 came from the cold replay)
-            if (p.act == PFD_ACT_GEGLU && p.ksize == 0 && p.N % 320 == 0 && p.M >= 2048 && nk_all >= 5) variant = 84;
-      else if (p.ksize == 0 && (variant == 24 || variant == 25) && p.M <= 2048 && nk_all >= 32) variant = 43;   // (>= 64 until round 5; >= 32: -0.5 % end to end)
-      else if (p.ksize > 0 && p.stride == 2 && p.M <= 8192 && (variant == 24 || variant == 25 || variant == 22)) variant = 43;
-      else if (variant == 24) variant = 82;
-      else if (variant == 25) variant = 83;
+            if (p.act == PFD_ACT_GEGLU && p.ksize == 0 && p.N % 320 == 0 && p.M >= 2048 && nk_all >= 5) variant = V84_256_GEGLU;
+      else if (p.ksize == 0 && (variant == V24_128 || variant == V25_128_RING) && p.M <= 2048 && nk_all >= 32)
+        variant = V43_64_W8_RING;   // (>= 64 until round 5; >= 32: -0.5 % end to end)
+      else if (p.ksize > 0 && p.stride == 2 && p.M <= 8192 && (variant == V24_128 || variant == V25_128_RING || variant == V22_64))
+        variant = V43_64_W8_RING;
+      else if (variant == V24_128) variant = V82_128_W8;
+      else if (variant == V25_128_RING) variant = V83_128_W8_RING;
     }
   }
-  const int bm = (variant == 44 || variant == 48 || variant == 47 || variant == 84) ? 256
-                 : (variant == 24 || variant == 25 || variant == 82 || variant == 83) ? 128 : 64;
+  // tile rows of the variant: 0 for a code the table does not know (no split rule applies; PFD_EINVAL at the switches below)
+  const VariantInfo* const vi = find_variant(variant);
+  const int bm = vi ? vi->rows : 0;
   if (splits == 0) {
     splits = 1;
-    const long tl = tiles(bm);
+    const long tl = bm ? tiles(bm) : 0;
     const int nk = nk_all;
-    if (p.act != PFD_ACT_GEGLU && d->ws && (variant == 44 || variant == 48 || variant == 47) && tl < 200 && nk >= 48 &&
+    const bool may_split = p.act != PFD_ACT_GEGLU && d->ws;
+    if (may_split && bm == 256 && variant != V84_256_GEGLU /* the GEGLU tile never splits */ && tl < 200 && nk >= 48 &&
         (size_t)2 * p.M * p.N * 4 <= d->ws_bytes) {
       splits = 2;  // 128 tiles of 256x160: two K halves fill the chip (758 vs 579 TF at 640->640 @32^2)
-    } else if (p.act != PFD_ACT_GEGLU && d->ws && (variant == 24 || variant == 25 || variant == 82 || variant == 83) && tl < 256) {
+    } else if (may_split && bm == 128 && tl < 256) {
       splits = (int)((512 + tl - 1) / tl);
       if (splits > 8) splits = 8;
       while (splits > 1 && nk / splits < 16) --splits;  // the slab round trip must stay small vs the K loop
       while (splits > 1 && (size_t)splits * p.M * p.N * 4 > d->ws_bytes) --splits;
-    } else if (p.act != PFD_ACT_GEGLU && d->ws && (variant == 22 || variant == 23 || variant == 41 || variant == 43) && tl <= 128 && nk >= 16) {
+    } else if (may_split && bm == 64 && tl <= 128 && nk >= 16) {
       splits = (int)(256 / tl);   // M <= 1024 rows (8^2 level, cond-half projections): 25 -> 21 us
       if (splits > 4) splits = 4;
       while (splits > 1 && (size_t)splits * p.M * p.N * 4 > d->ws_bytes) --splits;
@@ -2342,10 +2342,7 @@ int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s
   }
   if (splits > 1 && (!d->ws || (size_t)splits * p.M * p.N * 4 > d->ws_bytes || p.act == PFD_ACT_GEGLU)) splits = 1;
   p.splits = splits;
-  {   // (the launchers turn the request into K tiles per split: the count they will really launch)
-    const int kps = (nk_all + splits - 1) / splits;
-    if (!gnf_arm((nk_all + kps - 1) / kps)) return 1;
-  }
+  if (gnf && real_splits(nk_all, splits) <= 1) return 1;   // the problem is not split -> not served (nothing launched yet)
   if (auto_variant && bn == 160) {
     // Problems whose blocks fill the chip once (the 16^2 / 8^2 levels: <= 256 tiles, or split-K slices of them) are
     // bound by the DMA round trip per K tile, not by MFMA or LDS capacity: they take the deep operand rings (3 K tiles
@@ -2353,49 +2350,50 @@ int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s
     // list: 2048x1280x1280 23 -> 18 us, 4096x640x640 15 -> 12.5, 8^2 convs 512x1280x11520 38 -> 34, 512x1280x23040
     // 60 -> 51, GEGLU 512x10240x1280 30 -> 24 (profiles/r02_ring_replay.log).
     const int nk_split = nk_all / splits;
-    if (variant == 22 && tiles(64) * splits <= 256 && nk_split >= 8) variant = 23;
-    if (variant == 24 && tiles(128) < 256 && nk_split >= 6) variant = 25;
-    if (variant == 82 && (p.ksize == 0 || (p.stride == 1 && !p.ups)) && tiles(128) <= 256 && nk_split >= 6) variant = 83;
+    if (variant == V22_64 && tiles(64) * splits <= 256 && nk_split >= 8) variant = V23_64_RING;
+    if (variant == V24_128 && tiles(128) < 256 && nk_split >= 6) variant = V25_128_RING;
+    if (variant == V82_128_W8 && (p.ksize == 0 || (p.stride == 1 && !p.ups)) && tiles(128) <= 256 && nk_split >= 6)
+      variant = V83_128_W8_RING;
   }
   const int conv = p.ksize > 0 ? 1 : 0;
   // round 5: the 64-row tiles run on EIGHT waves (4 x 1 wave layout, wave tile 16 x 160: variants 41 / 43) wherever the rules
   // above picked the four-wave forms 22 / 23 -- twice the waves issuing LDS-DMA pieces per CU on launches that are chains of
   // round trips.  Same tile, same split counts, same K order.  End to end -0.2 % (22 -> 41) and -0.3 % (23 -> 43), alternating on
   // one box (profiles/r05_e2e_ab_candidates.log); round 3 had adopted the eight-wave forms only where the COLD REPLAY showed a gain.
-  if (auto_variant && bn == 160) variant = variant == 22 ? 41 : variant == 23 ? 43 : variant;
-  if (variant == 48 || variant == 47) {   // 8 MFMA waves + 4 loader waves (48: two operand stages, 47: 3-stage ring)
-    const int mode = variant == 47 ? 2 : 0;
-    if (bn == 128) return launch160ws<4>(p, 12 + 4 * conv, s, mode) < 0 ? PFD_ELAUNCH : 0;
-    return launch160ws<5>(p, 12 + 4 * conv, s, mode) < 0 ? PFD_ELAUNCH : 0;
+  if (auto_variant && bn == 160) variant = variant == V22_64 ? V41_64_W8 : variant == V23_64_RING ? V43_64_W8_RING : variant;
+  if (variant == V48_256_LW || variant == V47_256_LW_RING) {   // 8 MFMA waves + 4 loader waves (48: two operand stages, 47: 3-stage ring)
+    const int mode = variant == V47_256_LW_RING ? 2 : 0;
+    if (bn == 128) return launch160ws<4>(p, 12 + 4 * conv, gnf, s, mode);
+    return launch160ws<5>(p, 12 + 4 * conv, gnf, s, mode);
   }
   if (bn == 128) {
     switch (variant) {
-      case 44: return launch160<4, 4, 2, 4>(p, 12 + 4 * conv, s) < 0 ? PFD_ELAUNCH : 0;
-      case 24: return launch160<2, 4, 2, 4>(p, 13 + 4 * conv, s) < 0 ? PFD_ELAUNCH : 0;
-      case 22: return launch160<2, 2, 2, 4>(p, 14 + 4 * conv, s) < 0 ? PFD_ELAUNCH : 0;
-      default: return variant == 99 ? 1 : PFD_EINVAL;
+      case V44_256: return launch160<4, 4, 2, 4>(p, 12 + 4 * conv, gnf, s);
+      case V24_128: return launch160<2, 4, 2, 4>(p, 13 + 4 * conv, gnf, s);
+      case V22_64: return launch160<2, 2, 2, 4>(p, 14 + 4 * conv, gnf, s);
+      default: return variant == V99_PATCH_W8 ? 1 : PFD_EINVAL;
     }
   }
-  if (variant == 84) {   // 256 x 320 tile (wave tile 64 x 160): GEGLU projections whose tiles fill the chip
+  if (variant == V84_256_GEGLU) {   // 256 x 320 tile (wave tile 64 x 160): GEGLU projections whose tiles fill the chip
     if (p.act != PFD_ACT_GEGLU || conv || p.N % 320 || p.splits != 1) return PFD_EINVAL;
-    return launch160<4, 4, 2, 10>(p, 12, s) < 0 ? PFD_ELAUNCH : 0;
+    return launch160<4, 4, 2, 10>(p, 12, gnf, s);
   }
   switch (variant) {
-    case 44: return launch160<4, 4>(p, 12 + 4 * conv, s) < 0 ? PFD_ELAUNCH : 0;
-    case 24: return launch160<2, 4>(p, 13 + 4 * conv, s) < 0 ? PFD_ELAUNCH : 0;
-    case 22: return launch160<2, 2>(p, 14 + 4 * conv, s) < 0 ? PFD_ELAUNCH : 0;
+    case V44_256: return launch160<4, 4>(p, 12 + 4 * conv, gnf, s);
+    case V24_128: return launch160<2, 4>(p, 13 + 4 * conv, gnf, s);
+    case V22_64: return launch160<2, 2>(p, 14 + 4 * conv, gnf, s);
     // deep operand rings (counted vmcnt): K tiles in flight ahead of the MFMAs = 3 (64-row tile) / 2 (128-row tile)
-    case 23: return launch160<2, 2, 4>(p, 14 + 4 * conv, s) < 0 ? PFD_ELAUNCH : 0;
-    case 25: return launch160<2, 4, 3>(p, 13 + 4 * conv, s) < 0 ? PFD_ELAUNCH : 0;
+    case V23_64_RING: return launch160<2, 2, 4>(p, 14 + 4 * conv, gnf, s);
+    case V25_128_RING: return launch160<2, 4, 3>(p, 13 + 4 * conv, gnf, s);
     // (round 5: the same tiles on a 5-stage ring -- 4 K tiles in flight -- measured 0.0 % end to end and were removed,
     //  profiles/r05_e2e_ab_candidates.log)
     // round 3 experiments: the same tiles on 8 waves (4 x 2 wave layout, wave tile 16 x 80 / 32 x 80): twice the waves
     // issuing LDS-DMA pieces per CU and two waves per SIMD on the problems whose one 4-wave block per CU is bound by the
     // piece issue rate (64-row tiles: 41 two stages, 43 four-stage ring; 128-row tiles: 82 two stages, 83 three)
-    case 41: return launch160<4, 1, 2>(p, 14 + 4 * conv, s) < 0 ? PFD_ELAUNCH : 0;
-    case 43: return launch160<4, 1, 4>(p, 14 + 4 * conv, s) < 0 ? PFD_ELAUNCH : 0;
-    case 82: return launch160<4, 2, 2>(p, 13 + 4 * conv, s) < 0 ? PFD_ELAUNCH : 0;
-    case 83: return launch160<4, 2, 3>(p, 13 + 4 * conv, s) < 0 ? PFD_ELAUNCH : 0;
+    case V41_64_W8: return launch160<4, 1, 2>(p, 14 + 4 * conv, gnf, s);
+    case V43_64_W8_RING: return launch160<4, 1, 4>(p, 14 + 4 * conv, gnf, s);
+    case V82_128_W8: return launch160<4, 2, 2>(p, 13 + 4 * conv, gnf, s);
+    case V83_128_W8_RING: return launch160<4, 2, 3>(p, 13 + 4 * conv, gnf, s);
     default: return PFD_EINVAL;
   }
 }

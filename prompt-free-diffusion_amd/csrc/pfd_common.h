@@ -93,6 +93,10 @@ struct PfdProfScope {
   PfdProfScope& operator=(const PfdProfScope&) = delete;
 };
 
+// pointer alignment the 16-byte (8-byte) vector accesses of the kernels need
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
 // host-side error plumbing (defined in capi.cpp)
 int pfd_check_launch(const char* what);
 void pfd_set_error(const char* msg);

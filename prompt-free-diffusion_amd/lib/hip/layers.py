@@ -171,8 +171,9 @@ class Conv2d(nn.Conv2d, _Packed):
         emits its statistics (PfdGemmDesc.gn_out); they ride on the returned tensor (ops.get_gn_stats)"""
         k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
         cin = self.in_channels
+        ln_out = ops.ln_out_arg(ln_out)
         if ups and ops.UPS_FOLD and gn is None and cin % 64 == 0 and (k, s, p) == (3, 1, 1) and rowvec is None and res is None and out_hw is None \
-                and ln_out in (None, False) and res_rows is None:
+                and ln_out is None and res_rows is None:
             # nearest-2x + 3x3 as four 2x2-tap phase convolutions (4/9 of the MFMAs) where the library serves the shape; a shape
             # it declined once is not asked again and its folded pack is not kept
             key = ops.ups_fold_key(x, self.out_channels, act, self.bias, out, gn_out)
@@ -191,18 +192,18 @@ class Conv2d(nn.Conv2d, _Packed):
                 B, H, W_, _ = x.shape
                 o2 = None if out is None else out.view(-1, out.shape[-1])
                 r2 = None if res is None else res.reshape(-1, res.shape[-1])
-                want = bool(gn_out) and (ln_out is None or ln_out is False) and act != ACT_GEGLU and \
+                want = bool(gn_out) and ln_out is None and act != ACT_GEGLU and \
                     ops.gn_stats_wanted(B, H * W_, self.out_channels) and ops.wide_tile_ok(self.out_channels, cin)
                 y = ops.gemm(x.reshape(-1, cin), w, bias=b, rowvec=rowvec,
                              rows_per_rv=H * W_ if rows_per_rv is None else rows_per_rv, res=r2, act=act,
                              out=o2, ln_out=ln_out, gn_out=want, res_rows=res_rows)
-                if ln_out is not None and ln_out is not False:
+                if ln_out is not None:
                     return y[0].view(B, H, W_, self.out_channels), y[1]
                 v = y.view(B, H, W_, self.out_channels)
                 if want:
                     ops.set_gn_stats(v, ops.get_gn_stats(y))
                 return v
-            if (ln_out is not None and ln_out is not False) or res_rows is not None:
+            if ln_out is not None or res_rows is not None:
                 raise ValueError("ln_out / res_rows are for 1x1 convolutions (token-wise linears)")
             return ops.conv(x, w, k, stride=s, pad=p, ups=ups, bias=b, rowvec=rowvec, res=res, act=act, out=out,
                             out_hw=out_hw, rows_per_rv=rows_per_rv, gn_out=gn_out)
@@ -234,6 +235,7 @@ class Linear(nn.Linear, _Packed):
         """x: [..., K] fp16 token-major -> [..., N].
         ln = (LayerNorm module, partial row sums of x): the LayerNorm in front of this Linear is folded into the GEMM
         (x is the UN-normalised tensor).  ln_out: see ops.gemm (returns (y, stats))."""
+        ln_out = ops.ln_out_arg(ln_out)
         if ln is not None:
             norm, st = ln
             w, cs, b = self._pk_ln(norm)
@@ -248,7 +250,7 @@ class Linear(nn.Linear, _Packed):
             x2 = xp
         r2 = None if res is None else (res.reshape(-1, res.shape[-1]) if res.dim() != 2 else res)
         y = ops.gemm(x2, w, bias=b, act=act, res=r2, rowvec=rowvec, rows_per_rv=rows_per_rv, out=out, ln_out=ln_out)
-        if ln_out is not None and ln_out is not False:
+        if ln_out is not None:
             return y
         return y if x.dim() == 2 else y.view(*x.shape[:-1], y.shape[-1])
 

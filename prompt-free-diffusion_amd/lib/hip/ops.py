@@ -111,6 +111,42 @@ def _trace(d):
         f.write(" ".join(str(v) for v in trace_record(d)) + "\n")
 
 
+# Requests the library declined once under its heuristic (it decides whether a problem splits K, which upsample shapes the
+# phase form serves): not asked again.  Keys: everything the decision depends on (conv(gn_fuse=...): built there; conv(ups=2):
+# ups_fold_key).
+_DECLINED = set()
+
+
+def _launch(d, tile, label, decline_key=None):
+    """the one GEMM / conv launch: pfd_gemm_f16 (tile 0: the library's heuristic) or pfd_gemm_f16_ex.  True when it launched (and
+    left its PFD_TRACE_GEMM record).  decline_key: the caller has another way to run the request -- PFD_ESHAPE (nothing was
+    launched, nothing written: include/pfd_hip.h) then returns False and, for a heuristic call, remembers the key (a decline
+    under a forced tile says nothing about the heuristic's choice)."""
+    lib = _lib()
+    rc = lib.pfd_gemm_f16_ex(_byref(d), tile, _stream()) if tile else lib.pfd_gemm_f16(_byref(d), _stream())
+    if decline_key is not None and rc == _b.PFD_ESHAPE:
+        if tile == 0:
+            _DECLINED.add(decline_key)
+        return False
+    _b.check(rc, label)
+    if _TRACE:
+        _trace(d)
+    return True
+
+
+def _gemm_desc(a, w, out, M, N, K, lda, ldw, bias, rowvec, res):
+    """PfdGemmDesc with the fields gemm() and conv() share: operands, epilogue vectors, leading dimensions, sizes, workspace"""
+    d = _b.PfdGemmDesc()
+    d.A, d.W, d.C = a.data_ptr(), w.data_ptr(), out.data_ptr()
+    d.bias, d.rowvec, d.R = _ptr(bias), _ptr(rowvec), _ptr(res)
+    d.lda, d.ldw, d.ldc = lda, ldw, _rows(out)[2]
+    d.ldr = _rows(res)[2] if res is not None else 0
+    d.ldrv = _rows(rowvec)[2] if rowvec is not None else 0
+    d.M, d.N, d.K = M, N, K
+    d.ws, d.ws_bytes = _workspace(a.device).data_ptr(), _WS_BYTES
+    return d
+
+
 def _chk16(t, what):
     if t.dtype != torch.float16:
         raise TypeError(f"{what}: expected float16, got {t.dtype}")
@@ -145,15 +181,27 @@ def ln_fold_ok(C):
     return LN_FOLD and C % 160 == 0 and C // 160 <= 8 and C % 64 == 0
 
 
+def ln_out_arg(ln_out):
+    """the ln_out keyword of gemm / Conv2d.hip / Linear.hip -- None | False (no statistics), True (allocate) or a float32
+    tensor -- with "none" spelled one way: None"""
+    return None if ln_out is False else ln_out
+
+
+def _row_stats(what, dims, rows, cols, device, given=None):
+    """the float32 [rows, cols / 160, 2] partial row sums (the layout gemm(ln=...) takes): `given` checked, or a new tensor"""
+    if given is None or given is True:
+        return torch.empty((rows, cols // 160, 2), dtype=torch.float32, device=device)
+    if given.dtype != torch.float32 or not given.is_contiguous() or given.numel() != rows * (cols // 160) * 2:
+        raise ValueError(f"{what} must be a contiguous float32 [{dims}]")
+    return given
+
+
 def ln_rowstats(x, out=None):
     """partial row sums [M, C/160, 2] (fp32) of a token matrix, in the layout gemm(ln=...) takes -- for tensors that
     were not written by a gemm(ln_out=...) launch"""
     _chk16(x, "ln_rowstats x")
     M, Cc, ld = _rows(x)
-    if out is None:
-        out = torch.empty((M, Cc // 160, 2), dtype=torch.float32, device=x.device)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != M * (Cc // 160) * 2:
-        raise ValueError("ln_rowstats: out must be a contiguous float32 [M, C/160, 2]")
+    out = _row_stats("ln_rowstats: out", "M, C/160, 2", M, Cc, x.device, out)
     _b.check(_lib().pfd_ln_rowstats_f16(x.data_ptr(), ld, M, Cc, out.data_ptr(), _stream()), "pfd_ln_rowstats_f16")
     return out
 
@@ -283,22 +331,14 @@ def gemm(a, w, *, bias=None, rowvec=None, rows_per_rv=1, res=None, act=ACT_NONE,
         _chk16(out, "gemm out")
         if out.device != a.device or out.shape[-1] != n_out or out.numel() != M * n_out:
             raise ValueError(f"gemm: out {tuple(out.shape)} on {out.device} cannot hold [{M}, {n_out}] on {a.device}")
-    _, _, ldc = _rows(out)
-    d = _b.PfdGemmDesc()
+    d = _gemm_desc(a, w, out, M, N, K, lda, ldw, bias, rowvec, res)
     if out_t is not None:
         _chk16(out_t, "gemm out_t")
         if out_t.shape[0] != N - n_split or out_t.shape[1] < M or out_t.stride(1) != 1:
             raise ValueError(f"gemm: out_t {tuple(out_t.shape)} cannot hold [{N - n_split}, {M}]")
         d.Ct, d.ldct, d.n_split = out_t.data_ptr(), out_t.stride(0), n_split
-    d.A, d.W, d.C = a.data_ptr(), w.data_ptr(), out.data_ptr()
-    d.bias, d.rowvec, d.R = _ptr(bias), _ptr(rowvec), _ptr(res)
-    d.lda, d.ldw, d.ldc = lda, ldw, ldc
-    d.ldr = _rows(res)[2] if res is not None else 0
-    d.ldrv = _rows(rowvec)[2] if rowvec is not None else 0
-    d.M, d.N, d.K = M, N, K
     d.rows_per_rv, d.act, d.bias_per_row = rows_per_rv, act, 1 if bias_per_row else 0
     d.ksize = 0
-    d.ws, d.ws_bytes = _workspace(a.device).data_ptr(), _WS_BYTES
     if a2 is not None:
         d.A2, d.lda2, d.k_split = a2.data_ptr(), lda2, Ka
     d.zero_rows = zero_rows
@@ -317,23 +357,15 @@ def gemm(a, w, *, bias=None, rowvec=None, rows_per_rv=1, res=None, act=ACT_NONE,
             raise ValueError("gemm: ln column sums must be a contiguous float32 [N]")
         d.ln_stats, d.ln_colsum, d.ln_parts, d.ln_eps = st.data_ptr(), cs.data_ptr(), st.shape[1], float(eps)
     stats = None
-    if ln_out is not None and ln_out is not False:
-        if ln_out is True:
-            stats = torch.empty((M, N // 160, 2), dtype=torch.float32, device=a.device)
-        else:
-            stats = ln_out
-            if stats.dtype != torch.float32 or not stats.is_contiguous() or stats.numel() != M * (N // 160) * 2:
-                raise ValueError("gemm: ln_out must be a contiguous float32 [M, N/160, 2]")
+    ln_out = ln_out_arg(ln_out)
+    if ln_out is not None:
+        stats = _row_stats("gemm: ln_out", "M, N/160, 2", M, N, a.device, ln_out)
         d.ln_out = stats.data_ptr()
     gst = None
     if gn_out:
         gst = _new_gn_stats(M, N, a.device)
         d.gn_out = gst.data_ptr()
-    if _TRACE:
-        _trace(d)
-    lib = _lib()
-    rc = lib.pfd_gemm_f16_ex(_byref(d), tile, _stream()) if tile else lib.pfd_gemm_f16(_byref(d), _stream())
-    _b.check(rc, f"pfd_gemm_f16 M{M} N{N} K{K}")
+    _launch(d, tile, f"pfd_gemm_f16 M{M} N{N} K{K}")
     _written(out, gst)
     return out if stats is None else (out, stats)
 
@@ -345,16 +377,9 @@ def conv_gn_fusable(B, H, W_, C1, C2, N, ksize=3, stride=1, pad=1):
             (B * H * W_) % 256 == 0 and N % 160 == 0 and C1 % 64 == 0 and C2 % 64 == 0)
 
 
-# Shapes whose fused GroupNorm request (conv(gn_fuse=...)) the library declined once (it decides whether a problem splits K):
-# not asked again.  Key: everything the decision depends on.
-_GNF_DECLINED = set()
-
-
 # Upsample convolutions as four 2x2-tap phase convolutions (PfdGemmDesc.ups = 2) where the library serves the shape;
 # PFD_UPS_FOLD=0: every upsample convolution runs the 9-tap gather of ups = 1 (A/B runs)
 UPS_FOLD = os.environ.get("PFD_UPS_FOLD", "1") != "0"
-# Shapes whose phase-folded upsample convolution (conv(ups=2)) the library declined once: not asked again.
-_UPS_FOLD_DECLINED = set()
 
 
 def ups_fold_key(x, N, act, bias, out, gn_out):
@@ -364,7 +389,7 @@ def ups_fold_key(x, N, act, bias, out, gn_out):
 
 
 def ups_fold_declined(key):
-    return key in _UPS_FOLD_DECLINED
+    return key in _DECLINED
 
 
 def conv(x, w, ksize, *, stride=1, pad=None, ups=False, bias=None, rowvec=None, res=None, act=ACT_NONE,
@@ -418,7 +443,7 @@ def conv(x, w, ksize, *, stride=1, pad=None, ups=False, bias=None, rowvec=None, 
             raise ValueError(f"conv: ups=2 takes the folded weight [4, N, {4 * Cin}] of a 3x3 convolution, got {tuple(w.shape)}")
         N, K, ldw = w.shape[1], w.shape[2], w.shape[2]
         fold_key = ups_fold_key(x, N, act, bias, out, gn_out)
-        if tile == 0 and fold_key in _UPS_FOLD_DECLINED:
+        if tile == 0 and fold_key in _DECLINED:
             return None
     else:
         N, K, ldw = _rows(w)
@@ -431,17 +456,10 @@ def conv(x, w, ksize, *, stride=1, pad=None, ups=False, bias=None, rowvec=None, 
         _chk16(out, "conv out")
         if out.device != x.device or out.shape[-1] != N or out.numel() != M * N:
             raise ValueError(f"conv: out {tuple(out.shape)} on {out.device} cannot hold [{B},{Ho},{Wo},{N}]")
-    d = _b.PfdGemmDesc()
-    d.A, d.W, d.C = x.data_ptr(), w.data_ptr(), out.data_ptr()
-    d.bias, d.rowvec, d.R = _ptr(bias), _ptr(rowvec), _ptr(res)
-    d.lda, d.ldw, d.ldc = lda, ldw, _rows(out)[2]
-    d.ldr = _rows(res)[2] if res is not None else 0
-    d.ldrv = _rows(rowvec)[2] if rowvec is not None else 0
-    d.M, d.N, d.K = M, N, K
+    d = _gemm_desc(x, w, out, M, N, K, lda, ldw, bias, rowvec, res)
     d.rows_per_rv, d.act, d.bias_per_row = (Ho * Wo if rows_per_rv is None else rows_per_rv), act, 0
     d.ksize, d.stride, d.pad, d.ups = ksize, stride, pad, 2 if phase else 1 if ups else 0
     d.B, d.H, d.Wd, d.Cin, d.Ho, d.Wo = B, H, W_, Cin, Ho, Wo
-    d.ws, d.ws_bytes = _workspace(x.device).data_ptr(), _WS_BYTES
     if gn is not None:
         d.gn_table, d.gn_c1, d.gn_act = table.data_ptr(), C1, ACT_SILU if gn_silu else ACT_NONE
         if x2 is not None:
@@ -455,7 +473,7 @@ def conv(x, w, ksize, *, stride=1, pad=None, ups=False, bias=None, rowvec=None, 
         #  and only for heuristic calls: a decline under a forced tile says nothing about the heuristic's choice)
         key = (B, H, W_, Cin, N, ksize, stride, pad, bool(ups), Ho, Wo, act, rowvec is not None,
                None if rowvec is None else d.rows_per_rv, res is not None, int(d.lda), int(d.ldc), int(d.ldr), str(x.device))
-        if tile == 0 and key in _GNF_DECLINED:
+        if tile == 0 and key in _DECLINED:
             return None
         _chk16(g_gamma, "conv gn_fuse gamma")
         _chk16(g_beta, "conv gn_fuse beta")
@@ -464,35 +482,16 @@ def conv(x, w, ksize, *, stride=1, pad=None, ups=False, bias=None, rowvec=None, 
         y = torch.empty((B, Ho, Wo, N), dtype=torch.float16, device=x.device)
         d.gnf_gamma, d.gnf_beta, d.gnf_y, d.gnf_ldy = g_gamma.data_ptr(), g_beta.data_ptr(), y.data_ptr(), N
         d.gnf_eps, d.gnf_act, d.gnf_rows, d.gnf_skip_raw = float(g_eps), ACT_SILU if g_silu else ACT_NONE, Ho * Wo, 0 if g_keep else 1
-        lib = _lib()
-        rc = lib.pfd_gemm_f16_ex(_byref(d), tile, _stream()) if tile else lib.pfd_gemm_f16(_byref(d), _stream())
-        if rc == _b.PFD_ESHAPE:      # nothing was launched (include/pfd_hip.h)
-            if tile == 0:
-                _GNF_DECLINED.add(key)
+        if not _launch(d, tile, f"pfd_gemm_f16(conv, fused GroupNorm) M{M} N{N} K{K}", key):
             return None
-        _b.check(rc, f"pfd_gemm_f16(conv, fused GroupNorm) M{M} N{N} K{K}")
-        if _TRACE:
-            _trace(d)
         return (_written(out) if g_keep else None), y
     if gn_out and gn is None and gn_stats_wanted(B, Ho * Wo, N) and Cin % 64 == 0:   # (True = "where a GroupNorm will use them")
         gst = _new_gn_stats(M, N, x.device)
         d.gn_out = gst.data_ptr()
-    if phase:
-        lib = _lib()
-        rc = lib.pfd_gemm_f16_ex(_byref(d), tile, _stream()) if tile else lib.pfd_gemm_f16(_byref(d), _stream())
-        if rc == _b.PFD_ESHAPE:      # nothing was launched, nothing written (include/pfd_hip.h)
-            if tile == 0:
-                _UPS_FOLD_DECLINED.add(fold_key)
-            return None
-        _b.check(rc, f"pfd_gemm_f16(conv, phase-folded upsample) M{M} N{N} K{K}")
-        if _TRACE:
-            _trace(d)
-        return _written(out, gst)
-    if _TRACE:
-        _trace(d)
-    lib = _lib()
-    rc = lib.pfd_gemm_f16_ex(_byref(d), tile, _stream()) if tile else lib.pfd_gemm_f16(_byref(d), _stream())
-    _b.check(rc, f"pfd_gemm_f16(conv) M{M} N{N} K{K}" + (" with GroupNorm prologue" if gn is not None else ""))
+    form = ", phase-folded upsample" if phase else ""
+    if not _launch(d, tile, f"pfd_gemm_f16(conv{form}) M{M} N{N} K{K}" + (" with GroupNorm prologue" if gn is not None else ""),
+                   fold_key if phase else None):
+        return None
     return _written(out, gst)
 
 
@@ -859,8 +858,7 @@ def add_rowvec(x, v, out=None, ln_out=None):
     if out is None:
         out = torch.empty(x.shape, dtype=torch.float16, device=x.device)
     if ln_out is not None:
-        if ln_out.dtype != torch.float32 or not ln_out.is_contiguous() or ln_out.numel() != R * (Cc // 160) * 2:
-            raise ValueError("add_rowvec: ln_out must be a contiguous float32 [R, C/160, 2]")
+        ln_out = _row_stats("add_rowvec: ln_out", "R, C/160, 2", R, Cc, x.device, ln_out)
         _b.check(_lib().pfd_add_rowvec_lnstats_f16(x.data_ptr(), ldx, v.data_ptr(), out.data_ptr(), _rows(out)[2], R, Cc,
                                                    ln_out.data_ptr(), _stream()), "pfd_add_rowvec_lnstats_f16")
         return _written(out)

@@ -71,6 +71,27 @@ def test_splitk_reduce_with_fused_groupnorm(emu):
     assert len(lines) == 1 and all("unsplit request declined, nothing written" in l for l in lines), "\n".join(lines)
 
 
+DISPATCH_SHAPES = ("unet_c2_gemm_shapes.txt", "ups_phase_fold_shapes.txt", "lin_shapes_ablation.txt", "r06_fixed_cost_probe_shapes.txt")
+
+
+def test_dispatch_table_is_pinned(emu):
+    """what pfd_gemm160_try decides -- kernel instantiation, grid, split count, the G160Params it hands over -- for every record of
+    the tracked launch lists under the heuristic, for hand-written requests (LayerNorm fold, transposed tail, GroupNorm
+    prologue, tiled weights, 128-wide problems, requests that must be declined) and for a dozen records under every forced
+    variant: `emu_gemm --dispatch` (a dry run: nothing is emulated) against tests/golden/gemm_dispatch.txt, line for line.
+    A change of the heuristic regenerates the fixture and shows up as a reviewed diff of it.
+    The kernel names in the text ("gemm160_kernel<4, 4, false, 2, 5>") are the demangled type name of a tag template, cut to size by
+    emu::kernel_name (tools/cpu_emu/hip/hip_runtime.h): if EVERY line differs, and only in how those names are spelled, after a
+    compiler / C++ runtime update, the demangler's format moved, not the dispatcher."""
+    files = [os.path.join(REPO, "profiles", f) for f in DISPATCH_SHAPES]
+    r = subprocess.run([emu, "--dispatch"] + files, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = r.stdout.splitlines()
+    want = open(os.path.join(REPO, "tests", "golden", "gemm_dispatch.txt")).read().splitlines()
+    diff = [f"line {i + 1}:\n  fixture: {w}\n  probe:   {g}" for i, (w, g) in enumerate(zip(want, got)) if w != g]
+    assert not diff and len(got) == len(want), f"{len(diff)} lines differ, {len(got)} lines against {len(want)} in the fixture\n" + "\n".join(diff[:5])
+
+
 def test_attention_kernels_on_the_emulation(emu):
     """csrc/attention.hip on the same emulation (v_mfma_f32_32x32x16_f16, v_permlane16_swap, 16-byte clears of the LDS image):
     the 8-wave d = 40 form and the 4-wave forms against a double-precision softmax(Q K^T) V at d = 40 / 80 / 96 / 160 with

@@ -10,7 +10,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
-CSRC = os.path.join(REPO, "prompt-free-diffusion_amd", "csrc")
+CSRC = os.environ.get("EMU_CSRC") or os.path.join(REPO, "prompt-free-diffusion_amd", "csrc")   # EMU_CSRC: the kernel files of another checkout
 CXX = os.environ.get("EMU_CXX", "/opt/rocm/lib/llvm/bin/clang++")
 
 SUBST = [

@@ -6,9 +6,13 @@
 // compared with a double-precision reference.  What it cannot see: s_waitcnt counts (a copy lands when it is issued),
 // register allocation, timing.
 //   usage: emu_gemm [case ...]      no argument = the built-in list; exit code = number of failed cases
+//          emu_gemm --dispatch [--sweep] FILE...    what the dispatcher decides, one text line per call, nothing executed
+//                                                   (tests/golden/gemm_dispatch.txt; see "dispatch probe" below)
 #include <stdio.h>
 
+#include <array>
 #include <random>
+#include <set>
 #include <string>
 
 #include "hip/hip_runtime.h"
@@ -22,7 +26,10 @@ void pfd_prof_end(hipStream_t) {}
 static std::string g_err;
 int pfd_check_launch(const char*) { return 0; }
 void pfd_set_error(const char* m) { g_err = m; }
-int pfd_ln_rowstats_launch(const half_t*, long, int, int, float*, hipStream_t, bool) { return PFD_ESHAPE; }
+int pfd_ln_rowstats_launch(const half_t*, long, int, int, float*, hipStream_t, bool) {   // (norm.hip: not part of this build)
+  if (emu::dry_run) emu::launch_log.push_back({"pfd_ln_rowstats_launch (norm.hip)", 0, 0, 0, {}});
+  return PFD_ESHAPE;
+}
 
 #include "gemm_glds_emu.inc"
 
@@ -269,7 +276,216 @@ static int run_case(const Case& c) {
   return fails;
 }
 
+// ---- dispatch probe: emu_gemm --dispatch FILE... ----
+// A dry run of pfd_gemm160_try (emu::dry_run: launches are recorded, nothing executes, no pointer is dereferenced) over
+//  (a) every distinct record of the given PFD_TRACE_GEMM files (TRACE_FIELDS of lib/hip/ops.py: 19, 22 or 24 integers, short
+//      ones zero-padded) under the heuristic (variant 0, splits 0);
+//  (b) hand-written requests for what a record does not carry (LayerNorm fold, transposed tail, GroupNorm prologue, tiled
+//      weights, 128-wide problems, requests that must be declined);
+//  (c) a dozen records under every forced variant that serves them, splits 0 and 2.
+// One line per call: the record, "v <variant> s <splits> -> <return value>", then per launch the instantiated kernel, grid x / z,
+// block x, the named integer fields of the G160Params it was handed (the rarely set ones only where they are set), its non-null
+// pointers and whether A2 == A.  Named fields only: the struct is filled field by field and has padding.  --sweep: every record under variant 0 and every
+// variant code with splits 0 1 2 3 4 8 instead (comparing two builds of the dispatcher).
+typedef std::array<long, 24> Rec;
+static void* fake(int i) { return reinterpret_cast<void*>((uintptr_t)0x10000 * (i + 1)); }   // 16-byte aligned, never dereferenced
+enum { P_A, P_W, P_BIAS, P_RV, P_R, P_C, P_WS, P_A2, P_GNO, P_GAMMA, P_BETA, P_Y, P_CT, P_LNS, P_LNC, P_LNO, P_TABLE };
+
+static PfdGemmDesc desc_of(const Rec& q) {   // as selftest --replay and ops.gemm / ops.conv fill it
+  PfdGemmDesc d;
+  memset(&d, 0, sizeof(d));
+  d.M = q[0]; d.N = q[1]; d.K = q[2]; d.act = q[3];
+  d.A = fake(P_A); d.W = fake(P_W); d.C = fake(P_C);
+  d.bias = q[4] ? fake(P_BIAS) : nullptr; d.rowvec = q[5] ? fake(P_RV) : nullptr; d.R = q[6] ? fake(P_R) : nullptr;
+  d.bias_per_row = q[7];
+  d.ksize = q[8]; d.stride = q[9]; d.pad = q[10]; d.ups = q[11];
+  d.B = q[12]; d.H = q[13]; d.Wd = q[14]; d.Cin = q[15]; d.Ho = q[16]; d.Wo = q[17];
+  d.rows_per_rv = (int)std::min<long>(q[18], 1 << 30);
+  const long nout = d.act == PFD_ACT_GEGLU ? d.N / 2 : d.N;
+  d.lda = d.ksize > 0 ? d.Cin : d.K; d.ldw = d.K; d.ldc = nout; d.ldr = nout; d.ldrv = d.N;
+  d.ws = fake(P_WS); d.ws_bytes = (size_t)96 << 20;   // ops._WS_BYTES
+  if (q[19] > 0) { d.k_split = (int)q[19]; d.A2 = fake(P_A2); d.lda = d.k_split; d.lda2 = d.K - d.k_split; }
+  d.zero_rows = (int)q[20];
+  if (q[21]) d.gn_out = fake(P_GNO);
+  if (q[22]) {
+    d.gnf_gamma = fake(P_GAMMA); d.gnf_beta = fake(P_BETA); d.gnf_y = fake(P_Y); d.gnf_ldy = nout; d.gnf_eps = 1e-5f; d.gnf_act = PFD_ACT_SILU;
+    d.gnf_rows = d.ksize > 0 ? d.Ho * d.Wo : (int)std::min<long>(q[18], d.M);
+    d.gnf_skip_raw = q[22] == 2;
+  }
+  if (q[23] > 0 && d.R && !q[22]) d.res_rows = (int)q[23];
+  return d;
+}
+
+static std::string launches_text() {
+  std::string out, prev;
+  char b[1024];
+  for (const auto& l : emu::launch_log) {
+    snprintf(b, sizeof(b), " | %s grid %ux%u block %u", l.kernel.c_str(), l.grid_x, l.grid_z, l.block_x);
+    out += b;
+    if (l.args.empty() || l.args[0].size() != sizeof(G160Params)) continue;
+    G160Params p;
+    memcpy(&p, l.args[0].data(), sizeof(p));
+    snprintf(b, sizeof(b), " tiles_m=%d tiles_n=%d splits=%d kt_per_split=%d k_split=%d rows_per_rv=%d", p.tiles_m, p.tiles_n, p.splits, p.kt_per_split,
+             p.k_split, p.rows_per_rv);
+    std::string t = b;
+    // the other named fields where they differ from kFieldDefaults (the first line of the output)
+    const struct { const char* name; long v, dflt; } opt[] = {{"nmajor", p.nmajor, 0}, {"krot", p.krot, 0}, {"pt_w", p.pt_w, 0}, {"pt_sh", p.pt_sh, 0},
+        {"w_tu", p.w_tu, 0}, {"w_kstep", p.w_kstep, 64}, {"zero_rows", p.zero_rows, 0}, {"r_wrap", p.r_wrap, 0x7fffffff}, {"gn_c1", p.gn_c1, 0},
+        {"gn_act", p.gn_act, 0}, {"ln_P", p.ln_P, 0}};
+    for (const auto& o : opt)
+      if (o.v != o.dflt) t += std::string(" ") + o.name + "=" + std::to_string(o.v);
+    t += " ptr";   // the non-null pointer fields (every other pointer of the struct is null)
+    const std::pair<const char*, const void*> ptrs[] = {{"A", p.A}, {"W", p.W}, {"bias", p.bias}, {"rowvec", p.rowvec}, {"R", p.R}, {"C", p.C},
+        {"ws", p.ws}, {"Ct", p.Ct}, {"ln_in", p.ln_in}, {"ln_cs", p.ln_cs}, {"ln_out", p.ln_out}, {"gn_table", p.gn_table}, {"A2", p.A2}, {"gn_out", p.gn_out}};
+    for (const auto& q : ptrs)
+      if (q.second) t += std::string(" ") + q.first;
+    t += p.A2 == p.A ? " A2==A" : " A2!=A";
+    out += t == prev ? " (the same parameters)" : t;
+    prev = t;
+    if (l.args.size() > 1 && l.args[1].size() == sizeof(GnFuse)) {
+      GnFuse f;
+      memcpy(&f, l.args[1].data(), sizeof(f));
+      snprintf(b, sizeof(b), " gnf: ldy=%ld act=%d rows=%d skip_raw=%d ptr%s%s%s", f.ldy, f.act, f.rows, f.skip_raw, f.gamma ? " gamma" : "",
+               f.beta ? " beta" : "", f.y ? " y" : "");
+      out += b;
+    }
+  }
+  return out;
+}
+static const char kFieldDefaults[] = "# fields printed only where they differ: nmajor=0 krot=0 pt_w=0 pt_sh=0 w_tu=0 w_kstep=64 zero_rows=0 r_wrap=2147483647 "
+                                     "gn_c1=0 gn_act=0 ln_P=0; pointers not listed after \"ptr\" are null";
+
+// one call, one line; served_only: print nothing unless the call returned 0
+static void probe(const std::string& what, const PfdGemmDesc& d, int variant, int splits, bool served_only = false) {
+  emu::launch_log.clear();
+  emu::launched.clear();
+  const int rc = pfd_gemm160_try(&d, variant, splits, nullptr);
+  if (served_only && rc != 0) return;
+  printf("%s v %d s %d -> %d%s\n", what.c_str(), variant, splits, rc, launches_text().c_str());
+}
+
+static std::string rec_text(const Rec& q) {
+  std::string s;
+  for (long v : q) s += (s.empty() ? "" : " ") + std::to_string(v);
+  return s;
+}
+static Rec rec_of(const char* line, int* nfields = nullptr) {
+  Rec r{};
+  int n = 0, off = 0, adv = 0;
+  while (n < 24 && sscanf(line + off, "%ld%n", &r[n], &adv) == 1) { ++n; off += adv; }
+  if (nfields) *nfields = n;
+  return r;
+}
+
+static const int kVariants[] = {22, 23, 24, 25, 41, 43, 44, 47, 48, 82, 83, 84, 96, 98, 99};
+
+static int dispatch_probe(int argc, char** argv) {
+  emu::dry_run = true;
+  bool sweep = false;
+  puts(kFieldDefaults);
+  for (int i = 0; i < argc; ++i) {
+    if (!strcmp(argv[i], "--sweep")) { sweep = true; continue; }
+    FILE* f = fopen(argv[i], "r");
+    if (!f) { fprintf(stderr, "emu_gemm: cannot open %s\n", argv[i]); return 2; }
+    const char* base = strrchr(argv[i], '/');
+    printf("# %s\n", base ? base + 1 : argv[i]);
+    std::set<Rec> seen;
+    char line[512];
+    for (int ln = 1; fgets(line, sizeof(line), f); ++ln) {
+      int n;
+      const Rec q = rec_of(line, &n);
+      if (n == 0) continue;
+      if (n != 19 && n != 22 && n != 24) { fprintf(stderr, "emu_gemm: %s:%d: %d fields\n", argv[i], ln, n); return 2; }
+      if (!seen.insert(q).second) continue;
+      const PfdGemmDesc d = desc_of(q);
+      probe(rec_text(q), d, 0, 0);
+      if (sweep)
+        for (int v : {0, 22, 23, 24, 25, 41, 43, 44, 47, 48, 82, 83, 84, 96, 98, 99})
+          for (int s : {0, 1, 2, 3, 4, 8})
+            if (v || s) probe(rec_text(q), d, v, s);
+    }
+    fclose(f);
+  }
+  if (sweep) return 0;
+
+  // (b) what a launch record does not carry, named after the model shape it stands for
+  printf("# hand-written requests\n");
+  auto lin = [](int M, int N, int K, int act, bool bias, bool res) { return desc_of(Rec{M, N, K, act, bias, 0, res, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1}); };
+  auto conv3 = [](int B, int H, int Cin, int N, int ups = 0, bool res = false) {
+    const int Ho = ups ? 2 * H : H;
+    return desc_of(Rec{(long)B * Ho * Ho, N, (ups == 2 ? 4 : 9) * Cin, 0, 1, 0, res, 0, 3, 1, 1, ups, B, H, H, Cin, Ho, Ho, (long)Ho * Ho});
+  };
+  auto ln_in = [](PfdGemmDesc d) { d.ln_stats = fake(P_LNS); d.ln_colsum = fake(P_LNC); d.ln_parts = d.K / 160; d.ln_eps = 1e-5f; return d; };
+  auto ln_out = [](PfdGemmDesc d) { d.ln_out = fake(P_LNO); return d; };
+  auto tail = [](PfdGemmDesc d, int n_split) { d.Ct = fake(P_CT); d.ldct = d.M; d.n_split = n_split; d.ldc = n_split; return d; };
+  auto gn_pro = [](PfdGemmDesc d, int c1, int act) {
+    d.gn_table = fake(P_TABLE); d.gn_c1 = c1; d.gn_act = act;
+    if (c1 < d.Cin) { d.lda = c1; d.A2 = fake(P_A2); d.lda2 = d.Cin - c1; }
+    return d;
+  };
+  auto tiled = [](PfdGemmDesc d) { d.w_tiled = 1; return d; };
+  probe("64^2 norm1 -> q|k|v 32768x960x320, LayerNorm fold (ln_stats + ln_colsum)", ln_in(lin(32768, 960, 320, 0, false, false)), 0, 0);
+  probe("32^2 norm3 -> GEGLU projection 8192x5120x640, LayerNorm fold", ln_in(lin(8192, 5120, 640, PFD_ACT_GEGLU, true, false)), 0, 0);
+  probe("64^2 norm2 -> to_q 32768x320x320, LayerNorm fold, also emits ln_out", ln_out(ln_in(lin(32768, 320, 320, 0, false, false))), 0, 0);
+  probe("16^2 norm2 -> to_q 2048x1280x1280, LayerNorm fold, also emits ln_out", ln_out(ln_in(lin(2048, 1280, 1280, 0, false, false))), 0, 0);
+  probe("64^2 out-projection 32768x320x320 + residual, emits ln_out", ln_out(lin(32768, 320, 320, 0, true, true)), 0, 0);
+  probe("8^2 ff-out 512x1280x5120 + residual, emits ln_out (split K: statistics by the stand-alone kernel)", ln_out(lin(512, 1280, 5120, 0, true, true)), 0, 0);
+  probe("32^2 fused q|k|v 8192x1920x640, v transposed (Ct, n_split 1280), LayerNorm fold", tail(ln_in(lin(8192, 1920, 640, 0, false, false)), 1280), 0, 0);
+  probe("16^2 fused q|k|v 2048x3840x1280, v transposed (Ct, n_split 2560)", tail(lin(2048, 3840, 1280, 0, false, false), 2560), 0, 0);
+  probe("SeeCoder q|k|v 4096x384x128 (128-wide), v transposed (Ct, n_split 256)", tail(lin(4096, 384, 128, 0, true, false), 256), 0, 0);
+  probe("32^2 ResBlock conv 640 -> 640, GroupNorm + SiLU prologue (gn_table, one source)", gn_pro(conv3(8, 32, 640, 640), 640, PFD_ACT_SILU), 0, 0);
+  probe("32^2 output ResBlock conv 1280|640 -> 640, GroupNorm + SiLU prologue over the skip concat (gn_table, A2)", gn_pro(conv3(8, 32, 1920, 640), 1280, PFD_ACT_SILU), 0, 0);
+  probe("64^2 conv 320 -> 320, GroupNorm prologue without SiLU (gn_table, one source)", gn_pro(conv3(8, 64, 320, 320), 320, PFD_ACT_NONE), 0, 0);
+  probe("64^2 conv 320|320 -> 320, GroupNorm prologue without SiLU (gn_table, A2), variant 98 named", gn_pro(conv3(8, 64, 640, 320), 320, PFD_ACT_NONE), 98, 0);
+  probe("64^2 conv 320 -> 320 on a 48-wide image, GroupNorm prologue (pixel tiles)", gn_pro(desc_of(Rec{8 * 64 * 48, 320, 2880, 0, 1, 0, 0, 0, 3, 1, 1, 0, 8, 64, 48, 320, 64, 48, 64 * 48}), 320, PFD_ACT_SILU), 0, 0);
+  probe("16^2 linear 2048x1280x1280, K-tile-contiguous weight (w_tiled)", tiled(lin(2048, 1280, 1280, 0, true, true)), 0, 0);
+  probe("16^2 conv 1280 -> 1280, K-tile-contiguous weight (w_tiled)", tiled(conv3(8, 16, 1280, 1280)), 0, 0);
+  probe("VAE 512 -> 512 linear 4096x512x512, K-tile-contiguous weight (w_tiled, 128-wide)", tiled(lin(4096, 512, 512, 0, true, false)), 0, 0);
+  probe("VAE mid attention projection 4096x512x512 (128-wide, 64-row tile)", lin(4096, 512, 512, 0, true, true), 0, 0);
+  probe("VAE 64^2 conv 512 -> 512 (128-wide, 128-row tile)", conv3(1, 64, 512, 512), 0, 0);
+  probe("VAE 256^2 conv 256 -> 128 (128-wide, 256-row tile, loader waves)", conv3(1, 256, 256, 128), 0, 0);
+  probe("Swin linear 65536x256x4096 (128-wide, 256-row tile)", lin(65536, 256, 4096, 0, true, false), 0, 0);
+  printf("# requests that must be declined (return value 1)\n");
+  {
+    PfdGemmDesc d = conv3(16, 32, 640, 640);   // 256 patch tiles: not split
+    d.gnf_gamma = fake(P_GAMMA); d.gnf_beta = fake(P_BETA); d.gnf_y = fake(P_Y); d.gnf_ldy = d.N; d.gnf_eps = 1e-5f; d.gnf_act = PFD_ACT_SILU; d.gnf_rows = 1024;
+    probe("fused GroupNorm (gnf_y) on 32^2 conv 640 -> 640 with 16 samples: a problem that does not split", d, 0, 0);
+    d = lin(32768, 1280, 320, 0, true, true);
+    d.gnf_gamma = fake(P_GAMMA); d.gnf_beta = fake(P_BETA); d.gnf_y = fake(P_Y); d.gnf_ldy = d.N; d.gnf_eps = 1e-5f; d.gnf_act = PFD_ACT_SILU; d.gnf_rows = 512;
+    probe("fused GroupNorm (gnf_y) on linear 32768x1280x320: a problem that does not split", d, 0, 0);
+  }
+  probe("phase-folded upsample conv (ups = 2) 16^2 1280 -> 1280 with a residual", conv3(8, 16, 1280, 1280, 2, true), 0, 0);
+  probe("skip conv 32768x320x640 over two sources (k_split 320) under variant 47", desc_of(Rec{32768, 320, 640, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 320, 0, 0, 0, 0}), 47, 0);
+  probe("linear 2080x1280x1280 with GroupNorm statistics (gn_out), M % 64 != 0", desc_of(Rec{2080, 1280, 1280, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 0, 0}), 0, 0);
+
+  // (c) every case of the two variant switches and every branch of the loader-wave / patch launchers
+  printf("# forced variants that serve the request (splits 0 and 2)\n");
+  static const char* forced[] = {
+      "8192 640 2560 0 1 0 1 0 0 0 0 0 0 0 0 0 0 0 1",                              // linear, 160-wide
+      "2048 1280 5120 0 1 0 1 0 0 0 0 0 0 0 0 0 0 0 1 0 0 1 0 0",                   // linear + GroupNorm statistics
+      "8192 5120 640 4 1 0 0 0 0 0 0 0 0 0 0 0 0 0 1",                              // GEGLU projection (84)
+      "32768 320 640 0 1 0 0 0 0 0 0 0 0 0 0 0 0 0 1 320 0 0 0 0",                  // two-source contraction
+      "16384 640 640 0 1 0 1 0 0 0 0 0 0 0 0 0 0 0 1 0 8192 0 0 8192",              // zero rows + residual stored once
+      "4096 512 512 0 1 0 1 0 0 0 0 0 0 0 0 0 0 0 1",                               // linear, 128-wide
+      "8192 640 5760 0 1 1 0 0 3 1 1 0 8 32 32 640 32 32 1024",                     // 3x3 conv, patch kernel
+      "2048 1280 11520 0 1 1 0 0 3 1 1 0 8 16 16 1280 16 16 256 0 0 0 1 0",         // 3x3 conv + fused GroupNorm (raw kept)
+      "2048 640 5760 0 1 0 0 0 3 2 1 0 8 32 32 640 16 16 256",                      // stride-2 conv (implicit GEMM)
+      "8192 1280 11520 0 1 0 0 0 3 1 1 1 8 16 16 1280 32 32 1024 0 0 1 0 0",        // upsample conv, 9-tap gather
+      "8192 1280 5120 0 1 0 0 0 3 1 1 2 8 16 16 1280 32 32 1024 0 0 1 0 0",         // upsample conv, phase form
+      "4096 512 4608 0 1 0 0 0 3 1 1 0 1 64 64 512 64 64 4096",                     // 3x3 conv, 128-wide
+      "4096 256 1024 0 1 0 0 0 3 1 1 2 1 32 32 256 64 64 4096",                     // phase form, 128-wide
+  };
+  for (const char* r : forced) {
+    const Rec q = rec_of(r);
+    const PfdGemmDesc d = desc_of(q);
+    for (int v : kVariants)
+      for (int s : {0, 2}) probe(rec_text(q), d, v, s, true);
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "--dispatch")) return dispatch_probe(argc - 2, argv + 2);
   std::vector<Case> cases;
   auto lin = [&](const char* w, int M, int N, int K, int v, int sp, bool res, int base) {
     Case c{w, M, N, K, v, sp}; c.res = res; c.base_variant = base; cases.push_back(c); return &cases.back();

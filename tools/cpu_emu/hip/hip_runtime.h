@@ -15,11 +15,14 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <cxxabi.h>
+
 #include <algorithm>
 #include <cmath>
 #include <functional>
 #include <string>
 #include <thread>
+#include <typeinfo>
 #include <vector>
 
 #define __global__
@@ -59,6 +62,42 @@ inline Block* cur = nullptr;
 inline const void* kernarg = nullptr;
 inline bool dry_run = false;                // record the launches, do not execute them
 inline std::vector<std::string> launched;   // the kernel expression of every launch, in order (hipLaunchKernelGGL's first argument)
+// the same launches in full: the instantiated kernel ("gemm160_kernel<4, 4, false, 2, 5>": the expression above reads
+// <WAVES_M, WMB, ...> inside a launcher template), grid x / z, block x and a byte copy of every kernel argument
+struct LaunchRecord {
+  std::string kernel;
+  unsigned grid_x, grid_z, block_x;
+  std::vector<std::string> args;
+};
+inline std::vector<LaunchRecord> launch_log;
+template <auto K> struct KernelTag {};
+template <auto K>
+inline std::string kernel_name() {   // the tag's type name carries the kernel's linkage name: "emu::KernelTag<&(void (anonymous namespace)::name<args>(params))>"
+  int st = 0;
+  char* d = abi::__cxa_demangle(typeid(KernelTag<K>).name(), nullptr, nullptr, &st);
+  std::string s = d ? d : typeid(KernelTag<K>).name();
+  free(d);
+  s = s.substr(s.find('<') + 1);
+  s = s.substr(0, s.rfind('>'));
+  const std::string anon = "(anonymous namespace)::";
+  for (size_t at; (at = s.find(anon)) != std::string::npos;) s.erase(at, anon.size());
+  size_t start = s.find_first_not_of("&(");   // "&name" or "&(void name<args>(params))": keep name<args>
+  int depth = 0;
+  for (size_t i = start; i < s.size(); ++i) {
+    if (s[i] == '<') ++depth;
+    if (s[i] == '>') --depth;
+    if (depth == 0 && s[i] == ' ') start = i + 1;
+    if (depth == 0 && s[i] == '(') return s.substr(start, i - start);
+  }
+  return s.substr(start);
+}
+template <class... T>
+inline void record(const char* expr, const std::string& name, dim3 grid, dim3 block, const T&... a) {
+  launched.push_back(expr);
+  LaunchRecord r{name, grid.x, grid.z, block.x, {}};
+  (r.args.emplace_back(reinterpret_cast<const char*>(&a), sizeof(a)), ...);
+  launch_log.push_back(r);
+}
 inline int lane() { return t_idx.x & 63; }
 inline Wave& wave() { return cur->waves[t_idx.x >> 6]; }
 inline void wave_sync() { pthread_barrier_wait(&wave().bar); }
@@ -119,7 +158,7 @@ inline T exchange(T v, int src) {   // every lane of the wave calls this; return
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...)                                      \
   do {                                                                                                    \
     auto emu_arg0 = EMU_FIRST(__VA_ARGS__);                                                               \
-    emu::launched.push_back(#kernel);                                                                     \
+    emu::record(#kernel, emu::kernel_name<&kernel>(), grid, block, __VA_ARGS__);                          \
     emu::launch([&]() { kernel(__VA_ARGS__); }, grid, block, &emu_arg0);                                  \
   } while (0)
 

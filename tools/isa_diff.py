@@ -4,7 +4,7 @@ hipcc -S cross-compiles).  The last hardware-validated library of a round is a c
 spent add forced variants / opt-in modes and claim "the ISA of every existing instantiation is unchanged" -- this is
 the check behind that sentence.
 
-usage: isa_diff.py <rev> [file.hip ...]      (default files: every kernel file of csrc/)
+usage: isa_diff.py <rev> [file.hip ...]      (default files: SRCS of csrc/Makefile, each with the flags the Makefile gives it)
 prints one line per kernel: same | CHANGED | new | gone; exit 1 when a kernel that exists in both differs
 (unless it is listed with --allow <substring>, repeatable)."""
 import argparse
@@ -17,7 +17,14 @@ import tempfile
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC_REL = os.path.join("prompt-free-diffusion_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FILES = ("gemm_glds.hip", "gemm_conv.hip", "attention.hip", "swin_attn.hip", "norm.hip", "elementwise.hip")
+
+
+def makefile_sources(root):
+    """{file.hip: [its extra flags]} from csrc/Makefile: the SRCS list and the `build/<file>.o: CXXFLAGS += ...` lines"""
+    text = open(os.path.join(root, CSRC_REL, "Makefile")).read()
+    srcs = re.search(r"^SRCS\s*:?=\s*(.+)$", text, re.M).group(1).split()
+    extra = {m.group(1) + ".hip": m.group(2).split() for m in re.finditer(r"^build/(\w+)\.o:\s*CXXFLAGS\s*\+=\s*(.+)$", text, re.M)}
+    return {f: extra.get(f, []) for f in srcs}
 
 
 def flags(root):
@@ -48,12 +55,13 @@ def kernels(asm_path):
 
 def compile_tree(root, files, tag):
     res = {}
+    extra = makefile_sources(root)
     for f in files:
         src = os.path.join(root, CSRC_REL, f)
         if not os.path.exists(src):
             continue
         asm = os.path.join(tempfile.gettempdir(), f"pfd_isadiff_{tag}_{f}.s")
-        subprocess.run([HIPCC] + flags(root) + [src, "-o", asm], check=True, stderr=subprocess.DEVNULL)
+        subprocess.run([HIPCC] + flags(root) + extra.get(f, []) + [src, "-o", asm], check=True, stderr=subprocess.DEVNULL)
         for k, v in kernels(asm).items():
             res[(f, k)] = v
     return res
@@ -62,7 +70,7 @@ def compile_tree(root, files, tag):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("rev")
-    ap.add_argument("files", nargs="*", default=list(FILES))
+    ap.add_argument("files", nargs="*", default=list(makefile_sources(REPO)))
     ap.add_argument("--allow", action="append", default=[])
     ap.add_argument("--map", action="append", default=[], metavar="OLD=NEW",
                     help="an old symbol that is gone is looked up again with this substring replaced (a template that "
