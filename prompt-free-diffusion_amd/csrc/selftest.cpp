@@ -1,124 +1,15 @@
 // Torch-free self test + micro benchmark of libpfd_hip.so (runs in seconds on a GPU box).
 // Every kernel is checked against a straightforward fp64/fp32 CPU loop over the SAME fp16
 // inputs.  This is test infrastructure: nothing here is linked into the product library.
-//   build/selftest            -> correctness (exit code = number of failed cases)
-//   build/selftest --bench    -> also time the UNet-shaped problems and print TFLOP/s
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <functional>
-#include <random>
-#include <string>
-#include <array>
-#include <atomic>
-#include <thread>
-#include <vector>
-
-#include "pfd_hip.h"
-
-typedef _Float16 h16;
-
-#define HIP_OK(x)                                                                 \
-  do {                                                                            \
-    hipError_t e_ = (x);                                                          \
-    if (e_ != hipSuccess) {                                                       \
-      fprintf(stderr, "HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); \
-      exit(99);                                                                   \
-    }                                                                             \
-  } while (0)
-
-static std::mt19937 rng(1234);
-static int g_fail = 0, g_total = 0;
-
-static std::vector<h16> rand_h(size_t n, float scale = 1.f) {
-  std::uniform_real_distribution<float> d(-1.f, 1.f);
-  std::vector<h16> v(n);
-  for (auto& x : v) x = (h16)(d(rng) * scale);
-  return v;
-}
-static std::vector<float> rand_f(size_t n, float scale = 1.f) {
-  std::uniform_real_distribution<float> d(-1.f, 1.f);
-  std::vector<float> v(n);
-  for (auto& x : v) x = d(rng) * scale;
-  return v;
-}
-template <class T>
-struct Dev {
-  T* p = nullptr;
-  size_t n = 0;
-  Dev() {}
-  explicit Dev(size_t n_) : n(n_) { HIP_OK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T))); HIP_OK(hipMemset(p, 0, std::max<size_t>(n,1) * sizeof(T))); }
-  explicit Dev(const std::vector<T>& h) : n(h.size()) {
-    HIP_OK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-    HIP_OK(hipMemcpy(p, h.data(), n * sizeof(T), hipMemcpyHostToDevice));
-  }
-  ~Dev() { if (p) hipFree(p); }
-  std::vector<T> get() const {
-    std::vector<T> h(n);
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(h.data(), p, n * sizeof(T), hipMemcpyDeviceToHost));
-    return h;
-  }
-  Dev(const Dev&) = delete;
-  Dev& operator=(const Dev&) = delete;
-};
-
-template <class T>
-static void report(const std::string& name, const std::vector<T>& got, const std::vector<double>& ref,
-                   double atol, double rtol) {
-  double worst = 0, maxabs = 0;
-  size_t bad = 0, worst_i = 0;
-  for (size_t i = 0; i < ref.size(); ++i) {
-    const double g = (double)got[i];
-    const double d = fabs(g - ref[i]);
-    const double lim = atol + rtol * fabs(ref[i]);
-    if (!(d <= lim) || !std::isfinite(g)) ++bad;
-    if (d / lim > worst || !std::isfinite(g)) { worst = std::isfinite(g) ? d / lim : 1e30; worst_i = i; }
-    maxabs = std::max(maxabs, d);
-  }
-  ++g_total;
-  if (bad) {
-    ++g_fail;
-    printf("FAIL %-58s bad=%zu/%zu max|d|=%.4g worst@%zu got=%.5g ref=%.5g\n", name.c_str(), bad, ref.size(),
-           maxabs, worst_i, (double)got[worst_i], ref[worst_i]);
-  } else {
-    printf("ok   %-58s max|d|=%.3g\n", name.c_str(), maxabs);
-  }
-  fflush(stdout);
-}
-
-static double act_ref(double v, int act) {
-  switch (act) {
-    case PFD_ACT_GELU: return 0.5 * v * (1.0 + erf(v / sqrt(2.0)));
-    case PFD_ACT_RELU: return v > 0 ? v : 0;
-    case PFD_ACT_SILU: return v / (1.0 + exp(-v));
-    default: return v;
-  }
-}
-
-
-
-// the host references are plain fp64 loops: rows are independent, so they run on the box's host threads (the round-5
-// candidate list took > 400 s single-threaded -- 6 s per case -- and was cut off by its GPU-call limit)
-template <class F>
-static void parallel_rows(int M, F&& body) {
-  unsigned nt = std::thread::hardware_concurrency();
-  nt = std::max(1u, std::min(nt ? nt : 1u, 48u));
-  if (M < 64 || nt == 1) { for (int m = 0; m < M; ++m) body(m); return; }
-  std::vector<std::thread> th;
-  std::atomic<int> next{0};
-  for (unsigned t = 0; t < nt; ++t)
-    th.emplace_back([&]() { for (int m; (m = next.fetch_add(8)) < M;) for (int i = m; i < std::min(M, m + 8); ++i) body(i); });
-  for (auto& t : th) t.join();
-}
+//   build/selftest            -> the default correctness run (exit code = number of failed cases)
+//   build/selftest --help     -> every mode (kModes at the end of this file), and what the default run leaves out
+// This file: the correctness cases, the mode table and main.  selftest_bench.cpp: the timed runs.  selftest_replay.cpp:
+// the launch-list replay.
+#include "selftest_util.h"
 
 // ------------------------------------------------------------------ GEMM / conv
 struct GemmCase {
-  int M, N, K;
+  int M = 0, N = 0, K = 0;
   int act = 0;
   bool bias = true, res = false, rowvec = false, bias_row = false;
   int tile = 0;
@@ -132,6 +23,31 @@ struct GemmCase {
   int res_rows = 0;   // > 0: the residual holds that many rows and is read with one wrap (PfdGemmDesc.res_rows)
   int declined = 0;   // 1: the library must answer PFD_ESHAPE and leave the output untouched
 };
+
+// How the case lists spell a GemmCase: lin(M, N, K) or conv(B, H, W, Cin, N) -- a 3x3 / stride 1 / pad 1 convolution unless
+// .k() / .stride() / .pad() say otherwise -- then one setter per field that leaves its default.  The setters carry the
+// fields' names, so they live in a derived type; run_gemm_case reads the plain GemmCase.
+struct Case : GemmCase {
+  Case& k(int v) { ksize = v; return *this; }
+  Case& stride(int v) { GemmCase::stride = v; return *this; }
+  Case& pad(int v) { GemmCase::pad = v; return *this; }
+  Case& ups(int v) { GemmCase::ups = v; return *this; }   // 1: nearest-2x in the gather, 2: four folded phase blocks
+  Case& act(int v) { GemmCase::act = v; return *this; }
+  Case& no_bias() { bias = false; return *this; }
+  Case& res() { GemmCase::res = true; return *this; }
+  Case& rowvec() { GemmCase::rowvec = true; return *this; }
+  Case& bias_row() { GemmCase::bias_row = true; return *this; }
+  Case& tile(int v) { GemmCase::tile = v; return *this; }   // forced tile code of pfd_gemm_f16_ex
+  Case& ld(int extra) { extra_ld = extra; return *this; }
+  Case& n_split(int v) { GemmCase::n_split = v; return *this; }
+  Case& w_tiled() { GemmCase::w_tiled = 1; return *this; }
+  Case& gn_out() { GemmCase::gn_out = 1; return *this; }
+  Case& res_rows(int v) { GemmCase::res_rows = v; return *this; }
+  Case& zero_rows(int v) { GemmCase::zero_rows = v; return *this; }
+  Case& declined() { GemmCase::declined = 1; return *this; }
+};
+static Case lin(int M, int N, int K) { Case c; c.M = M; c.N = N; c.K = K; return c; }
+static Case conv(int B, int H, int W, int Cin, int N) { Case c; c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.N = N; return c.k(3).pad(1); }
 
 // PfdGemmDesc.ups = 2: the 3x3 weight [N][ldw >= 9 Cin] folded in fp32 and rounded once into four 2x2-tap phase blocks
 // [py][px][N][ldf >= 4 Cin]; phase tap (ty, tx) sums the 3x3 taps that read the same low-res pixel
@@ -205,9 +121,7 @@ static void run_gemm_case(const GemmCase& c) {
       }
   Dev<h16> dA(Adev), dA2(A2dev), dW(Wup), dB(bias), dRV(rv), dR(R), dC((size_t)M * ldc);
   Dev<float> dWS((size_t)8 * M * N + 64);
-  PfdGemmDesc d;
-  memset(&d, 0, sizeof(d));
-  d.ws = dWS.p; d.ws_bytes = ((size_t)8 * M * N + 64) * sizeof(float);
+  PfdGemmDesc d = gemm_desc(dWS);
   d.A = dA.p; d.W = dW.p; d.bias = c.bias ? dB.p : nullptr; d.rowvec = c.rowvec ? dRV.p : nullptr;
   d.R = c.res ? dR.p : nullptr; d.C = dC.p;
   d.lda = lda; d.ldw = ldwd; d.ldr = ldr; d.ldc = ldc; d.ldrv = ldrv;
@@ -245,11 +159,7 @@ static void run_gemm_case(const GemmCase& c) {
     printf("%s %-58s declined: rc=%d, %zu elements written\n", ok ? "ok  " : "FAIL", name, rc, touched);
     return;
   }
-  if (rc != 0) {
-    ++g_total; ++g_fail;
-    printf("FAIL %-58s rc=%d (%s)\n", name, rc, pfd_last_error());
-    return;
-  }
+  if (rc != 0) return fail_rc(name, rc);
   auto got = dC.get();
   // CPU reference
   std::vector<double> pre((size_t)M * N);
@@ -343,45 +253,45 @@ static void run_gemm_case(const GemmCase& c) {
   }
 }
 
-// K-tile-contiguous weights (PfdGemmDesc.w_tiled): every wide-tile kernel family, both tile widths, conv K walks, split-K
 // conv3x3_narrow_kernel (round 6): 3x3 convolutions with N <= 16 output channels
 static void run_narrow_conv_cases() {
-  run_gemm_case({0, 4, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 0, 2, 16, 64, 320});    // the UNet head: 320 -> 4 on a 64-wide image
-  run_gemm_case({0, 3, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 0, 1, 12, 40, 128});    // N = 3 (VAE conv_out), one ragged segment
-  run_gemm_case({0, 4, 0, 0, false, false, false, false, 0, 8, 3, 1, 1, 0, 1, 9, 96, 64});     // no bias, ld + 8, 64 + 32 pixel segments
-  run_gemm_case({0, 8, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 0, 1, 8, 16, 512});     // N = 8: two row groups store
-  run_gemm_case({0, 13, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 0, 1, 5, 130, 64});    // N = 13: element stores, three segments
-  run_gemm_case({0, 4, 0, PFD_ACT_SILU, true, false, false, false, 0, 0, 3, 1, 1, 0, 1, 8, 64, 64});   // an activation: the general kernel
+  run_gemm_case(conv(2, 16, 64, 320, 4));   // the UNet head: 320 -> 4 on a 64-wide image
+  run_gemm_case(conv(1, 12, 40, 128, 3));   // N = 3 (VAE conv_out), one ragged segment
+  run_gemm_case(conv(1, 9, 96, 64, 4).no_bias().ld(+8));   // no bias, ld + 8, 64 + 32 pixel segments
+  run_gemm_case(conv(1, 8, 16, 512, 8));   // N = 8: two row groups store
+  run_gemm_case(conv(1, 5, 130, 64, 13));   // N = 13: element stores, three segments
+  run_gemm_case(conv(1, 8, 64, 64, 4).act(PFD_ACT_SILU));   // an activation: the general kernel
 }
 
 // PfdGemmDesc.ups = 2 against the nearest-2x + 3x3 reference: one 256-row tile per phase, both tile widths, both forms of the
 // loader-wave kernel, statistics, K-tile-contiguous phase blocks, several samples, a 4x16 image, and a declined request
 static void run_ups_fold_cases() {
-  { GemmCase c{0, 320, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 2, 1, 16, 16, 64}; c.gn_out = 1; run_gemm_case(c); }
-  run_gemm_case({0, 160, 0, 0, true, false, false, false, 5800, 0, 3, 1, 1, 2, 1, 16, 16, 64});
-  run_gemm_case({0, 128, 0, PFD_ACT_SILU, true, false, false, false, 0, 8, 3, 1, 1, 2, 1, 16, 16, 64});
-  { GemmCase c{0, 160, 0, 0, false, false, false, false, 0, 0, 3, 1, 1, 2, 3, 8, 32, 128}; c.w_tiled = 1; run_gemm_case(c); }
-  run_gemm_case({0, 320, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 2, 2, 16, 48, 64});
-  { GemmCase c{0, 160, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 2, 1, 8, 8, 64}; c.declined = 1; run_gemm_case(c); }
-  { GemmCase c{0, 160, 0, 0, true, true, false, false, 0, 0, 3, 1, 1, 2, 1, 16, 16, 64}; c.declined = 1; run_gemm_case(c); }   // residual: not served
+  run_gemm_case(conv(1, 16, 16, 64, 320).ups(2).gn_out());
+  run_gemm_case(conv(1, 16, 16, 64, 160).ups(2).tile(5800));
+  run_gemm_case(conv(1, 16, 16, 64, 128).ups(2).act(PFD_ACT_SILU).ld(+8));
+  run_gemm_case(conv(3, 8, 32, 128, 160).ups(2).no_bias().w_tiled());
+  run_gemm_case(conv(2, 16, 48, 64, 320).ups(2));
+  run_gemm_case(conv(1, 8, 8, 64, 160).ups(2).declined());
+  run_gemm_case(conv(1, 16, 16, 64, 160).ups(2).res().declined());   // residual: not served
 }
 
+// K-tile-contiguous weights (PfdGemmDesc.w_tiled): every wide-tile kernel family, both tile widths, conv K walks, split-K
 static void run_tiled_weight_cases() {
   for (int v : {0, 3200, 3300, 3400, 3500, 5400, 5800, 5100, 5300, 9200, 9300}) {
-    GemmCase a{700, 320, 1024, 0, true, true, true, false, v}; a.w_tiled = 1; run_gemm_case(a);
-    GemmCase b{0, 320, 0, 0, true, true, false, false, v, 0, 3, 1, 1, 0, 3, 16, 16, 128}; b.w_tiled = 1; run_gemm_case(b);
+    run_gemm_case(lin(700, 320, 1024).res().rowvec().tile(v).w_tiled());
+    run_gemm_case(conv(3, 16, 16, 128, 320).res().tile(v).w_tiled());
   }
-  { GemmCase c{600, 640, 320, PFD_ACT_GEGLU, true, false, false, false, 9400}; c.w_tiled = 1; run_gemm_case(c); }
-  { GemmCase c{520, 960, 320, 0, false, false, false, false, 0}; c.n_split = 640; c.w_tiled = 1; run_gemm_case(c); }
-  { GemmCase c{900, 320, 1536, 0, true, false, false, false, 3203}; c.w_tiled = 1; run_gemm_case(c); }
-  { GemmCase c{600, 256, 512, 0, true, true, false, false, 5400}; c.w_tiled = 1; run_gemm_case(c); }          // 128-wide tiles
-  { GemmCase c{0, 256, 0, PFD_ACT_SILU, true, true, true, false, 0, 0, 3, 1, 1, 0, 2, 9, 7, 128}; c.w_tiled = 1; run_gemm_case(c); }
+  run_gemm_case(lin(600, 640, 320).act(PFD_ACT_GEGLU).tile(9400).w_tiled());
+  run_gemm_case(lin(520, 960, 320).no_bias().n_split(640).w_tiled());
+  run_gemm_case(lin(900, 320, 1536).tile(3203).w_tiled());
+  run_gemm_case(lin(600, 256, 512).res().tile(5400).w_tiled());   // 128-wide tiles
+  run_gemm_case(conv(2, 9, 7, 128, 256).act(PFD_ACT_SILU).res().rowvec().w_tiled());
   for (int v : {10800, 10600, 10900, 10802}) {   // patch kernels (tap / channel-block walk over the tiled K axis)
-    GemmCase c{0, 320, 0, 0, true, true, true, false, v, 0, 3, 1, 1, 0, 2, 32, 32, 128}; c.w_tiled = 1; run_gemm_case(c);
-    GemmCase e{0, 160, 0, PFD_ACT_SILU, true, false, true, false, v, 0, 3, 1, 1, 0, 1, 64, 64, 256}; e.w_tiled = 1; run_gemm_case(e);
+    run_gemm_case(conv(2, 32, 32, 128, 320).res().rowvec().tile(v).w_tiled());
+    run_gemm_case(conv(1, 64, 64, 256, 160).act(PFD_ACT_SILU).rowvec().tile(v).w_tiled());
   }
-  { GemmCase c{0, 160, 0, PFD_ACT_SILU, true, false, true, false, 5800, 0, 3, 2, 1, 0, 5, 20, 16, 64}; c.w_tiled = 1; run_gemm_case(c); }   // stride 2
-  { GemmCase c{0, 160, 0, 0, true, false, false, false, 5800, 0, 3, 1, 1, 1, 2, 9, 12, 64}; c.w_tiled = 1; run_gemm_case(c); }               // upsample
+  run_gemm_case(conv(5, 20, 16, 64, 160).stride(2).act(PFD_ACT_SILU).rowvec().tile(5800).w_tiled());   // stride 2
+  run_gemm_case(conv(2, 9, 12, 64, 160).ups(1).tile(5800).w_tiled());   // upsample
 }
 
 // ------------------------------------------------------------------ LayerNorm folded into the GEMM (ABI 7)
@@ -420,23 +330,19 @@ static void run_ln_fold_case(int M, int C, int N, int act, int tile_prod, int ti
   Dev<h16> dCt(n_split > 0 ? (size_t)(N - n_split) * ldct : 8);
   char name[200];
   snprintf(name, sizeof(name), "ln-fold M%d C%d N%d act%d prod%d cons%d split%d", M, C, N, act, tile_prod, tile_cons, n_split);
-  PfdGemmDesc d;
-  memset(&d, 0, sizeof(d));
+  PfdGemmDesc d = gemm_desc(dWS);
   d.A = dA0.p; d.W = dW0.p; d.bias = db0.p; d.R = dR0.p; d.C = dX.p;
   d.lda = Kp; d.ldw = Kp; d.ldr = C; d.ldc = C; d.M = M; d.N = C; d.K = Kp; d.rows_per_rv = 1;
-  d.ws = dWS.p; d.ws_bytes = dWS.n * sizeof(float);
   d.ln_out = dst.p;
   int rc = pfd_gemm_f16_ex(&d, tile_prod, nullptr);
   if (rc == 0) rc = pfd_ln_rowstats_f16(dX.p, C, M, C, dst2.p, nullptr);
-  PfdGemmDesc e;
-  memset(&e, 0, sizeof(e));
+  PfdGemmDesc e = gemm_desc(dWS);
   e.A = dX.p; e.W = dWg.p; e.bias = dbp.p; e.C = dY.p;
   e.lda = C; e.ldw = C; e.ldc = Nout; e.M = M; e.N = N; e.K = C; e.rows_per_rv = 1; e.act = act;
-  e.ws = dWS.p; e.ws_bytes = dWS.n * sizeof(float);
   e.ln_stats = dst.p; e.ln_colsum = dcs.p; e.ln_parts = P; e.ln_eps = eps;
   if (n_split > 0) { e.Ct = dCt.p; e.ldct = ldct; e.n_split = n_split; }
   if (rc == 0) rc = pfd_gemm_f16_ex(&e, tile_cons, nullptr);
-  if (rc != 0) { ++g_total; ++g_fail; printf("FAIL %-58s rc=%d (%s)\n", name, rc, pfd_last_error()); return; }
+  if (rc != 0) return fail_rc(name, rc);
   auto X = dX.get();
   auto st = dst.get(), st2 = dst2.get();
   {  // statistics: producer epilogue vs stand-alone kernel vs fp64 over the stored x
@@ -486,88 +392,6 @@ static void run_ln_fold_case(int M, int C, int N, int act, int tile_prod, int ti
   }
 }
 
-// the same 3x3 / s1 / p1 convolution under two forced tile codes: the results must be the same bits, on every one of
-// `reps` launches of the second code (a hand-over protocol that races shows up as a launch that differs)
-static void run_conv_same_case(int B, int H, int W, int Cin, int N, int tile_a, int tile_b, bool res, int reps = 8) {
-  const long M = (long)B * H * W, K = 9L * Cin;
-  auto A = rand_h((size_t)M * Cin), Wt = rand_h((size_t)N * K, 1.7f / sqrtf((float)K)), Bv = rand_h(N), R = rand_h((size_t)M * N);
-  Dev<h16> dA(A), dW(Wt), dB(Bv), dR(R), dC1((size_t)M * N), dC2((size_t)M * N);
-  Dev<float> dWS((size_t)8 * M * N);
-  PfdGemmDesc d;
-  memset(&d, 0, sizeof(d));
-  d.M = (int)M; d.N = N; d.K = (int)K; d.A = dA.p; d.W = dW.p; d.bias = dB.p; d.R = res ? dR.p : nullptr;
-  d.lda = Cin; d.ldw = K; d.ldc = N; d.ldr = N; d.ldrv = N; d.rows_per_rv = 1;
-  d.ksize = 3; d.stride = 1; d.pad = 1; d.B = B; d.H = H; d.Wd = W; d.Cin = Cin; d.Ho = H; d.Wo = W;
-  d.ws = dWS.p; d.ws_bytes = (size_t)8 * M * N * sizeof(float);
-  char name[160];
-  snprintf(name, sizeof(name), "conv3x3 B%d %dx%d %d->%d tile %d == tile %d (bitwise, %d launches)%s", B, H, W, Cin, N, tile_a, tile_b, reps, res ? " +res" : "");
-  ++g_total;
-  d.C = dC1.p;
-  int rc = pfd_gemm_f16_ex(&d, tile_a, nullptr);
-  if (rc != 0) { ++g_fail; printf("FAIL %-58s rc=%d (%s)\n", name, rc, pfd_last_error()); return; }
-  auto y1 = dC1.get();
-  d.C = dC2.p;
-  for (int r = 0; r < reps; ++r) {
-    HIP_OK(hipMemset(dC2.p, 0xFF, (size_t)M * N * sizeof(h16)));
-    rc = pfd_gemm_f16_ex(&d, tile_b, nullptr);
-    if (rc != 0) { ++g_fail; printf("FAIL %-58s rc=%d (%s)\n", name, rc, pfd_last_error()); return; }
-    auto y2 = dC2.get();
-    if (memcmp(y1.data(), y2.data(), y1.size() * sizeof(h16))) {
-      size_t nd = 0;
-      for (size_t i = 0; i < y1.size(); ++i) nd += memcmp(&y1[i], &y2[i], sizeof(h16)) != 0;
-      ++g_fail;
-      printf("FAIL %-58s launch %d: %zu of %zu elements differ\n", name, r, nd, y1.size());
-      return;
-    }
-  }
-  printf("ok   %-58s\n", name);
-}
-
-// the same linear layer (bias, optional residual / split-K / two-source contraction / zero rows) under two forced tile
-// codes: same bits, on every one of `reps` launches of the second code
-static void run_lin_same_case(int M, int N, int K, int tile_a, int tile_b, bool res, int k_split = 0, int zero_rows = 0, int reps = 8) {
-  auto A = rand_h((size_t)M * K), Wt = rand_h((size_t)N * K, 1.7f / sqrtf((float)K)), Bv = rand_h(N), R = rand_h((size_t)M * N);
-  const int K1 = k_split > 0 ? k_split : K, K2 = K - K1, Mz = M - zero_rows;
-  // operand rows below zero_rows are not stored; columns >= k_split live in a second buffer
-  std::vector<h16> A1((size_t)Mz * K1), A2((size_t)Mz * (K2 > 0 ? K2 : 1));
-  for (int m = 0; m < Mz; ++m) {
-    for (int k = 0; k < K1; ++k) A1[(size_t)m * K1 + k] = A[(size_t)(m + zero_rows) * K + k];
-    for (int k = 0; k < K2; ++k) A2[(size_t)m * K2 + k] = A[(size_t)(m + zero_rows) * K + K1 + k];
-  }
-  Dev<h16> dA(A1), dA2(A2), dW(Wt), dB(Bv), dR(R), dC1((size_t)M * N), dC2((size_t)M * N);
-  Dev<float> dWS((size_t)8 * M * N);
-  PfdGemmDesc d;
-  memset(&d, 0, sizeof(d));
-  d.M = M; d.N = N; d.K = K; d.A = dA.p; d.W = dW.p; d.bias = dB.p; d.R = res ? dR.p : nullptr;
-  d.lda = K1; d.ldw = K; d.ldc = N; d.ldr = N; d.ldrv = N; d.rows_per_rv = 1;
-  if (k_split > 0) { d.k_split = k_split; d.A2 = dA2.p; d.lda2 = K2; }
-  d.zero_rows = zero_rows;
-  d.ws = dWS.p; d.ws_bytes = (size_t)8 * M * N * sizeof(float);
-  char name[200];
-  snprintf(name, sizeof(name), "linear %dx%dx%d tile %d == tile %d (bitwise, %d launches)%s ks%d zr%d", M, N, K, tile_a, tile_b, reps,
-           res ? " +res" : "", k_split, zero_rows);
-  ++g_total;
-  d.C = dC1.p;
-  int rc = pfd_gemm_f16_ex(&d, tile_a, nullptr);
-  if (rc != 0) { ++g_fail; printf("FAIL %-58s rc=%d (%s)\n", name, rc, pfd_last_error()); return; }
-  auto y1 = dC1.get();
-  d.C = dC2.p;
-  for (int r = 0; r < reps; ++r) {
-    HIP_OK(hipMemset(dC2.p, 0xFF, (size_t)M * N * sizeof(h16)));
-    rc = pfd_gemm_f16_ex(&d, tile_b, nullptr);
-    if (rc != 0) { ++g_fail; printf("FAIL %-58s rc=%d (%s)\n", name, rc, pfd_last_error()); return; }
-    auto y2 = dC2.get();
-    if (memcmp(y1.data(), y2.data(), y1.size() * sizeof(h16))) {
-      size_t nd = 0;
-      for (size_t i = 0; i < y1.size(); ++i) nd += memcmp(&y1[i], &y2[i], sizeof(h16)) != 0;
-      ++g_fail;
-      printf("FAIL %-58s launch %d: %zu of %zu elements differ\n", name, r, nd, y1.size());
-      return;
-    }
-  }
-  printf("ok   %-58s\n", name);
-}
-
 // pfd_add_rowvec_lnstats_f16 == pfd_add_rowvec_f16 followed by pfd_ln_rowstats_f16, bit for bit (values and statistics)
 static void run_add_rowvec_lnstats_case(int R, int C) {
   auto X = rand_h((size_t)R * C, 3.0f), V = rand_h(C, 1.0f);
@@ -579,8 +403,8 @@ static void run_add_rowvec_lnstats_case(int R, int C) {
   if (rc == 0) rc = pfd_ln_rowstats_f16(dY2.p, C, R, C, s2.p, nullptr);
   char name[128];
   snprintf(name, sizeof(name), "add_rowvec + row statistics R%d C%d (bitwise vs two launches)", R, C);
+  if (rc != 0) return fail_rc(name, rc);
   ++g_total;
-  if (rc != 0) { ++g_fail; printf("FAIL %-58s rc=%d (%s)\n", name, rc, pfd_last_error()); return; }
   auto y1 = dY1.get(), y2 = dY2.get();
   auto a = s1.get(), b = s2.get();
   const bool same = !memcmp(y1.data(), y2.data(), y1.size() * sizeof(h16)) && !memcmp(a.data(), b.data(), a.size() * sizeof(float));
@@ -591,14 +415,14 @@ static void run_add_rowvec_lnstats_case(int R, int C) {
 static void run_ln_fold_suite() {
   run_add_rowvec_lnstats_case(130, 320);
   run_add_rowvec_lnstats_case(77, 1280);
-  run_ln_fold_case(300, 320, 960, 0, 0, 0, 640);            // fused q | k | v^T of a 320-wide block (transposed tail)
-  run_ln_fold_case(700, 320, 320, 0, 3400, 3400, 0);        // 128-row tiles, 4 waves
-  run_ln_fold_case(520, 640, 640, 0, 9200, 9200, 0);        // 128-row tiles, 8 waves
+  run_ln_fold_case(300, 320, 960, 0, 0, 0, 640);   // fused q | k | v^T of a 320-wide block (transposed tail)
+  run_ln_fold_case(700, 320, 320, 0, 3400, 3400, 0);   // 128-row tiles, 4 waves
+  run_ln_fold_case(520, 640, 640, 0, 9200, 9200, 0);   // 128-row tiles, 8 waves
   run_ln_fold_case(300, 640, 1280, PFD_ACT_GEGLU, 5400, 5400, 0);   // GEGLU, 256-row tiles
-  run_ln_fold_case(600, 320, 640, PFD_ACT_GEGLU, 3200, 9400, 0);    // 256 x 320 GEGLU tile; 64-row producer
-  run_ln_fold_case(130, 1280, 320, 0, 3204, 3204, 0);       // split-K on both sides (stats by the stand-alone kernel)
+  run_ln_fold_case(600, 320, 640, PFD_ACT_GEGLU, 3200, 9400, 0);   // 256 x 320 GEGLU tile; 64-row producer
+  run_ln_fold_case(130, 1280, 320, 0, 3204, 3204, 0);   // split-K on both sides (stats by the stand-alone kernel)
   run_ln_fold_case(200, 1280, 1280, PFD_ACT_GELU, 5300, 3300, 0);   // 8-wave 64-row ring producer, 4-wave ring consumer
-  run_ln_fold_case(77, 960, 160, 0, 9300, 3500, 0);         // ragged M, 6 partials
+  run_ln_fold_case(77, 960, 160, 0, 9300, 3500, 0);   // ragged M, 6 partials
 }
 
 // ------------------------------------------------------------------ attention
@@ -629,7 +453,7 @@ static void run_attn_case(int B, int H, int Nq, int Nk, int D, bool fused_layout
   const int rc = pfd_attention_f16(&d, nullptr);
   char name[128];
   snprintf(name, sizeof(name), "attention B%d H%d Nq%d Nk%d D%d fused%d spike%d", B, H, Nq, Nk, D, (int)fused_layout, spike);
-  if (rc != 0) { ++g_total; ++g_fail; printf("FAIL %-58s rc=%d (%s)\n", name, rc, pfd_last_error()); return; }
+  if (rc != 0) return fail_rc(name, rc);
   auto got = dO.get();
   std::vector<double> ref(got.size(), 0.0);
   const int koff = fused_layout ? C : 0;
@@ -669,7 +493,7 @@ static void run_swin_case(int B, int H, int W, int nH, int shift) {
   const int rc = pfd_swin_window_attention_f16(&d, nullptr);
   char name[128];
   snprintf(name, sizeof(name), "swin_attn B%d H%d W%d nH%d shift%d", B, H, W, nH, shift);
-  if (rc != 0) { ++g_total; ++g_fail; printf("FAIL %-58s rc=%d (%s)\n", name, rc, pfd_last_error()); return; }
+  if (rc != 0) return fail_rc(name, rc);
   auto got = dout.get();
   std::vector<double> ref(got.size(), 0.0);
   const int Hp = (H + ws - 1) / ws * ws, Wp = (W + ws - 1) / ws * ws;
@@ -739,7 +563,7 @@ static void run_gn_case(int B, int HW, int C1, int C2, int G, int act, float eps
                                    dws.p, wsb, nullptr);
   char name[128];
   snprintf(name, sizeof(name), "groupnorm B%d HW%d C%d+%d G%d act%d", B, HW, C1, C2, G, act);
-  if (rc != 0) { ++g_total; ++g_fail; printf("FAIL %-58s rc=%d (%s)\n", name, rc, pfd_last_error()); return; }
+  if (rc != 0) return fail_rc(name, rc);
   auto got = dy.get();
   std::vector<double> ref(got.size());
   const int cpg = C / G;
@@ -761,9 +585,6 @@ static void run_gn_case(int B, int HW, int C1, int C2, int G, int act, float eps
   report(name, got, ref, 4e-3, 3e-3);
 }
 
-// conv3x3(act(GroupNorm([x1 | x2]))) two ways: pfd_groupnorm_f16 + plain patch conv vs pfd_groupnorm_table_f16 + the
-// conv's GroupNorm prologue.  Same statistics code, same fp32 affine map, same kernel behind it: the outputs must be
-// identical, not merely close.
 // PfdGemmDesc.gnf_y (ABI 9): GroupNorm(32)(+SiLU) of a convolution's output inside its split-K reduction launch vs the two-call
 // form (the same convolution without the request, then pfd_groupnorm_f16 on its output): the same bits, raw and normalised
 static void run_gnf_case(int B, int H, int W, int Cin, int N, int act_gn, float eps, bool res, bool rowvec, bool keep_raw, int tile = 0) {
@@ -772,13 +593,11 @@ static void run_gnf_case(int B, int H, int W, int Cin, int N, int act_gn, float 
   auto rv = rand_h((size_t)B * N, 0.5f), R = rand_h((size_t)M * N, 1.0f), gm = rand_h(N, 1.f), bt = rand_h(N, 0.5f);
   Dev<h16> dA(A), dW(Wt), dB(bias), dRV(rv), dR(R), dG(gm), dBt(bt), dC((size_t)M * N), dC2((size_t)M * N), dY((size_t)M * N), dY2((size_t)M * N);
   Dev<float> dWS((size_t)8 * M * N + 64);
-  PfdGemmDesc d;
-  memset(&d, 0, sizeof(d));
+  PfdGemmDesc d = gemm_desc(dWS);
   d.A = dA.p; d.W = dW.p; d.bias = dB.p; d.rowvec = rowvec ? dRV.p : nullptr; d.R = res ? dR.p : nullptr; d.C = dC.p;
   d.lda = Cin; d.ldw = K; d.ldc = N; d.ldr = N; d.ldrv = N;
   d.M = M; d.N = N; d.K = K; d.rows_per_rv = HW; d.act = 0;
-  d.ksize = 3; d.stride = 1; d.pad = 1; d.B = B; d.H = H; d.Wd = W; d.Cin = Cin; d.Ho = H; d.Wo = W;
-  d.ws = dWS.p; d.ws_bytes = ((size_t)8 * M * N + 64) * sizeof(float);
+  conv3x3_geometry(d, B, H, W, Cin);
   char name[200];
   snprintf(name, sizeof(name), "conv3x3 B%d %dx%d %d->%d + fused GroupNorm act%d res%d rv%d raw%d tile%d", B, H, W, Cin, N, act_gn, res, rowvec, keep_raw, tile);
   HIP_OK(hipMemset(dC.p, 0x3C, (size_t)M * N * sizeof(h16)));     // 1.0 pattern: an unwritten raw tensor stays recognisable
@@ -786,8 +605,8 @@ static void run_gnf_case(int B, int H, int W, int Cin, int N, int act_gn, float 
   f.gnf_gamma = dG.p; f.gnf_beta = dBt.p; f.gnf_y = dY.p; f.gnf_ldy = N; f.gnf_eps = eps; f.gnf_act = act_gn; f.gnf_rows = HW;
   f.gnf_skip_raw = keep_raw ? 0 : 1;
   const int rc = tile ? pfd_gemm_f16_ex(&f, tile, nullptr) : pfd_gemm_f16(&f, nullptr);
+  if (rc != 0) return fail_rc(name, rc);
   ++g_total;
-  if (rc != 0) { ++g_fail; printf("FAIL %-58s rc=%d (%s)\n", name, rc, pfd_last_error()); return; }
   d.C = dC2.p;
   const size_t wsb = pfd_groupnorm_ws_bytes(B, N, HW);
   Dev<char> dws(wsb);
@@ -836,11 +655,9 @@ static void run_gnf_decline_case(int B, int H, int W, int Cin, int N) {
   Dev<float> dWS((size_t)8 * M * N + 64);
   HIP_OK(hipMemset(dC.p, 0x3C, (size_t)M * N * sizeof(h16)));
   HIP_OK(hipMemset(dY.p, 0x3C, (size_t)M * N * sizeof(h16)));
-  PfdGemmDesc d;
-  memset(&d, 0, sizeof(d));
+  PfdGemmDesc d = gemm_desc(dWS);
   d.A = dA.p; d.W = dW.p; d.bias = dB.p; d.C = dC.p; d.lda = Cin; d.ldw = K; d.ldc = N; d.M = M; d.N = N; d.K = K; d.rows_per_rv = HW;
-  d.ksize = 3; d.stride = 1; d.pad = 1; d.B = B; d.H = H; d.Wd = W; d.Cin = Cin; d.Ho = H; d.Wo = W;
-  d.ws = dWS.p; d.ws_bytes = ((size_t)8 * M * N + 64) * sizeof(float);
+  conv3x3_geometry(d, B, H, W, Cin);
   d.gnf_gamma = dG.p; d.gnf_beta = dBt.p; d.gnf_y = dY.p; d.gnf_ldy = N; d.gnf_eps = 1e-5f; d.gnf_act = PFD_ACT_SILU; d.gnf_rows = HW;
   const int rc = pfd_gemm_f16(&d, nullptr);
   HIP_OK(hipDeviceSynchronize());
@@ -881,7 +698,7 @@ static void run_gn_pstats_case(int B, int HW, int C1, int C2, int act, float eps
   if (!pfd_groupnorm_takes_pstats(B, C1, C2, HW, G)) { ++g_total; ++g_fail; printf("FAIL %s: shape refused\n", name); return; }
   const int rc = pfd_groupnorm_pstats_f16(d1.p, C1, C1, ds1.p, C2 ? d2.p : nullptr, C2, C2, C2 ? ds2.p : nullptr, dg.p, db.p, dy.p, C,
                                           B, HW, G, eps, act, nullptr);
-  if (rc != 0) { ++g_total; ++g_fail; printf("FAIL %s rc=%d (%s)\n", name, rc, pfd_last_error()); return; }
+  if (rc != 0) return fail_rc(name, rc);
   auto got = dy.get();
   std::vector<double> ref((size_t)B * HW * C);
   auto at = [&](int b, int r, int c) { return c < C1 ? (double)x1[((size_t)b * HW + r) * C1 + c] : (double)x2[((size_t)b * HW + r) * C2 + c - C1]; };
@@ -898,6 +715,9 @@ static void run_gn_pstats_case(int B, int HW, int C1, int C2, int act, float eps
   report(name, got, ref, 6e-3, 4e-3);
 }
 
+// conv3x3(act(GroupNorm([x1 | x2]))) two ways: pfd_groupnorm_f16 + plain patch conv vs pfd_groupnorm_table_f16 + the
+// conv's GroupNorm prologue.  Same statistics code, same fp32 affine map, same kernel behind it: the outputs must be
+// identical, not merely close.
 static void run_gn_conv_case(int B, int H, int W, int C1, int C2, int N, int act, bool with_res) {
   const int C = C1 + C2, HW = H * W, G = 32, M = B * HW, K = 9 * C;
   const float eps = 1e-5f;
@@ -916,13 +736,11 @@ static void run_gn_conv_case(int B, int H, int W, int C1, int C2, int N, int act
   snprintf(name, sizeof(name), "gn-prologue conv B%d %dx%d C%d+%d N%d act%d res%d", B, H, W, C1, C2, N, act, (int)with_res);
   int rc = pfd_groupnorm_f16(d1.p, C1, C1, C2 ? d2.p : nullptr, C2, C2, dg.p, db.p, dy.p, C, B, HW, G, eps, act, dws.p,
                              wsb, nullptr);
-  PfdGemmDesc d;
-  memset(&d, 0, sizeof(d));
-  d.ws = dWS.p; d.ws_bytes = ((size_t)8 * M * N + 64) * sizeof(float);
+  PfdGemmDesc d = gemm_desc(dWS);
   d.A = dy.p; d.W = dW.p; d.bias = dB.p; d.rowvec = dRV.p; d.R = with_res ? dR.p : nullptr; d.C = dC0.p;
   d.lda = C; d.ldw = K; d.ldr = N; d.ldc = N; d.ldrv = N;
   d.M = M; d.N = N; d.K = K; d.rows_per_rv = HW;
-  d.ksize = 3; d.stride = 1; d.pad = 1; d.B = B; d.H = H; d.Wd = W; d.Cin = C; d.Ho = H; d.Wo = W;
+  conv3x3_geometry(d, B, H, W, C);
   if (rc == 0) rc = pfd_gemm_f16_ex(&d, 10800, nullptr);
   if (rc == 0)
     rc = pfd_groupnorm_table_f16(d1.p, C1, C1, C2 ? d2.p : nullptr, C2, C2, dg.p, db.p, dT.p, B, HW, G, eps, dws.p, wsb,
@@ -930,8 +748,8 @@ static void run_gn_conv_case(int B, int H, int W, int C1, int C2, int N, int act
   d.A = d1.p; d.lda = C1; d.A2 = C2 ? d2.p : nullptr; d.lda2 = C2; d.gn_c1 = C1; d.gn_table = dT.p; d.gn_act = act;
   d.C = dC1.p;
   if (rc == 0) rc = pfd_gemm_f16(&d, nullptr);
+  if (rc != 0) return fail_rc(name, rc);
   ++g_total;
-  if (rc != 0) { ++g_fail; printf("FAIL %-58s rc=%d (%s)\n", name, rc, pfd_last_error()); return; }
   auto c0 = dC0.get(), c1 = dC1.get();
   size_t bad = 0;
   double worst = 0, mag = 0;
@@ -958,7 +776,7 @@ static void run_ln_case(int M, int C, int gather4, int B, int H, int W) {
   const int rc = pfd_layernorm_f16(dx.p, gather4 ? Cq : C, dg.p, db.p, dy.p, C, M, C, 1e-5f, gather4, B, H, W, nullptr);
   char name[128];
   snprintf(name, sizeof(name), "layernorm M%d C%d gather%d", M, C, gather4);
-  if (rc != 0) { ++g_total; ++g_fail; printf("FAIL %-58s rc=%d (%s)\n", name, rc, pfd_last_error()); return; }
+  if (rc != 0) return fail_rc(name, rc);
   auto got = dy.get();
   std::vector<double> ref(got.size());
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
@@ -987,7 +805,7 @@ static void run_softmax_case(int R, int N, float scale) {
   const int rc = pfd_softmax_rows_f16(dx.p, N, dy.p, N, R, N, scale, nullptr);
   char name[128];
   snprintf(name, sizeof(name), "softmax_rows R%d N%d", R, N);
-  if (rc != 0) { ++g_total; ++g_fail; printf("FAIL %-58s rc=%d\n", name, rc); return; }
+  if (rc != 0) return fail_rc(name, rc);
   auto got = dy.get();
   std::vector<double> ref(got.size());
   for (int r = 0; r < R; ++r) {
@@ -1261,918 +1079,322 @@ static void run_image_case(int B, int H, int W, int C, int Ho, int Wo) {
 }
 
 static void run_image() {
-  run_image_case(2, 37, 53, 3, 64, 96);     // enlarging: 4 taps, odd row pitch (byte heads and tails), 4-pixel vertical form
+  run_image_case(2, 37, 53, 3, 64, 96);   // enlarging: 4 taps, odd row pitch (byte heads and tails), 4-pixel vertical form
   run_image_case(1, 200, 333, 3, 50, 70);   // shrinking by 4 and 4.8, 1-pixel vertical form (70 % 4 != 0)
   run_image_case(1, 300, 300, 1, 20, 20);   // one channel, ratio 15
   const int rc = pfd_image_resample_check(1, 1025, 64, 64, 64, 3);
   report_bytes("image resample bounds: ratio above 16 is PFD_ESHAPE rc=" + std::to_string(rc), rc != PFD_ESHAPE, 1);
 }
 
-// ------------------------------------------------------------------ bench
-static float time_ms(const std::function<void()>& f, int iters) {
-  hipEvent_t a, b;
-  HIP_OK(hipEventCreate(&a)); HIP_OK(hipEventCreate(&b));
-  for (int i = 0; i < 3; ++i) f();
-  HIP_OK(hipEventRecord(a, 0));
-  for (int i = 0; i < iters; ++i) f();
-  HIP_OK(hipEventRecord(b, 0));
-  HIP_OK(hipEventSynchronize(b));
-  float ms = 0;
-  HIP_OK(hipEventElapsedTime(&ms, a, b));
-  return ms / iters;
+// ------------------------------------------------------------------ the case lists of the modes
+// the d = 40 ... 160 attention cases that the default run and --attn share
+static void run_attn_shared_cases() {
+  run_attn_case(2, 2, 128, 128, 40, true);
+  run_attn_case(1, 2, 300, 148, 40, false);   // ragged queries and keys (2 full tiles + 20 keys)
+  run_attn_case(2, 2, 512, 256, 40, true);   // full tiles only
+  run_attn_case(1, 1, 256, 40, 40, false);   // a single ragged tile
+  run_attn_case(1, 2, 520, 1000, 40, false);   // 15 full tiles + 40 keys
+  run_attn_case(1, 2, 77, 64, 40, true);   // exactly one full tile
+  run_attn_case(1, 2, 200, 148, 40, false);
+  run_attn_case(2, 2, 64, 64, 80, true);
+  run_attn_case(1, 2, 144, 256, 96, false);
+  run_attn_case(1, 3, 148, 148, 96, false);
+  run_attn_case(2, 2, 64, 148, 160, false);
+  run_attn_case(1, 1, 256, 320, 160, true);
 }
 
-static void bench_gemm(const char* label, int M, int N, int K, int ksize, int B, int H, int Cin, int tile) {
-  const bool conv = ksize > 0;
-  if (conv) { M = B * H * H; K = ksize * ksize * Cin; }
-  auto A = rand_h(conv ? (size_t)B * H * H * Cin : (size_t)M * K), W = rand_h((size_t)N * K, 0.05f), bias = rand_h(N);
-  Dev<h16> dA(A), dW(W), dB(bias), dC((size_t)M * N);
-  Dev<float> dWS((size_t)16 << 20);
-  PfdGemmDesc d;
-  memset(&d, 0, sizeof(d));
-  d.ws = dWS.p; d.ws_bytes = (size_t)64 << 20;
-  d.A = dA.p; d.W = dW.p; d.bias = dB.p; d.C = dC.p;
-  d.lda = conv ? Cin : K; d.ldw = K; d.ldc = N; d.M = M; d.N = N; d.K = K; d.rows_per_rv = 1;
-  d.ksize = ksize; d.stride = 1; d.pad = ksize / 2; d.B = B; d.H = H; d.Wd = H; d.Cin = Cin; d.Ho = H; d.Wo = H;
-  int rc = 0;
-  const float ms = time_ms([&] { rc |= pfd_gemm_f16_ex(&d, tile, nullptr); }, 20);
-  const double tf = 2.0 * M * N * K / (ms * 1e-3) / 1e12;
-  printf("bench %-34s M%-6d N%-5d K%-6d tile%-2d rc=%d %8.3f ms %8.1f TFLOP/s\n", label, M, N, K, tile, rc, ms, tf);
-  fflush(stdout);
+static void run_default_cases() {
+  const int tiles[] = {22, 21, 12, 11};
+  for (int t : tiles) {
+    run_gemm_case(lin(256, 256, 128).tile(t));
+    run_gemm_case(lin(301, 203 - 3, 192).act(PFD_ACT_GELU).res().rowvec().tile(t));
+    run_gemm_case(lin(77, 72, 64).act(PFD_ACT_SILU).res().bias_row().tile(t).ld(+8));
+  }
+  run_gemm_case(lin(130, 4, 128).res());   // N = 4 (UNet head)
+  run_gemm_case(lin(64, 37, 64).act(PFD_ACT_RELU).no_bias());   // odd N -> scalar stores
+  run_gemm_case(lin(200, 256, 128).act(PFD_ACT_GEGLU).res());
+  run_gemm_case(lin(512, 1280, 320).rowvec());
+  for (int t : tiles) run_gemm_case(conv(2, 9, 7, 64, 96).res().rowvec().tile(t));
+  run_gemm_case(conv(2, 10, 8, 64, 128).stride(2).act(PFD_ACT_SILU));   // stride 2
+  run_gemm_case(conv(1, 5, 6, 128, 64).ups(1).res());   // upsample
+  run_gemm_case(conv(1, 9, 9, 64, 64).stride(2).pad(0).ld(+8));   // pad 0, stride 2, ld+8
+  run_gemm_case(conv(2, 6, 6, 128, 80).k(1).pad(0));   // 1x1 as conv
+
+  // wide-tile LDS-DMA kernel (N % 160 == 0): variants 256x160 / 128x160 / 64x160, split-K, conv gather
+  for (int v : {0, 5400, 3400, 3200}) {
+    run_gemm_case(lin(300, 320, 192).act(PFD_ACT_SILU).res().rowvec().tile(v));
+    run_gemm_case(lin(77, 160, 64).tile(v).ld(+8));
+    run_gemm_case(conv(2, 9, 7, 64, 320).res().rowvec().tile(v));
+  }
+  // patch conv kernel: W in {16,32,64}, whole image rows per tile, halo zero padding, split over channel blocks
+  run_gemm_case(conv(2, 16, 16, 64, 160).act(PFD_ACT_SILU).res().rowvec().tile(10900));
+  run_gemm_case(conv(1, 32, 32, 128, 320).res().tile(10900));
+  run_gemm_case(conv(1, 64, 64, 128, 160).rowvec().tile(10902));
+  run_gemm_case(conv(3, 16, 16, 192, 320));
+  run_gemm_case(lin(520, 160, 1024).act(PFD_ACT_GELU).res().rowvec().tile(3204));   // 64x160 tiles, split-K 4
+  run_gemm_case(lin(130, 320, 2048).res().tile(5403));   // 256x160, split-K 3
+  run_gemm_case(lin(200, 320, 128).act(PFD_ACT_GEGLU));   // GEGLU, 40-row packing
+  // 128-wide tiles of the wide kernel (N % 128 == 0, N % 160 != 0: VAE / Swin / SeeCoder widths)
+  run_gemm_case(lin(300, 256, 192).act(PFD_ACT_SILU).res().rowvec().tile(5400));
+  run_gemm_case(lin(77, 128, 64).tile(3400).ld(+8));
+  run_gemm_case(lin(130, 384, 320).act(PFD_ACT_GELU).res().tile(3200));
+  run_gemm_case(lin(520, 256, 2048).res().tile(3404));
+  run_gemm_case(conv(2, 9, 7, 128, 256).act(PFD_ACT_SILU).res().rowvec());
+  run_gemm_case(conv(1, 5, 6, 128, 128).ups(1).tile(5400));   // upsample
+  run_gemm_case(conv(1, 9, 9, 64, 512).stride(2).pad(0));   // stride 2, pad 0
+  run_gemm_case(lin(200, 384, 128).n_split(256));
+  // transposed tail (fused q|k|v projection): all three tile heights, ragged M, bias
+  run_gemm_case(lin(520, 480, 128).no_bias().n_split(320));
+  run_gemm_case(lin(301, 320, 192).tile(5400).n_split(160));
+  run_gemm_case(lin(77, 960, 320).no_bias().tile(3400).n_split(640));
+  run_gemm_case(lin(130, 480, 64).tile(3200).n_split(320));
+  // deep operand rings (counted vmcnt + raw barrier): K shorter than, equal to and longer than the ring, split-K, conv
+  run_gemm_case(lin(130, 320, 128).res().tile(3300));
+  run_gemm_case(lin(300, 160, 256).act(PFD_ACT_GELU).res().rowvec().tile(3500));
+  run_gemm_case(lin(300, 320, 1024).res().rowvec().tile(3300));
+  run_gemm_case(lin(77, 160, 1344).tile(3500));
+  run_gemm_case(lin(520, 320, 2048).res().tile(3304));
+  run_gemm_case(lin(130, 160, 1536).tile(3503));
+  run_gemm_case(conv(2, 8, 8, 256, 320).res().tile(3302));
+  run_gemm_case(conv(2, 10, 8, 128, 160).stride(2).act(PFD_ACT_SILU).rowvec().tile(3500));
+  // wave-specialised forms: 256-row tile with loader waves (48), patch kernel with loader waves (98) / without (99)
+  run_gemm_case(lin(300, 320, 1024).res().rowvec().tile(5800));
+  run_gemm_case(conv(2, 8, 8, 256, 320).res().tile(5800));
+  run_gemm_case(conv(2, 10, 8, 128, 160).stride(2).act(PFD_ACT_SILU).rowvec().tile(5800));
+  run_gemm_case(conv(1, 32, 32, 128, 320).res().tile(10800));
+  run_gemm_case(conv(1, 64, 64, 128, 160).rowvec().tile(10802));
+  // round 3: rotated K walk (several M tiles, K tiles >= M tiles and < M tiles, split-K, conv wrap-around) and the
+  // loader-wave kernels (5800 / 5700 = 256-row tile, 10800 / 10600 = patch kernel with two / three weight stages)
+  for (int v : {5800, 5700}) {   // 58 = two operand stages, 57 = the 3-stage ring (the default)
+    run_gemm_case(lin(1100, 320, 1024).res().rowvec().tile(v));
+    run_gemm_case(lin(700, 640, 192).act(PFD_ACT_GELU).rowvec().tile(v));
+    run_gemm_case(lin(600, 320, 2048).res().tile(v + 2));   // split-K 2
+    run_gemm_case(conv(3, 16, 16, 128, 320).res().tile(v));   // conv, 3 M tiles
+    run_gemm_case(conv(5, 20, 16, 64, 160).stride(2).act(PFD_ACT_SILU).rowvec().tile(v));   // stride 2
+    run_gemm_case(conv(2, 9, 12, 64, 160).ups(1).tile(v));   // upsample
+    run_gemm_case(lin(600, 256, 512).res().tile(v));   // 128-wide tiles
+  }
+  for (int v : {10800, 10600}) {
+    run_gemm_case(conv(2, 32, 32, 128, 320).res().rowvec().tile(v));
+    run_gemm_case(conv(1, 64, 64, 256, 160).act(PFD_ACT_SILU).rowvec().tile(v));
+    run_gemm_case(conv(3, 16, 16, 320, 320).res().tile(v));
+    run_gemm_case(conv(2, 16, 16, 512, 160).tile(v + 2));   // split over cb
+  }
+  run_gemm_case(lin(600, 640, 320).act(PFD_ACT_GEGLU).tile(9400));   // 256 x 320 GEGLU tile
+  run_gemm_case(lin(300, 320, 64).act(PFD_ACT_GEGLU).no_bias().tile(9400));
+  for (int v : {3200, 3300, 3400, 3500, 5400, 5100, 5300, 9200, 9300}) {   // rotated walk over several M tiles; 8-wave small tiles
+    run_gemm_case(lin(1100, 320, 1024).res().rowvec().tile(v));
+    run_gemm_case(conv(3, 16, 16, 128, 160).res().tile(v));
+    run_gemm_case(lin(900, 320, 1536).tile(v + 3));
+  }
+  // GroupNorm(+SiLU) prologue of the patch kernel == pfd_groupnorm_f16 followed by the plain convolution, bit for bit
+  run_gn_conv_case(2, 16, 16, 64, 0, 160, PFD_ACT_SILU, false);
+  run_gn_conv_case(1, 32, 32, 128, 64, 320, PFD_ACT_SILU, true);
+  run_gn_conv_case(2, 64, 64, 64, 128, 160, PFD_ACT_NONE, true);
+  run_gn_conv_case(3, 32, 32, 320, 0, 320, PFD_ACT_SILU, true);
+  run_gemm_case(conv(2, 10, 8, 128, 160).stride(2).act(PFD_ACT_SILU));   // stride 2
+  run_gemm_case(conv(1, 5, 6, 128, 160).ups(1).res().tile(3402));   // upsample + split
+  run_gemm_case(conv(1, 9, 9, 64, 320).stride(2).pad(0).ld(+8));   // pad 0, ld+8
+  run_gemm_case(conv(2, 6, 6, 128, 160).k(1).pad(0));   // 1x1 as conv
+  run_ups_fold_cases();
+  run_narrow_conv_cases();
+
+  run_gemm_case(conv(1, 16, 48, 128, 160).act(PFD_ACT_SILU).res().rowvec());   // patch kernel, 2-D tiles
+  run_gemm_case(conv(2, 8, 96, 64, 320).res().rowvec());
+  run_ln_fold_suite();
+  run_attn_shared_cases();
+  run_attn_case(2, 1, 256, 256, 512, false);   // VAE mid-block attention (attention512_kernel)
+  run_attn_case(1, 1, 200, 96, 512, false);
+
+  run_swin_case(1, 14, 17, 2, 0);
+  run_swin_case(1, 14, 17, 2, 6);
+  run_swin_case(2, 24, 24, 1, 6);
+  run_swin_case(1, 8, 8, 3, 6);
+
+  run_gn_case(2, 64, 320, 0, 32, PFD_ACT_SILU, 1e-5f);
+  run_gn_case(2, 100, 64, 32, 32, PFD_ACT_NONE, 1e-6f);   // groups straddle the concat seam
+  run_gn_case(1, 50, 1280, 1280, 32, PFD_ACT_SILU, 1e-5f);   // two vec slots per thread
+  run_gn_case(2, 1024, 128, 0, 32, PFD_ACT_SILU, 1e-6f);
+  run_gn_case(1, 16, 1920, 0, 32, PFD_ACT_SILU, 1e-5f);
+  // single-launch small-slab form ((C/G) % 4 == 0, slab <= 32 K elements, >= 128 blocks)
+  run_gn_case(4, 64, 1280, 0, 32, PFD_ACT_SILU, 1e-5f);
+  run_gn_case(4, 256, 1280, 1280, 32, PFD_ACT_SILU, 1e-5f);
+  run_gn_case(8, 128, 1024, 0, 32, PFD_ACT_NONE, 1e-6f);
+  run_gn_case(4, 100, 1280, 640, 32, PFD_ACT_SILU, 1e-5f);   // cpg 60: groups straddle the seam
+
+  run_ln_case(37, 320, 0, 0, 0, 0);
+  run_ln_case(10, 1280, 0, 0, 0, 0);
+  run_ln_case(5, 3072, 0, 0, 0, 0);
+  run_ln_case(2 * 4 * 3, 4 * 96, 1, 2, 7, 5);
+  run_ln_case(8195, 320, 0, 0, 0, 0);   // multi-row form (M >= 8192), ragged last wave
+  run_ln_case(8192, 640, 0, 0, 0, 0);
+  run_ln_case(8193, 1280, 0, 0, 0, 0);
+  run_softmax_case(5, 4096, 0.044f);
+  run_softmax_case(3, 1152, 0.1f);
+  run_softmax_case(2, 36864, 0.044f);   // long-row form (N > 16384)
+  run_softmax_case(2, 16392, 0.05f);
+  run_elementwise();
+  run_image();
 }
 
-static void bench_gn_conv(const char* label, int B, int H, int C1, int C2, int N) {
-  const int C = C1 + C2, HW = H * H, M = B * HW, K = 9 * C, G = 32;
-  auto x1 = rand_h((size_t)M * C1), x2 = rand_h((size_t)M * std::max(C2, 8)), gm = rand_h(C), bt = rand_h(C);
-  auto Wt = rand_h((size_t)N * K, 0.05f), bias = rand_h(N);
-  Dev<h16> d1(x1), d2(x2), dg(gm), db(bt), dy((size_t)M * C), dW(Wt), dB(bias), dC((size_t)M * N);
-  Dev<float> dT((size_t)B * C * 2);
-  const size_t wsb = pfd_groupnorm_ws_bytes(B, C, HW);
-  Dev<char> dws(wsb);
-  PfdGemmDesc d;
-  memset(&d, 0, sizeof(d));
-  d.W = dW.p; d.bias = dB.p; d.C = dC.p; d.ldw = K; d.ldc = N; d.M = M; d.N = N; d.K = K; d.rows_per_rv = 1;
-  d.ksize = 3; d.stride = 1; d.pad = 1; d.B = B; d.H = H; d.Wd = H; d.Cin = C; d.Ho = H; d.Wo = H;
-  int rc = 0;
-  d.A = dy.p; d.lda = C;
-  const float gn = time_ms([&] {
-    rc |= pfd_groupnorm_f16(d1.p, C1, C1, C2 ? d2.p : nullptr, C2, C2, dg.p, db.p, dy.p, C, B, HW, G, 1e-5f, PFD_ACT_SILU,
-                            dws.p, wsb, nullptr); }, 20);
-  const float conv = time_ms([&] { rc |= pfd_gemm_f16(&d, nullptr); }, 20);
-  const float two = time_ms([&] {
-    rc |= pfd_groupnorm_f16(d1.p, C1, C1, C2 ? d2.p : nullptr, C2, C2, dg.p, db.p, dy.p, C, B, HW, G, 1e-5f, PFD_ACT_SILU,
-                            dws.p, wsb, nullptr);
-    rc |= pfd_gemm_f16(&d, nullptr); }, 20);
-  d.A = d1.p; d.lda = C1; d.A2 = C2 ? d2.p : nullptr; d.lda2 = C2; d.gn_c1 = C1; d.gn_table = dT.p; d.gn_act = PFD_ACT_SILU;
-  const float tab = time_ms([&] {
-    rc |= pfd_groupnorm_table_f16(d1.p, C1, C1, C2 ? d2.p : nullptr, C2, C2, dg.p, db.p, dT.p, B, HW, G, 1e-5f, dws.p, wsb,
-                                  nullptr); }, 20);
-  const float pconv = time_ms([&] { rc |= pfd_gemm_f16(&d, nullptr); }, 20);
-  const float fused = time_ms([&] {
-    rc |= pfd_groupnorm_table_f16(d1.p, C1, C1, C2 ? d2.p : nullptr, C2, C2, dg.p, db.p, dT.p, B, HW, G, 1e-5f, dws.p, wsb,
-                                  nullptr);
-    rc |= pfd_gemm_f16(&d, nullptr); }, 20);
-  printf("bench gn+conv %-30s rc=%d  groupnorm %.1f + conv %.1f = %.1f us | table %.1f + prologue conv %.1f = %.1f us\n",
-         label, rc, gn * 1e3, conv * 1e3, two * 1e3, tab * 1e3, pconv * 1e3, fused * 1e3);
+// the wide-tile variants with 8 waves on small tiles and 3-stage rings (5100 / 5300 / 9200 / 9300), the GEGLU tile, then the tiled-weight list
+static void run_tile_variant_cases() {
+  for (int v : {5100, 5300, 9200, 9300}) {
+    run_gemm_case(lin(1100, 320, 1024).res().rowvec().tile(v));
+    run_gemm_case(lin(300, 320, 192).act(PFD_ACT_SILU).res().rowvec().tile(v));
+    run_gemm_case(lin(77, 160, 64).tile(v).ld(+8));
+    run_gemm_case(conv(3, 16, 16, 128, 160).res().tile(v));
+    run_gemm_case(lin(900, 320, 1536).tile(v + 3));
+    run_gemm_case(lin(200, 320, 128).act(PFD_ACT_GEGLU).tile(v));
+  }
+  run_gemm_case(lin(520, 480, 128).no_bias().tile(5100).n_split(320));
+  run_gemm_case(lin(520, 480, 128).no_bias().tile(9200).n_split(320));
+  run_gemm_case(lin(600, 640, 320).act(PFD_ACT_GEGLU).tile(9400));
+  run_gemm_case(lin(300, 320, 64).act(PFD_ACT_GEGLU).no_bias().tile(9400));
+  run_tiled_weight_cases();
 }
 
-static void bench_attn(const char* label, int B, int H, int Nq, int Nk, int D) {
-  const int C = H * D, Nkp = (Nk + 7) / 8 * 8;
-  auto Q = rand_h((size_t)B * Nq * C), K = rand_h((size_t)B * Nk * C), Vt = rand_h((size_t)C * B * Nkp);
-  Dev<h16> dQ(Q), dK(K), dV(Vt), dO((size_t)B * Nq * C);
-  PfdAttnDesc d;
-  memset(&d, 0, sizeof(d));
-  d.Q = dQ.p; d.K = dK.p; d.Vt = dV.p; d.O = dO.p;
-  d.ldq = C; d.ldk = C; d.ldvt = (long)B * Nkp; d.ldo = C;
-  d.q_bs = (long)Nq * C; d.k_bs = (long)Nk * C; d.vt_bs = Nkp; d.o_bs = (long)Nq * C;
-  d.B = B; d.H = H; d.Nq = Nq; d.Nk = Nk; d.D = D; d.scale = 1.f / sqrtf((float)D);
-  int rc = 0;
-  const float ms = time_ms([&] { rc |= pfd_attention_f16(&d, nullptr); }, 20);
-  const double tf = 4.0 * B * H * (double)Nq * Nk * D / (ms * 1e-3) / 1e12;
-  printf("bench %-34s B%d H%d Nq%d Nk%d D%d rc=%d %8.3f ms %8.1f TFLOP/s\n", label, B, H, Nq, Nk, D, rc, ms, tf);
-  fflush(stdout);
+// fused GroupNorm in the split-K reduction (PfdGemmDesc.gnf_y), res_rows, and GroupNorm from producer statistics
+static void run_gn_fusion_cases() {
+  // adopted: the split-K reduction that also normalises (PfdGemmDesc.gnf_y) at the shapes the UNet / ControlNet give it
+  run_gnf_case(8, 16, 16, 1280, 1280, PFD_ACT_SILU, 1e-5f, false, true, false);   // ResBlock conv1 @16^2 (patch kernel, split 4)
+  run_gnf_case(8, 8, 8, 1280, 1280, PFD_ACT_SILU, 1e-5f, false, true, false);   // @8^2 (ring kernel, split 4)
+  run_gnf_case(8, 8, 8, 2560, 1280, PFD_ACT_SILU, 1e-5f, false, true, false);   // over the skip concat width, split 8
+  run_gnf_case(8, 16, 16, 640, 1280, PFD_ACT_SILU, 1e-5f, false, true, false);   // 640 -> 1280
+  run_gnf_case(8, 16, 16, 1280, 1280, PFD_ACT_NONE, 1e-6f, true, false, true);   // + residual, raw kept, no activation
+  run_gnf_case(4, 8, 8, 1280, 1280, PFD_ACT_SILU, 1e-5f, true, true, true);   // UNet batch 4
+  run_gnf_case(8, 16, 16, 1280, 1280, PFD_ACT_SILU, 1e-5f, false, true, false, 10802);   // forced patch kernel, split 2
+  run_gnf_case(8, 8, 8, 1280, 1280, PFD_ACT_SILU, 1e-5f, false, true, false, 3308);   // forced 4-stage ring, split 8
+  run_gnf_decline_case(8, 64, 64, 320, 320);   // 64^2: not split, cpg 10
+  // round 6: the 640-channel norms of the 32^2 level (20 channels per group, 1024 x 5 chunks per slab)
+  run_gnf_case(8, 32, 32, 640, 640, PFD_ACT_SILU, 1e-5f, false, true, false);   // ResBlock conv1 @32^2 (patch kernel, split 2)
+  run_gnf_case(8, 32, 32, 640, 640, PFD_ACT_SILU, 1e-5f, true, false, true);   // conv2: + residual, raw kept for the skip
+  run_gnf_case(8, 32, 32, 1280, 640, PFD_ACT_SILU, 1e-5f, false, true, false);   // over a skip concat width
+  run_gnf_case(4, 32, 32, 320, 640, PFD_ACT_SILU, 1e-5f, false, true, false);   // first ResBlock of the level, UNet batch 4
+  // residual stored once for a doubled batch (PfdGemmDesc.res_rows): every store pass and both plain reductions
+  for (int v : {0, 9200, 9300, 3200, 3300, 5400, 5800}) {
+    run_gemm_case(lin(1024, 320, 256).res().rowvec().tile(v).res_rows(512));   // plain store pass
+    if (v != 5800) run_gemm_case(lin(1024, 320, 256).res().tile(v).res_rows(512).zero_rows(512));   // + zero rows: the cross-attention re-join (not on the loader-wave kernel)
+    run_gemm_case(lin(1024, 320, 320).res().tile(v).res_rows(512).gn_out());   // statistics-emitting store pass: proj_out
+  }
+  run_gemm_case(lin(1024, 320, 2048).res().tile(3304).res_rows(512));   // split-K 4: plain reduction
+  run_gemm_case(lin(1024, 320, 2048).res().tile(3304).res_rows(512).gn_out());   // ... statistics-emitting reduction
+  // the statistics-emitting split-K reduction and the GroupNorm apply from producer statistics
+  run_gemm_case(lin(512, 1280, 2048).res().rowvec().tile(3304).gn_out());   // split-K 4, cpg 40
+  run_gemm_case(conv(2, 16, 16, 128, 320).res().rowvec().tile(9302).gn_out());   // conv, split-K 2
+  run_gn_case(8, 64, 1280, 0, 32, PFD_ACT_SILU, 1e-5f);
+  run_gn_case(8, 256, 1280, 1280, 32, PFD_ACT_SILU, 1e-5f);
+  run_gn_pstats_case(8, 4096, 320, 0, PFD_ACT_SILU, 1e-5f);
+  run_gn_pstats_case(8, 4096, 320, 320, PFD_ACT_SILU, 1e-5f);
+  run_gn_pstats_case(3, 1024, 640, 0, PFD_ACT_NONE, 1e-6f);
+  run_gn_pstats_case(2, 256, 1280, 1280, PFD_ACT_SILU, 1e-5f);
 }
 
-static void bench_gn(const char* label, int B, int HW, int C) {
-  auto x = rand_h((size_t)B * HW * C), g = rand_h(C), bt = rand_h(C);
-  Dev<h16> dx(x), dg(g), db(bt), dy((size_t)B * HW * C);
-  const size_t wsb = pfd_groupnorm_ws_bytes(B, C, HW);
-  Dev<char> dws(wsb);
-  int rc = 0;
-  const float ms = time_ms([&] { rc |= pfd_groupnorm_f16(dx.p, C, C, nullptr, 0, 0, dg.p, db.p, dy.p, C, B, HW, 32, 1e-5f, PFD_ACT_SILU, dws.p, wsb, nullptr); }, 20);
-  const double gbs = 6.0 * B * HW * C / (ms * 1e-3) / 1e9;
-  printf("bench %-34s B%d HW%d C%d rc=%d %8.3f ms %8.1f GB/s (6 B/elem)\n", label, B, HW, C, rc, ms, gbs);
-  fflush(stdout);
+static void run_patch_wide_cases() {
+  for (int v : {0, 10800, 10900}) {
+    run_gemm_case(conv(1, 16, 48, 128, 160).act(PFD_ACT_SILU).res().rowvec().tile(v));   // 16 x 16 tiles
+    run_gemm_case(conv(2, 8, 96, 64, 320).res().rowvec().tile(v));   // 8 x 32 tiles
+    run_gemm_case(conv(1, 32, 96, 128, 160).rowvec().tile(v));   // 4 x 3 tiles
+    run_gemm_case(conv(3, 32, 48, 64, 160).res().tile(v));   // several samples
+  }
+  run_gemm_case(conv(1, 16, 96, 256, 160).res().rowvec().tile(10802));   // split over channel blocks
+  run_gemm_case(conv(2, 16, 96, 128, 320).res().rowvec().w_tiled());
+  run_gemm_case(conv(1, 16, 48, 128, 160).res().tile(5400));   // same shape, implicit GEMM
 }
 
-static void bench_ln(const char* label, int M, int C) {
-  auto x = rand_h((size_t)M * C), g = rand_h(C), b = rand_h(C);
-  Dev<h16> dx(x), dg(g), db(b), dy((size_t)M * C);
-  int rc = 0;
-  const float ms = time_ms([&] { rc |= pfd_layernorm_f16(dx.p, C, dg.p, db.p, dy.p, C, M, C, 1e-5f, 0, 0, 0, 0, nullptr); }, 20);
-  printf("bench %-34s M%d C%d rc=%d %8.3f ms %8.1f GB/s (4 B/elem)\n", label, M, C, rc, ms, 4.0 * M * C / (ms * 1e-3) / 1e9);
-  fflush(stdout);
+static void run_attn_cases() {
+  run_attn_shared_cases();
+  run_attn_case(1, 2, 520, 1000, 40, false, 700);   // maximum jumps at key 700 (tile 10 of 16)
+  run_attn_case(2, 2, 512, 256, 40, true, 130);
+  run_attn_case(1, 2, 300, 148, 40, false, 140);   // ... inside the ragged tile
+  run_attn_case(1, 2, 512, 1024, 40, true, 700);   // round 6: whole 64-key tiles (attention3_kernel when PFD_ATTN3_FORCE=1 or the grid is big)
+  run_attn_case(1, 1, 700, 640, 40, false, 333);   // ragged last query block
+  run_attn_case(8, 8, 1024, 1024, 40, true, 500);   // 256 blocks: attention3_kernel by the dispatcher's own rule
 }
 
-// ------------------------------------------------------------------------------------------------
-// --winograd: Winograd F(2x2, 3x3) PROTOTYPE (selftest only; nothing here is linked into libpfd_hip.so).
-// the one exact-in-real-arithmetic lever on the 3x3 convolutions (2.25x fewer MACs).  Built the
-// way a product version would have to start: input transform V = B^T d B (4x4 tiles with stride 2, zero padding; one
-// pass, fp32 math, fp16 out), 16 GEMMs M_k = V_k U_k^T on the library's own wide-tile kernels (U = G g G^T transformed in
-// fp64 on the host and rounded to fp16), inverse transform Y = A^T M A (+ bias) -- measured against the patch kernel on
-// the same operands, with the error of both against an fp64 direct convolution at a shape the CPU can check.
-// ------------------------------------------------------------------------------------------------
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
+static void run_attn512_cases() {
+  run_attn_case(2, 1, 256, 256, 512, false);
+  run_attn_case(1, 1, 200, 96, 512, false);   // ragged query tile, 3 key tiles
+  run_attn_case(1, 1, 128, 32, 512, false);   // a single key tile
+  run_attn_case(2, 1, 128, 512, 512, true);   // Q / K as column slices of one matrix
+  run_attn_case(1, 1, 128, 512, 512, false, 300);   // the maximum jumps in the middle of the stream
+  bench_attn("vae mid attention 64^2 d512", 4, 1, 4096, 4096, 512);
+  bench_attn("vae mid attention 96^2 d512", 2, 1, 9216, 9216, 512);
+}
 
-// x [B,H,W,C] f16 -> V [16][T][C] f16, T = B * (H/2) * (W/2); one thread = one tile x 8 channels
-__global__ void wino_input_kernel(const h16* __restrict__ x, h16* __restrict__ V, int B, int H, int W, int C) {
-  const int cv = C / 8;
-  const long T = (long)B * (H / 2) * (W / 2);
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= T * cv) return;
-  const long t = i / cv;
-  const int c0 = (int)(i - t * cv) * 8;
-  const int tw = W / 2, th = H / 2;
-  const int b = (int)(t / (th * tw));
-  const int ty = (int)((t / tw) % th), tx = (int)(t % tw);
-  float d[4][4][8];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int y = 2 * ty - 1 + r, xx = 2 * tx - 1 + q;
-      h16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (y >= 0 && y < H && xx >= 0 && xx < W) v = *reinterpret_cast<const h16x8*>(x + (((long)b * H + y) * W + xx) * C + c0);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) d[r][q][e] = (float)v[e];
-    }
-  // B^T d B, B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]
-  float tmp[4][4][8];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      tmp[0][q][e] = d[0][q][e] - d[2][q][e];
-      tmp[1][q][e] = d[1][q][e] + d[2][q][e];
-      tmp[2][q][e] = d[2][q][e] - d[1][q][e];
-      tmp[3][q][e] = d[1][q][e] - d[3][q][e];
-    }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    h16x8 o[4];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      o[0][e] = (h16)(tmp[r][0][e] - tmp[r][2][e]);
-      o[1][e] = (h16)(tmp[r][1][e] + tmp[r][2][e]);
-      o[2][e] = (h16)(tmp[r][2][e] - tmp[r][1][e]);
-      o[3][e] = (h16)(tmp[r][1][e] - tmp[r][3][e]);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) *reinterpret_cast<h16x8*>(V + ((long)(r * 4 + q) * T + t) * C + c0) = o[q];
+static void run_narrow_mode() {
+  run_narrow_conv_cases();
+  bench_gemm("unet head conv 320->4 @64^2 B8", 8 * 4096, 4, 2880, 3, 8, 64, 320, 0);
+  bench_gemm("unet head conv 320->4 @96^2 B4", 4 * 9216, 4, 2880, 3, 4, 96, 320, 0);
+  bench_gemm("vae conv_out 128->3 @512^2 B4", 4 * 262144, 3, 1152, 3, 4, 512, 128, 0);
+  bench_gemm("unet head conv, round-5 kernel", 8 * 4096, 4, 2880, 3, 8, 64, 320, 11);
+  bench_gemm("vae conv_out, round-5 kernel", 4 * 262144, 3, 1152, 3, 4, 512, 128, 21);
+}
+
+static void run_ups_fold_mode(bool full) {
+  run_ups_fold_cases();
+  if (full) {       // the two large upsample convolutions of a C2 UNet pass against fp64 (a minute of host time)
+    run_gemm_case(conv(8, 32, 32, 640, 640).ups(2).gn_out());
+    run_gemm_case(conv(8, 16, 16, 1280, 1280).ups(2).gn_out());
   }
 }
 
-// Mk [16][T][N] f16 -> y [B,H,W,N] f16 (+ bias); one thread = one tile x 8 channels.  A^T = [1 1 1 0; 0 1 -1 -1]
-__global__ void wino_output_kernel(const h16* __restrict__ Mk, const h16* __restrict__ bias, h16* __restrict__ y, int B, int H,
-                                   int W, int N) {
-  const int nv = N / 8;
-  const long T = (long)B * (H / 2) * (W / 2);
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= T * nv) return;
-  const long t = i / nv;
-  const int n0 = (int)(i - t * nv) * 8;
-  const int tw = W / 2, th = H / 2;
-  const int b = (int)(t / (th * tw));
-  const int ty = (int)((t / tw) % th), tx = (int)(t % tw);
-  float m[4][4][8];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const h16x8 v = *reinterpret_cast<const h16x8*>(Mk + ((long)k * T + t) * N + n0);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) m[k >> 2][k & 3][e] = (float)v[e];
-  }
-  const h16x8 bv = *reinterpret_cast<const h16x8*>(bias + n0);
-  float tmp[2][4][8];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      tmp[0][q][e] = m[0][q][e] + m[1][q][e] + m[2][q][e];
-      tmp[1][q][e] = m[1][q][e] - m[2][q][e] - m[3][q][e];
-    }
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    h16x8 o0, o1;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      o0[e] = (h16)(tmp[r][0][e] + tmp[r][1][e] + tmp[r][2][e] + (float)bv[e]);
-      o1[e] = (h16)(tmp[r][1][e] - tmp[r][2][e] - tmp[r][3][e] + (float)bv[e]);
-    }
-    h16* row = y + (((long)b * H + 2 * ty + r) * W + 2 * tx) * N + n0;
-    *reinterpret_cast<h16x8*>(row) = o0;
-    *reinterpret_cast<h16x8*>(row + N) = o1;
-  }
-}
-
-// one shape: times (and, if check, verifies against fp64) the direct patch-kernel convolution and the Winograd pipeline
-static void winograd_case(const char* label, int B, int H, int Cin, int N, bool check) {
-  const int W = H, M = B * H * W, K = 9 * Cin;
-  const long T = (long)B * (H / 2) * (W / 2);
-  auto x = rand_h((size_t)M * Cin), wt = rand_h((size_t)N * K, 1.7f / sqrtf((float)K)), bias = rand_h(N, 0.5f);
-  // U_k[n][c] = (G g G^T)[k], G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1]; direct weight layout is [N][ky][kx][Cin]
-  std::vector<h16> U((size_t)16 * N * Cin);
-  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  for (int n = 0; n < N; ++n)
-    for (int c = 0; c < Cin; ++c) {
-      double g[3][3], t1[4][3];
-      for (int a = 0; a < 3; ++a)
-        for (int b2 = 0; b2 < 3; ++b2) g[a][b2] = (double)wt[(size_t)n * K + (a * 3 + b2) * Cin + c];
-      for (int a = 0; a < 4; ++a)
-        for (int b2 = 0; b2 < 3; ++b2) t1[a][b2] = G[a][0] * g[0][b2] + G[a][1] * g[1][b2] + G[a][2] * g[2][b2];
-      for (int a = 0; a < 4; ++a)
-        for (int b2 = 0; b2 < 4; ++b2)
-          U[((size_t)(a * 4 + b2) * N + n) * Cin + c] = (h16)(t1[a][0] * G[b2][0] + t1[a][1] * G[b2][1] + t1[a][2] * G[b2][2]);
-    }
-  Dev<h16> dx(x), dw(wt), db(bias), dU(U), dV((size_t)16 * T * Cin), dM((size_t)16 * T * N), dy((size_t)M * N), dyw((size_t)M * N);
-  Dev<float> dWS((size_t)24 << 20);
-  PfdGemmDesc d;
-  memset(&d, 0, sizeof(d));
-  d.A = dx.p; d.W = dw.p; d.bias = db.p; d.C = dy.p; d.lda = Cin; d.ldw = K; d.ldc = N; d.M = M; d.N = N; d.K = K; d.rows_per_rv = 1;
-  d.ksize = 3; d.stride = 1; d.pad = 1; d.B = B; d.H = H; d.Wd = W; d.Cin = Cin; d.Ho = H; d.Wo = W;
-  d.ws = dWS.p; d.ws_bytes = (size_t)96 << 20;
-  int rc = 0;
-  const float t_direct = time_ms([&] { rc |= pfd_gemm_f16(&d, nullptr); }, 20) * 1e3f;
-  PfdGemmDesc g;
-  memset(&g, 0, sizeof(g));
-  g.lda = Cin; g.ldw = Cin; g.ldc = N; g.M = (int)T; g.N = N; g.K = Cin; g.rows_per_rv = 1; g.ws = dWS.p; g.ws_bytes = (size_t)96 << 20;
-  const unsigned gi = (unsigned)((T * (Cin / 8) + 255) / 256), go = (unsigned)((T * (N / 8) + 255) / 256);
-  auto in_t = [&] { hipLaunchKernelGGL(wino_input_kernel, dim3(gi), dim3(256), 0, nullptr, dx.p, dV.p, B, H, W, Cin); };
-  auto gemms = [&] {
-    for (int k = 0; k < 16; ++k) {
-      g.A = dV.p + (size_t)k * T * Cin; g.W = dU.p + (size_t)k * N * Cin; g.C = dM.p + (size_t)k * T * N;
-      rc |= pfd_gemm_f16(&g, nullptr);
-    }
-  };
-  auto out_t = [&] { hipLaunchKernelGGL(wino_output_kernel, dim3(go), dim3(256), 0, nullptr, dM.p, db.p, dyw.p, B, H, W, N); };
-  const float t_in = time_ms(in_t, 20) * 1e3f, t_g = time_ms(gemms, 10) * 1e3f, t_out = time_ms(out_t, 20) * 1e3f;
-  const float t_all = time_ms([&] { in_t(); gemms(); out_t(); }, 10) * 1e3f;
-  // optimistic bound for a batched / fused product kernel: the same MACs and activation traffic as ONE launch (16 T rows
-  // against one weight matrix: 1/16 of the weight traffic, no launch boundaries between the 16 GEMMs)
-  PfdGemmDesc o = g;
-  o.A = dV.p; o.W = dU.p; o.C = dM.p; o.M = (int)(16 * T);
-  const float t_one = time_ms([&] { rc |= pfd_gemm_f16(&o, nullptr); }, 10) * 1e3f;
-  printf("winograd %-26s M%-6d N%-5d K%-6d rc=%d | direct %7.1f us (%6.1f TF/s) | F(2x2,3x3): transform %6.1f + 16 GEMMs %7.1f "
-         "+ inverse %6.1f = %7.1f us (x%.2f of direct); 16 GEMMs as one launch %7.1f us -> lower bound %7.1f us (x%.2f)\n",
-         label, M, N, K, rc, t_direct, 2.0 * M * N * K / t_direct * 1e-6, t_in, t_g, t_out, t_all, t_all / t_direct, t_one,
-         t_in + t_one + t_out, (t_in + t_one + t_out) / t_direct);
-  // the two results must agree with each other at the shape being timed (fp16 noise)
-  {
-    in_t(); gemms(); out_t();
-    rc |= pfd_gemm_f16(&d, nullptr);
-    auto a = dy.get(), b2 = dyw.get();
-    double worst = 0, rms = 0;
-    for (size_t i = 0; i < a.size(); ++i) { const double e = fabs((double)a[i] - (double)b2[i]); worst = std::max(worst, e); rms += e * e; }
-    printf("         winograd vs direct on the GPU: max |diff| %.3e, rms %.3e\n", worst, sqrt(rms / a.size()));
-  }
-  if (check) {   // fp64 direct convolution on the host
-    std::vector<double> ref((size_t)M * N);
-    for (int m = 0; m < M; ++m) {
-      const int b = m / (H * W), oy = (m / W) % H, ox = m % W;
-      for (int n = 0; n < N; ++n) {
-        double sacc = (double)bias[n];
-        for (int ky = 0; ky < 3; ++ky)
-          for (int kx = 0; kx < 3; ++kx) {
-            const int iy = oy + ky - 1, ix = ox + kx - 1;
-            if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
-            const h16* ap = &x[(((size_t)b * H + iy) * W + ix) * Cin];
-            const h16* wp = &wt[(size_t)n * K + (ky * 3 + kx) * Cin];
-            for (int c = 0; c < Cin; ++c) sacc += (double)ap[c] * (double)wp[c];
-          }
-        ref[(size_t)m * N + n] = sacc;
-      }
-    }
-    auto a = dy.get(), b2 = dyw.get();
-    double ed = 0, ew = 0, rd = 0, rw = 0, rr = 0;
-    for (size_t i = 0; i < ref.size(); ++i) {
-      const double e1 = fabs((double)a[i] - ref[i]), e2 = fabs((double)b2[i] - ref[i]);
-      ed = std::max(ed, e1); ew = std::max(ew, e2); rd += e1 * e1; rw += e2 * e2; rr += ref[i] * ref[i];
-    }
-    printf("         error vs fp64 direct convolution (output rms %.3f): direct max %.3e rel-L2 %.3e | winograd max %.3e rel-L2 %.3e "
-           "(x%.1f)\n", sqrt(rr / ref.size()), ed, sqrt(rd / rr), ew, sqrt(rw / rr), sqrt(rw / rd));
-    ++g_total;
-    if (!(sqrt(rw / rr) < 1e-2)) { ++g_fail; printf("FAIL winograd prototype is not a convolution\n"); }
-  }
-  fflush(stdout);
-}
-
-static int winograd_main() {
-  // numerics at a shape the host can check (same K structure as the UNet's 320 -> 320 convolutions)
-  winograd_case("check 320->320 @16^2", 1, 16, 320, 320, true);
-  winograd_case("check 1280->1280 @8^2", 1, 8, 1280, 1280, true);
-  // the four dominant 3x3 shapes of a C2 UNet pass (UNet batch 8)
-  winograd_case("320->320 @64^2", 8, 64, 320, 320, false);
-  winograd_case("960->320 @64^2", 8, 64, 960, 320, false);
-  winograd_case("640->640 @32^2", 8, 32, 640, 640, false);
-  winograd_case("1280->1280 @16^2", 8, 16, 1280, 1280, false);
-  printf("%d checks, %d failed\n", g_total, g_fail);
-  return g_fail ? 1 : 0;
-}
-
-// Per-launch floor of the runtime: N dependent launches of a kernel with ~no work, in-stream and as one
-// hipGraph -- what every one of the ~500 launches of a UNet pass pays on top of its own duration.
-static void bench_launch_floor() {
-  Dev<h16> a(std::vector<h16>(4096)), b(std::vector<h16>(4096)), c(4096);
-  const int N = 2000;
-  hipStream_t st;
-  HIP_OK(hipStreamCreate(&st));
-  hipEvent_t e0, e1;
-  HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
-  auto run = [&] { for (int i = 0; i < N; ++i) pfd_add_f16(a.p, b.p, c.p, 4096, st); };
-  run();
-  HIP_OK(hipStreamSynchronize(st));
-  HIP_OK(hipEventRecord(e0, st)); run(); HIP_OK(hipEventRecord(e1, st));
-  HIP_OK(hipEventSynchronize(e1));
-  float ms = 0;
-  HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-  printf("bench launch floor: in-stream      %6.2f us/launch (%d dependent tiny launches)\n", ms * 1e3 / N, N);
-  hipGraph_t g; hipGraphExec_t ge;
-  HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeGlobal));
-  run();
-  HIP_OK(hipStreamEndCapture(st, &g));
-  HIP_OK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-  HIP_OK(hipGraphLaunch(ge, st));
-  HIP_OK(hipStreamSynchronize(st));
-  HIP_OK(hipEventRecord(e0, st)); HIP_OK(hipGraphLaunch(ge, st)); HIP_OK(hipEventRecord(e1, st));
-  HIP_OK(hipEventSynchronize(e1));
-  HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-  printf("bench launch floor: hipGraph replay %6.2f us/launch\n", ms * 1e3 / N);
-  HIP_OK(hipGraphExecDestroy(ge)); HIP_OK(hipGraphDestroy(g)); HIP_OK(hipStreamDestroy(st));
-  fflush(stdout);
-}
-
-__global__ void count_mismatch_kernel(const unsigned short* a, const unsigned short* b, size_t n, unsigned* cnt) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned bad = 0;
-  for (; i < n; i += (size_t)gridDim.x * blockDim.x) bad += a[i] != b[i];
-  if (bad) atomicAdd(cnt, bad);
-}
-
-// --replay <file>: relaunch a recorded GEMM/conv launch list (tools/dump_unet_shapes.py) once each, in
-// order, on random operands -- the torch-free workload rocprofv3 --pmc is pointed at.
-static int replay(const char* path, bool timed = false, int force_tile = 0) {
-  FILE* f = fopen(path, "r");
-  if (!f) { printf("cannot open %s\n", path); return 1; }
-  // one launch per line: 19 fields (rounds 1-3), 22 (+ k_split, zero_rows, gn_out != NULL) or 24 (+ gnf = 0 | 1 | 2 = fused
-  // GroupNorm in the split-K reduction keeping / skipping the raw result, res_rows); shorter lines are padded with zeros
-  std::vector<std::array<long, 24>> rows;
-  char line[512];
-  while (fgets(line, sizeof(line), f)) {
-    std::array<long, 24> r{};
-    int n = 0, off = 0, adv = 0;
-    while (n < 24 && sscanf(line + off, "%ld%n", &r[n], &adv) == 1) { ++n; off += adv; }
-    if (n != 19 && n != 22 && n != 24) break;
-    rows.push_back(r);
-  }
-  fclose(f);
-  size_t maxA = 0, maxW = 0, maxC = 0, maxV = 0;
-  for (auto& q : rows) {
-    const long M = q[0], N = q[1], K = q[2], ks = q[8];
-    const size_t a = ks > 0 ? (size_t)q[12] * q[13] * q[14] * q[15] : (size_t)M * K;
-    maxA = std::max(maxA, a); maxW = std::max(maxW, (size_t)N * K * (ks > 0 && q[11] == 2 ? 4 : 1)); maxC = std::max(maxC, (size_t)M * N);
-    maxV = std::max(maxV, (size_t)std::max(M, N) * 4);
-  }
-  Dev<h16> dA(rand_h(maxA)), dW(rand_h(maxW, 0.05f)), dB(rand_h(maxV)), dRV(rand_h(maxC)), dR(rand_h(maxC)), dC(maxC), dY(maxC);
-  Dev<float> dWS((size_t)24 << 20);
-  size_t maxM = 1;
-  for (auto& q : rows) maxM = std::max(maxM, (size_t)q[0]);
-  Dev<float> dGnO((maxM / 64 + 1) * 8 * 16 * 2);   // PfdGemmDesc.gn_out: [M / 64][N / 160 <= 8][16] float2
-  Dev<float> dLnS(rand_f(maxM * 16, 1.0f)), dLnC(rand_f(16384, 1.0f)), dLnO(maxM * 16);   // [M][<= 8][2] statistics, column sums
-  {  // plausible statistics: sum ~ 0, sum of squares ~ K (so that rstd is finite)
-    std::vector<float> st(maxM * 16);
-    for (size_t i = 0; i < st.size(); i += 2) { st[i] = 0.5f; st[i + 1] = 200.f; }
-    HIP_OK(hipMemcpy(dLnS.p, st.data(), st.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  int bad = 0;
-  // --replay-time: every launch reads its weights from a fresh slice of a 2 GB pool (as in the UNet,
-  // where 1.7 GB of other layers' weights pass through the caches between two uses of a layer) and is
-  // bracketed by its own pair of events; the table lists, per distinct problem, the time against the
-  // per-problem roofline max(flops / 2.5 PF, algorithmic bytes / 8 TB/s).
-  const size_t pool_elems = timed ? (size_t)1 << 30 : 0;
-  Dev<h16> dPool(pool_elems ? pool_elems : 8);
-  if (timed) HIP_OK(hipMemset(dPool.p, 0x11, pool_elems * 2));
-  size_t pool_off = 0;
-  const int reps = timed ? 4 : 2;
-  std::vector<hipEvent_t> ev(timed ? rows.size() + 1 : 0);
-  for (auto& e : ev) HIP_OK(hipEventCreate(&e));
-  std::vector<double> acc_ms(rows.size(), 0.0);
-  for (int rep = 0; rep < reps; ++rep) {  // first pass warms caches / code objects
-    size_t li = 0;
-    if (timed) HIP_OK(hipEventRecord(ev[0], nullptr));
-    for (auto& q : rows) {
-      PfdGemmDesc d;
-      memset(&d, 0, sizeof(d));
-      d.M = q[0]; d.N = q[1]; d.K = q[2]; d.act = q[3];
-      d.A = dA.p; d.W = dW.p; d.C = dC.p;
-      d.bias = q[4] ? dB.p : nullptr; d.rowvec = q[5] ? dRV.p : nullptr; d.R = q[6] ? dR.p : nullptr;
-      d.bias_per_row = q[7];
-      d.ksize = q[8]; d.stride = q[9]; d.pad = q[10]; d.ups = q[11];
-      d.B = q[12]; d.H = q[13]; d.Wd = q[14]; d.Cin = q[15]; d.Ho = q[16]; d.Wo = q[17];
-      d.rows_per_rv = (int)std::min<long>(q[18], 1 << 30);
-      const long nout = d.act == PFD_ACT_GEGLU ? d.N / 2 : d.N;
-      d.lda = d.ksize > 0 ? d.Cin : d.K; d.ldw = d.K; d.ldc = nout; d.ldr = nout; d.ldrv = d.N;
-      d.ws = dWS.p; d.ws_bytes = (size_t)96 << 20;
-      if (q[19] > 0) { d.k_split = (int)q[19]; d.A2 = dA.p + (size_t)d.M * d.k_split; d.lda = d.k_split; d.lda2 = d.K - d.k_split; }
-      d.zero_rows = (int)q[20];
-      if (q[21]) d.gn_out = dGnO.p;
-      if (q[22]) {   // GroupNorm(+SiLU) of the output inside the split-K reduction (PfdGemmDesc.gnf_y); the residual then wraps never
-        d.gnf_gamma = dB.p; d.gnf_beta = dB.p + d.N; d.gnf_y = dY.p; d.gnf_ldy = nout; d.gnf_eps = 1e-5f; d.gnf_act = PFD_ACT_SILU;
-        d.gnf_rows = d.ksize > 0 ? d.Ho * d.Wo : (int)std::min<long>(q[18], d.M);
-        d.gnf_skip_raw = q[22] == 2;
-      }
-      if (q[23] > 0 && d.R && !q[22]) d.res_rows = (int)q[23];
-      static const bool replay_warm = getenv("PFD_REPLAY_WARM") && atoi(getenv("PFD_REPLAY_WARM")) != 0;   // weights of every launch from ONE buffer (cache-warm): the bound of any weight prefetch
-      if (timed && !replay_warm) {
-        const size_t wn = ((size_t)d.N * d.K * (d.ksize > 0 && d.ups == 2 ? 4 : 1) + 4095) & ~(size_t)4095;   // (ups = 2: four phase blocks)
-        if (pool_off + wn > pool_elems) pool_off = 0;
-        d.W = dPool.p + pool_off;
-        pool_off += wn;
-      }
-      // PFD_REPLAY_LN=1: the launches that carry a folded LayerNorm in the UNet do so here too (q|k|v, q and GEGLU
-      // projections consume row statistics; proj_in / out-projections emit them) -- prices the fold per shape
-      static const bool replay_ln = getenv("PFD_REPLAY_LN") && atoi(getenv("PFD_REPLAY_LN")) != 0;
-      if (replay_ln && d.ksize == 0 && d.N % 160 == 0 && !d.bias_per_row) {
-        const bool cwidth = d.K == 320 || d.K == 640 || d.K == 1280;
-        if (cwidth && (d.act == PFD_ACT_GEGLU || d.N == 3 * d.K || (d.N == d.K && !d.R && !d.bias))) {
-          d.ln_stats = dLnS.p; d.ln_colsum = dLnC.p; d.ln_parts = d.K / 160; d.ln_eps = 1e-5f;
-        } else if ((d.N == 320 || d.N == 640 || d.N == 1280) && d.act == 0 && d.bias && d.K == d.N) {   // out-projections, proj_in
-          d.ln_out = dLnO.p;
-        }
-      }
-      static const bool replay_tiled = getenv("PFD_REPLAY_TILED") && atoi(getenv("PFD_REPLAY_TILED")) != 0;
-      if (replay_tiled && (d.N % 160 == 0 || d.N % 128 == 0) && d.K % 64 == 0 && !d.bias_per_row) d.w_tiled = 1;
-      if (force_tile == 0 || pfd_gemm_f16_ex(&d, force_tile, nullptr) != 0) {
-        int rc = pfd_gemm_f16(&d, nullptr);
-        if (rc == PFD_ESHAPE && d.gnf_y) {   // declined (this build does not split the shape): the two-call form's first call
-          d.gnf_y = nullptr;
-          rc = pfd_gemm_f16(&d, nullptr);
-        }
-        bad += rc != 0;
-      }
-      // PFD_REPLAY_DET=1: every launch twice on the same operands into two buffers; the results must be the same bits
-      static const bool replay_det = getenv("PFD_REPLAY_DET") && atoi(getenv("PFD_REPLAY_DET")) != 0;
-      if (replay_det && rep == 0) {
-        static Dev<h16>* dC2 = nullptr;
-        static Dev<unsigned>* dCnt = nullptr;
-        if (!dC2) { dC2 = new Dev<h16>(maxC); dCnt = new Dev<unsigned>(1); }
-        PfdGemmDesc d2 = d;
-        d2.C = dC2->p;
-        HIP_OK(hipMemset(dCnt->p, 0, sizeof(unsigned)));
-        bad += pfd_gemm_f16(&d2, nullptr) != 0;
-        const size_t nel = (size_t)d.M * nout;
-        hipLaunchKernelGGL(count_mismatch_kernel, dim3(1024), dim3(256), 0, nullptr, (const unsigned short*)dC.p,
-                           (const unsigned short*)dC2->p, nel, dCnt->p);
-        const unsigned nb = dCnt->get()[0];
-        if (nb) {
-          ++bad;
-          printf("NONDETERMINISTIC: M%ld N%ld K%ld ksize%ld stride%ld ups%ld act%ld rv%d R%d: %u of %zu elements differ between two launches\n",
-                 (long)d.M, (long)d.N, (long)d.K, (long)d.ksize, (long)d.stride, (long)d.ups, (long)d.act, d.rowvec != nullptr, d.R != nullptr, nb, nel);
-        }
-      }
-      if (timed) HIP_OK(hipEventRecord(ev[++li], nullptr));
-    }
-    HIP_OK(hipDeviceSynchronize());
-    if (timed && rep > 0)
-      for (size_t i = 0; i < rows.size(); ++i) {
-        float ms = 0;
-        HIP_OK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-        acc_ms[i] += ms / (reps - 1);
-      }
-  }
-  HIP_OK(hipDeviceSynchronize());
-  printf("replayed %zu launches x%d, %d errors\n", rows.size(), reps, bad);
-  if (timed) {
-    struct Agg { std::array<long, 24> q; int n; double ms; };
-    std::vector<Agg> aggs;
-    for (size_t i = 0; i < rows.size(); ++i) {
-      bool found = false;
-      for (auto& a : aggs) if (a.q == rows[i]) { a.n++; a.ms += acc_ms[i]; found = true; break; }
-      if (!found) aggs.push_back({rows[i], 1, acc_ms[i]});
-    }
-    std::sort(aggs.begin(), aggs.end(), [](const Agg& a, const Agg& b) { return a.ms > b.ms; });
-    double tot = 0, tot_ideal = 0;
-    printf("%7s %6s %6s k s u act rv R ks zrows gn | %3s %9s %8s %8s %8s %8s\n", "M", "N", "K", "n", "us/launch", "TF/s", "GB/s", "ideal_us", "sum_ms");
-    for (auto& a : aggs) {
-      const auto& q = a.q;
-      const double M = q[0], N = q[1], K = q[2];
-      const double nout = q[3] == PFD_ACT_GEGLU ? N / 2 : N;
-      const double Mz = M - q[20];   // rows with a non-zero operand (PfdGemmDesc.zero_rows)
-      const double abytes = q[8] > 0 ? 2.0 * q[12] * q[13] * q[14] * q[15] : 2.0 * Mz * K;
-      const double bytes = abytes + 2.0 * N * K + 2.0 * M * nout + (q[6] ? 2.0 * M * nout : 0) + (q[5] ? 2.0 * M * N / std::max<double>(1, std::min<long>(q[18], M)) : 0);
-      const double flops = 2.0 * Mz * N * K;
-      const double us = a.ms / a.n * 1e3;
-      const double ideal = std::max(flops / 2.5e15, bytes / 8e12) * 1e6;
-      tot += a.ms; tot_ideal += ideal * a.n * 1e-3;
-      printf("%7ld %6ld %6ld %ld %ld %ld %3ld %2ld %ld %4ld %5ld %ld | %3d %9.1f %8.1f %8.1f %8.1f %8.2f\n", q[0], q[1], q[2], q[8], q[9], q[11], q[3], q[5], q[6],
-             q[19], q[20], q[21], a.n, us, flops / us * 1e-6, bytes / us * 1e-3, ideal, a.ms);
-    }
-    printf("total %.2f ms per UNet pass (GEMM/conv only); roofline-ideal %.2f ms\n", tot, tot_ideal);
-  }
-  return bad;
-}
-
-int main(int argc, char** argv) {
-  if (argc > 2 && !strcmp(argv[1], "--replay")) return replay(argv[2]);
-  if (argc > 1 && !strcmp(argv[1], "--launch-floor")) { bench_launch_floor(); return 0; }
-  if (argc > 1 && !strcmp(argv[1], "--winograd")) return winograd_main();
-  if (argc > 1 && !strcmp(argv[1], "--bench-patch")) {   // one 3x3 conv per image width the patch kernel serves
-    bench_gemm("conv3x3 320->320 @64^2", 0, 320, 0, 3, 8, 64, 320, 0);
-    bench_gemm("conv3x3 640->640 @32^2", 0, 640, 0, 3, 8, 32, 640, 0);
-    bench_gemm("conv3x3 1280->1280 @16^2", 0, 1280, 0, 3, 8, 16, 1280, 0);
-    bench_gemm("conv3x3 320->320 @64^2 implicit GEMM", 0, 320, 0, 3, 8, 64, 320, 5400);
-    return 0;
-  }
-  if (argc > 1 && !strcmp(argv[1], "--bench-gn-conv")) {   // GroupNorm + conv: two launches + a tensor vs table + prologue
-    bench_gn_conv("320->320 @64^2", 16, 64, 320, 0, 320);
-    bench_gn_conv("640->320 @64^2 (skip concat)", 16, 64, 320, 320, 320);
-    bench_gn_conv("960->320 @64^2 (skip concat)", 16, 64, 640, 320, 320);
-    bench_gn_conv("640->640 @32^2", 16, 32, 640, 0, 640);
-    bench_gn_conv("1280->640 @32^2 (skip concat)", 16, 32, 640, 640, 640);
-    bench_gn_conv("1920->640 @32^2 (skip concat)", 16, 32, 1280, 640, 640);
-    return 0;
-  }
-  if (argc > 1 && !strcmp(argv[1], "--gemm-new")) {   // quick correctness pass over the round-3 tile variants only
-    for (int v : {5100, 5300, 9200, 9300}) {
-      run_gemm_case({1100, 320, 1024, 0, true, true, true, false, v});
-      run_gemm_case({300, 320, 192, PFD_ACT_SILU, true, true, true, false, v});
-      run_gemm_case({77, 160, 64, 0, true, false, false, false, v, 8});
-      run_gemm_case({0, 160, 0, 0, true, true, false, false, v, 0, 3, 1, 1, 0, 3, 16, 16, 128});
-      run_gemm_case({900, 320, 1536, 0, true, false, false, false, v + 3});
-      run_gemm_case({200, 320, 128, PFD_ACT_GEGLU, true, false, false, false, v});
-    }
-    { GemmCase t{520, 480, 128, 0, false, false, false, false, 5100}; t.n_split = 320; run_gemm_case(t); }
-    { GemmCase t{520, 480, 128, 0, false, false, false, false, 9200}; t.n_split = 320; run_gemm_case(t); }
-    run_gemm_case({600, 640, 320, PFD_ACT_GEGLU, true, false, false, false, 9400});
-    run_gemm_case({300, 320, 64, PFD_ACT_GEGLU, false, false, false, false, 9400});
-    run_tiled_weight_cases();
-    printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
-    return g_fail;
-  }
-  if (argc > 1 && !strcmp(argv[1], "--r5")) {   // round 5: the kernels adopted this round
-    // adopted: the split-K reduction that also normalises (PfdGemmDesc.gnf_y) at the shapes the UNet / ControlNet give it
-    run_gnf_case(8, 16, 16, 1280, 1280, PFD_ACT_SILU, 1e-5f, false, true, false);       // ResBlock conv1 @16^2 (patch kernel, split 4)
-    run_gnf_case(8, 8, 8, 1280, 1280, PFD_ACT_SILU, 1e-5f, false, true, false);         // @8^2 (ring kernel, split 4)
-    run_gnf_case(8, 8, 8, 2560, 1280, PFD_ACT_SILU, 1e-5f, false, true, false);         // over the skip concat width, split 8
-    run_gnf_case(8, 16, 16, 640, 1280, PFD_ACT_SILU, 1e-5f, false, true, false);        // 640 -> 1280
-    run_gnf_case(8, 16, 16, 1280, 1280, PFD_ACT_NONE, 1e-6f, true, false, true);        // + residual, raw kept, no activation
-    run_gnf_case(4, 8, 8, 1280, 1280, PFD_ACT_SILU, 1e-5f, true, true, true);           // UNet batch 4
-    run_gnf_case(8, 16, 16, 1280, 1280, PFD_ACT_SILU, 1e-5f, false, true, false, 10802);   // forced patch kernel, split 2
-    run_gnf_case(8, 8, 8, 1280, 1280, PFD_ACT_SILU, 1e-5f, false, true, false, 3308);        // forced 4-stage ring, split 8
-    run_gnf_decline_case(8, 64, 64, 320, 320);                                          // 64^2: not split, cpg 10
-    // round 6: the 640-channel norms of the 32^2 level (20 channels per group, 1024 x 5 chunks per slab)
-    run_gnf_case(8, 32, 32, 640, 640, PFD_ACT_SILU, 1e-5f, false, true, false);         // ResBlock conv1 @32^2 (patch kernel, split 2)
-    run_gnf_case(8, 32, 32, 640, 640, PFD_ACT_SILU, 1e-5f, true, false, true);          // conv2: + residual, raw kept for the skip
-    run_gnf_case(8, 32, 32, 1280, 640, PFD_ACT_SILU, 1e-5f, false, true, false);        // over a skip concat width
-    run_gnf_case(4, 32, 32, 320, 640, PFD_ACT_SILU, 1e-5f, false, true, false);         // first ResBlock of the level, UNet batch 4
-    // residual stored once for a doubled batch (PfdGemmDesc.res_rows): every store pass and both plain reductions
-    for (int v : {0, 9200, 9300, 3200, 3300, 5400, 5800}) {
-      { GemmCase c{1024, 320, 256, 0, true, true, true, false, v}; c.res_rows = 512; run_gemm_case(c); }                      // plain store pass
-      if (v != 5800) { GemmCase c{1024, 320, 256, 0, true, true, false, false, v}; c.res_rows = 512; c.zero_rows = 512; run_gemm_case(c); }  // + zero rows: the cross-attention re-join (not on the loader-wave kernel)
-      { GemmCase c{1024, 320, 320, 0, true, true, false, false, v}; c.res_rows = 512; c.gn_out = 1; run_gemm_case(c); }       // statistics-emitting store pass: proj_out
-    }
-    { GemmCase c{1024, 320, 2048, 0, true, true, false, false, 3304}; c.res_rows = 512; run_gemm_case(c); }                    // split-K 4: plain reduction
-    { GemmCase c{1024, 320, 2048, 0, true, true, false, false, 3304}; c.res_rows = 512; c.gn_out = 1; run_gemm_case(c); }      // ... statistics-emitting reduction
-    // the statistics-emitting split-K reduction and the GroupNorm apply from producer statistics
-    { GemmCase c{512, 1280, 2048, 0, true, true, true, false, 3304}; c.gn_out = 1; run_gemm_case(c); }                          // split-K 4, cpg 40
-    { GemmCase c{0, 320, 0, 0, true, true, true, false, 9302, 0, 3, 1, 1, 0, 2, 16, 16, 128}; c.gn_out = 1; run_gemm_case(c); }   // conv, split-K 2
-    run_gn_case(8, 64, 1280, 0, 32, PFD_ACT_SILU, 1e-5f);
-    run_gn_case(8, 256, 1280, 1280, 32, PFD_ACT_SILU, 1e-5f);
-    run_gn_pstats_case(8, 4096, 320, 0, PFD_ACT_SILU, 1e-5f);
-    run_gn_pstats_case(8, 4096, 320, 320, PFD_ACT_SILU, 1e-5f);
-    run_gn_pstats_case(3, 1024, 640, 0, PFD_ACT_NONE, 1e-6f);
-    run_gn_pstats_case(2, 256, 1280, 1280, PFD_ACT_SILU, 1e-5f);
-    printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
-    return g_fail;
-  }
-  if (argc > 1 && !strcmp(argv[1], "--ups-fold")) {   // upsample convolution as four 2x2-tap phase convolutions (PfdGemmDesc.ups = 2)
-    run_ups_fold_cases();
-    if (argc > 2 && !strcmp(argv[2], "full")) {       // the two large upsample convolutions of a C2 UNet pass against fp64 (a minute of host time)
-      { GemmCase c{0, 640, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 2, 8, 32, 32, 640}; c.gn_out = 1; run_gemm_case(c); }
-      { GemmCase c{0, 1280, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 2, 8, 16, 16, 1280}; c.gn_out = 1; run_gemm_case(c); }
-    }
-    printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
-    return g_fail;
-  }
-  if (argc > 1 && !strcmp(argv[1], "--patch-wide")) {   // 3x3 patch kernels on 48- / 96-wide images (2-D output tiles)
-    for (int v : {0, 10800, 10900}) {
-      run_gemm_case({0, 160, 0, PFD_ACT_SILU, true, true, true, false, v, 0, 3, 1, 1, 0, 1, 16, 48, 128});   // 16 x 16 tiles
-      run_gemm_case({0, 320, 0, 0, true, true, true, false, v, 0, 3, 1, 1, 0, 2, 8, 96, 64});                 // 8 x 32 tiles
-      run_gemm_case({0, 160, 0, 0, true, false, true, false, v, 0, 3, 1, 1, 0, 1, 32, 96, 128});              // 4 x 3 tiles
-      run_gemm_case({0, 160, 0, 0, true, true, false, false, v, 0, 3, 1, 1, 0, 3, 32, 48, 64});               // several samples
-    }
-    run_gemm_case({0, 160, 0, 0, true, true, true, false, 10802, 0, 3, 1, 1, 0, 1, 16, 96, 256});             // split over channel blocks
-    { GemmCase c{0, 320, 0, 0, true, true, true, false, 0, 0, 3, 1, 1, 0, 2, 16, 96, 128}; c.w_tiled = 1; run_gemm_case(c); }
-    run_gemm_case({0, 160, 0, 0, true, true, false, false, 5400, 0, 3, 1, 1, 0, 1, 16, 48, 128});             // same shape, implicit GEMM
-    printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
-    return g_fail;
-  }
-  if (argc > 1 && !strcmp(argv[1], "--narrow")) {   // conv3x3_narrow_kernel: cases + the two shapes of the pipeline
-    run_narrow_conv_cases();
-    bench_gemm("unet head conv 320->4 @64^2 B8", 8 * 4096, 4, 2880, 3, 8, 64, 320, 0);
-    bench_gemm("unet head conv 320->4 @96^2 B4", 4 * 9216, 4, 2880, 3, 4, 96, 320, 0);
-    bench_gemm("vae conv_out 128->3 @512^2 B4", 4 * 262144, 3, 1152, 3, 4, 512, 128, 0);
-    bench_gemm("unet head conv, round-5 kernel", 8 * 4096, 4, 2880, 3, 8, 64, 320, 11);
-    bench_gemm("vae conv_out, round-5 kernel", 4 * 262144, 3, 1152, 3, 4, 512, 128, 21);
-    printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
-    return g_fail;
-  }
-  if (argc > 1 && !strcmp(argv[1], "--image")) {   // the uint8 picture ingest only
-    run_image();
-    printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
-    return g_fail;
-  }
-  if (argc > 1 && !strcmp(argv[1], "--elementwise")) {   // boundary / elementwise kernels only (the seeded noise among them)
-    run_elementwise();
-    printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
-    return g_fail;
-  }
-  if (argc > 1 && !strcmp(argv[1], "--ln")) {
-    run_ln_fold_suite();
-    printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
-    return g_fail;
-  }
-  if (argc > 1 && !strcmp(argv[1], "--attn")) {   // attention correctness cases only (seconds; run once per PFD_ATTN mode)
-    run_attn_case(2, 2, 128, 128, 40, true);
-    run_attn_case(1, 2, 300, 148, 40, false);
-    run_attn_case(2, 2, 512, 256, 40, true);
-    run_attn_case(1, 1, 256, 40, 40, false);
-    run_attn_case(1, 2, 520, 1000, 40, false);
-    run_attn_case(1, 2, 77, 64, 40, true);
-    run_attn_case(1, 2, 200, 148, 40, false);
-    run_attn_case(2, 2, 64, 64, 80, true);
-    run_attn_case(1, 2, 144, 256, 96, false);
-    run_attn_case(1, 3, 148, 148, 96, false);
-    run_attn_case(2, 2, 64, 148, 160, false);
-    run_attn_case(1, 1, 256, 320, 160, true);
-    run_attn_case(1, 2, 520, 1000, 40, false, 700);   // maximum jumps at key 700 (tile 10 of 16)
-    run_attn_case(2, 2, 512, 256, 40, true, 130);
-    run_attn_case(1, 2, 300, 148, 40, false, 140);    // ... inside the ragged tile
-    run_attn_case(1, 2, 512, 1024, 40, true, 700);    // round 6: whole 64-key tiles (attention3_kernel when PFD_ATTN3_FORCE=1 or the grid is big)
-    run_attn_case(1, 1, 700, 640, 40, false, 333);    // ragged last query block
-    run_attn_case(8, 8, 1024, 1024, 40, true, 500);   // 256 blocks: attention3_kernel by the dispatcher's own rule
-    printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
-    return g_fail;
-  }
-  if (argc > 1 && !strcmp(argv[1], "--attn512")) {   // VAE mid-block attention (d = 512, one head): cases + bench
-    run_attn_case(2, 1, 256, 256, 512, false);
-    run_attn_case(1, 1, 200, 96, 512, false);          // ragged query tile, 3 key tiles
-    run_attn_case(1, 1, 128, 32, 512, false);          // a single key tile
-    run_attn_case(2, 1, 128, 512, 512, true);          // Q / K as column slices of one matrix
-    run_attn_case(1, 1, 128, 512, 512, false, 300);    // the maximum jumps in the middle of the stream
-    bench_attn("vae mid attention 64^2 d512", 4, 1, 4096, 4096, 512);
-    bench_attn("vae mid attention 96^2 d512", 2, 1, 9216, 9216, 512);
-    printf("%d checks, %d failed\n", g_total, g_fail);
-    return g_fail ? 1 : 0;
-  }
-  if (argc > 1 && !strcmp(argv[1], "--bench-attn")) {
-    bench_attn("self-attn 64^2 d40", 8, 8, 4096, 4096, 40);
-    bench_attn("self-attn 64^2 d40 (CFG prefix)", 4, 8, 4096, 4096, 40);
-    bench_attn("self-attn 96^2 d40 (C5)", 4, 8, 9216, 9216, 40);
-    bench_attn("self-attn 32^2 d80", 8, 8, 1024, 1024, 80);
-    bench_attn("self-attn 16^2 d160", 8, 8, 256, 256, 160);
-    bench_attn("cross-attn 64^2 d40", 4, 8, 4096, 148, 40);
-    bench_attn("seecoder cross d96", 1, 8, 144, 4096, 96);
-    // fixed cost of the short launches: the same problems with fewer keys
-    bench_attn("cross-attn 64^2 d40, 64 keys", 4, 8, 4096, 64, 40);
-    bench_attn("cross-attn 64^2 d40, 8 keys", 4, 8, 4096, 8, 40);
-    bench_attn("cross-attn 32^2 d80", 4, 8, 1024, 148, 80);
-    bench_attn("cross-attn 32^2 d80, 8 keys", 4, 8, 1024, 8, 80);
-    bench_attn("cross-attn 16^2 d160", 4, 8, 256, 148, 160);
-    bench_attn("cross-attn 16^2 d160, 8 keys", 4, 8, 256, 8, 160);
-    bench_attn("self-attn 16^2 d160, 64 keys", 8, 8, 256, 64, 160);
-    return 0;
-  }
-  if (argc > 1 && !strcmp(argv[1], "--bench-gn")) {
-    bench_gn("groupnorm+silu 320 @64^2", 8, 4096, 320);
-    bench_gn("groupnorm+silu 640 @64^2", 8, 4096, 640);
-    bench_gn("groupnorm+silu 640 @32^2", 8, 1024, 640);
-    bench_gn("groupnorm+silu 1280 @32^2", 8, 1024, 1280);
-    bench_gn("groupnorm+silu 1280 @16^2", 8, 256, 1280);
-    bench_gn("groupnorm+silu 2560 @16^2", 8, 256, 2560);
-    bench_gn("groupnorm+silu 1280 @8^2", 8, 64, 1280);
-    bench_gn("groupnorm+silu 128 @512^2", 4, 262144, 128);
-    bench_ln("layernorm 320 @64^2", 32768, 320);
-    bench_ln("layernorm 640 @32^2", 8192, 640);
-    bench_ln("layernorm 1280 @16^2", 2048, 1280);
-    return 0;
-  }
-  if (argc > 2 && !strcmp(argv[1], "--replay-time")) return replay(argv[2], true, argc > 3 ? atoi(argv[3]) : 0);
-  const bool bench = argc > 1 && !strcmp(argv[1], "--bench");
-  const bool only_bench = argc > 1 && !strcmp(argv[1], "--only-bench");
+static void print_device() {
   hipDeviceProp_t prop;
   HIP_OK(hipGetDeviceProperties(&prop, 0));
   printf("device: %s  CUs=%d  abi=%d\n", prop.name, prop.multiProcessorCount, pfd_abi_version());
+}
 
-  if (!only_bench) {
-    const int tiles[] = {22, 21, 12, 11};
-    for (int t : tiles) {
-      run_gemm_case({256, 256, 128, 0, true, false, false, false, t});
-      run_gemm_case({301, 203 - 3, 192, PFD_ACT_GELU, true, true, true, false, t});
-      run_gemm_case({77, 72, 64, PFD_ACT_SILU, true, true, false, true, t, 8});
-    }
-    run_gemm_case({130, 4, 128, 0, true, true, false, false, 0});          // N = 4 (UNet head)
-    run_gemm_case({64, 37, 64, PFD_ACT_RELU, false, false, false, false, 0});  // odd N -> scalar stores
-    run_gemm_case({200, 256, 128, PFD_ACT_GEGLU, true, true, false, false, 0});
-    run_gemm_case({512, 1280, 320, 0, true, false, true, false, 0});
-    for (int t : tiles) {
-      GemmCase c{0, 96, 0, 0, true, true, true, false, t, 0, 3, 1, 1, 0, 2, 9, 7, 64};
-      run_gemm_case(c);
-    }
-    run_gemm_case({0, 128, 0, PFD_ACT_SILU, true, false, false, false, 0, 0, 3, 2, 1, 0, 2, 10, 8, 64});  // stride 2
-    run_gemm_case({0, 64, 0, 0, true, true, false, false, 0, 0, 3, 1, 1, 1, 1, 5, 6, 128});             // upsample
-    run_gemm_case({0, 64, 0, 0, true, false, false, false, 0, 8, 3, 2, 0, 0, 1, 9, 9, 64});             // pad 0, stride 2, ld+8
-    run_gemm_case({0, 80, 0, 0, true, false, false, false, 0, 0, 1, 1, 0, 0, 2, 6, 6, 128});            // 1x1 as conv
+// ------------------------------------------------------------------ modes
+// A row's `cases` run first and are followed by the summary line; its `tool` runs after that and returns what it adds to
+// the exit status (the number of failed cases).  Both get the arguments that follow the flag.
+struct Mode {
+  const char *flag, *alias;
+  void (*cases)(int nargs, char** args);
+  int (*tool)(int nargs, char** args);
+  const char* help;
+};
+#define CASES(body) [](int, char**) { body; }
+static const Mode kModes[] = {
+    {"", nullptr, CASES(print_device(); run_default_cases()), nullptr,
+     "default run: GEMM / conv (with --ups-fold, --narrow and the first two --patch-wide cases), --ln, the first 12 --attn\n"
+     "                             and the first 2 --attn512 cases, Swin attention, GroupNorm, LayerNorm, softmax, --elementwise, --image.\n"
+     "                             NOT in it: --gn-fusion, --tile-variants, --ups-fold full, the rest of --patch-wide, --attn, --attn512"},
+    {"--bench", nullptr, CASES(print_device(); run_default_cases()), bench_unet_list, "the default run, then the UNet-shaped GEMM / attention / GroupNorm timings"},
+    {"--only-bench", nullptr, nullptr, [](int n, char** a) { print_device(); return bench_unet_list(n, a); }, "those timings alone"},
+    {"--gn-fusion", "--r5", CASES(run_gn_fusion_cases()), nullptr, "GroupNorm fused into the split-K reduction (and its declined request), res_rows, GroupNorm from producer statistics"},
+    {"--tile-variants", "--gemm-new", CASES(run_tile_variant_cases()), nullptr, "8-wave small tiles, 3-stage rings, the GEGLU tile; K-tile-contiguous weights under every tile code"},
+    {"--patch-wide", nullptr, CASES(run_patch_wide_cases()), nullptr, "3x3 patch kernels on 48- / 96-wide images (2-D output tiles)"},
+    {"--ups-fold", nullptr, [](int n, char** a) { run_ups_fold_mode(n > 0 && !strcmp(a[0], "full")); }, nullptr,
+     "[full]  upsample convolution as four 2x2-tap phase convolutions; full: also the two large C2 shapes"},
+    {"--narrow", nullptr, CASES(run_narrow_mode()), nullptr, "conv3x3_narrow_kernel (N <= 16): cases and timings of the pipeline's shapes"},
+    {"--ln", nullptr, CASES(run_ln_fold_suite()), nullptr, "LayerNorm folded into the GEMM, add_rowvec + row statistics"},
+    {"--attn", nullptr, CASES(run_attn_cases()), nullptr, "attention, d = 40 ... 160 (run once per PFD_ATTN* test hook)"},
+    {"--attn512", nullptr, CASES(run_attn512_cases()), nullptr, "VAE mid-block attention (d = 512, one head): cases and timings"},
+    {"--image", nullptr, CASES(run_image()), nullptr, "the uint8 picture ingest"},
+    {"--elementwise", nullptr, CASES(run_elementwise()), nullptr, "boundary / elementwise kernels, the seeded noise among them"},
+    {"--bench-attn", nullptr, nullptr, bench_attn_list, "attention timings"},
+    {"--bench-gn", nullptr, nullptr, bench_gn_list, "GroupNorm / LayerNorm timings"},
+    {"--bench-patch", nullptr, nullptr, bench_patch, "one 3x3 convolution per image width the patch kernel serves"},
+    {"--bench-gn-conv", nullptr, nullptr, bench_gn_conv_list, "GroupNorm + conv as two launches vs table + prologue"},
+    {"--launch-floor", nullptr, nullptr, bench_launch_floor, "per-launch cost of the runtime, in-stream and as a hipGraph"},
+    {"--replay", nullptr, nullptr, [](int n, char** a) { return n > 0 ? replay(a[0], false, 0) : 2; },
+     "<file>  relaunch a recorded GEMM / conv launch list (switches: PFD_REPLAY_DET, PFD_REPLAY_LN, PFD_REPLAY_TILED = 1)"},
+    {"--replay-time", nullptr, nullptr, [](int n, char** a) { return n > 0 ? replay(a[0], true, n > 1 ? atoi(a[1]) : 0) : 2; },
+     "<file> [tile]  the same with cold weights and a per-problem time table (PFD_REPLAY_WARM=1: warm weights)"},
+};
 
-    // wide-tile LDS-DMA kernel (N % 160 == 0): variants 256x160 / 128x160 / 64x160, split-K, conv gather
-    for (int v : {0, 5400, 3400, 3200}) {
-      run_gemm_case({300, 320, 192, PFD_ACT_SILU, true, true, true, false, v});
-      run_gemm_case({77, 160, 64, 0, true, false, false, false, v, 8});
-      GemmCase c{0, 320, 0, 0, true, true, true, false, v, 0, 3, 1, 1, 0, 2, 9, 7, 64};
-      run_gemm_case(c);
-    }
-    // patch conv kernel: W in {16,32,64}, whole image rows per tile, halo zero padding, split over channel blocks
-    run_gemm_case({0, 160, 0, PFD_ACT_SILU, true, true, true, false, 10900, 0, 3, 1, 1, 0, 2, 16, 16, 64});
-    run_gemm_case({0, 320, 0, 0, true, true, false, false, 10900, 0, 3, 1, 1, 0, 1, 32, 32, 128});
-    run_gemm_case({0, 160, 0, 0, true, false, true, false, 10902, 0, 3, 1, 1, 0, 1, 64, 64, 128});
-    run_gemm_case({0, 320, 0, 0, true, false, false, false, 0, 0, 3, 1, 1, 0, 3, 16, 16, 192});
-    run_gemm_case({520, 160, 1024, PFD_ACT_GELU, true, true, true, false, 3204});   // 64x160 tiles, split-K 4
-    run_gemm_case({130, 320, 2048, 0, true, true, false, false, 5403});             // 256x160, split-K 3
-    run_gemm_case({200, 320, 128, PFD_ACT_GEGLU, true, false, false, false, 0});     // GEGLU, 40-row packing
-    // 128-wide tiles of the wide kernel (N % 128 == 0, N % 160 != 0: VAE / Swin / SeeCoder widths)
-    run_gemm_case({300, 256, 192, PFD_ACT_SILU, true, true, true, false, 5400});
-    run_gemm_case({77, 128, 64, 0, true, false, false, false, 3400, 8});
-    run_gemm_case({130, 384, 320, PFD_ACT_GELU, true, true, false, false, 3200});
-    run_gemm_case({520, 256, 2048, 0, true, true, false, false, 3404});
-    run_gemm_case({0, 256, 0, PFD_ACT_SILU, true, true, true, false, 0, 0, 3, 1, 1, 0, 2, 9, 7, 128});
-    run_gemm_case({0, 128, 0, 0, true, false, false, false, 5400, 0, 3, 1, 1, 1, 1, 5, 6, 128});   // upsample
-    run_gemm_case({0, 512, 0, 0, true, false, false, false, 0, 0, 3, 2, 0, 0, 1, 9, 9, 64});       // stride 2, pad 0
-    {
-      GemmCase t{200, 384, 128, 0, true, false, false, false, 0}; t.n_split = 256; run_gemm_case(t);
-    }
-    // transposed tail (fused q|k|v projection): all three tile heights, ragged M, bias
-    {
-      GemmCase t{520, 480, 128, 0, false, false, false, false, 0}; t.n_split = 320; run_gemm_case(t);
-      GemmCase u{301, 320, 192, 0, true, false, false, false, 5400}; u.n_split = 160; run_gemm_case(u);
-      GemmCase v{77, 960, 320, 0, false, false, false, false, 3400}; v.n_split = 640; run_gemm_case(v);
-      GemmCase w{130, 480, 64, 0, true, false, false, false, 3200}; w.n_split = 320; run_gemm_case(w);
-    }
-    // deep operand rings (counted vmcnt + raw barrier): K shorter than, equal to and longer than the ring, split-K, conv
-    run_gemm_case({130, 320, 128, 0, true, true, false, false, 3300});
-    run_gemm_case({300, 160, 256, PFD_ACT_GELU, true, true, true, false, 3500});
-    run_gemm_case({300, 320, 1024, 0, true, true, true, false, 3300});
-    run_gemm_case({77, 160, 1344, 0, true, false, false, false, 3500});
-    run_gemm_case({520, 320, 2048, 0, true, true, false, false, 3304});
-    run_gemm_case({130, 160, 1536, 0, true, false, false, false, 3503});
-    run_gemm_case({0, 320, 0, 0, true, true, false, false, 3302, 0, 3, 1, 1, 0, 2, 8, 8, 256});
-    run_gemm_case({0, 160, 0, PFD_ACT_SILU, true, false, true, false, 3500, 0, 3, 2, 1, 0, 2, 10, 8, 128});
-    // wave-specialised forms: 256-row tile with loader waves (48), patch kernel with loader waves (98) / without (99)
-    run_gemm_case({300, 320, 1024, 0, true, true, true, false, 5800});
-    run_gemm_case({0, 320, 0, 0, true, true, false, false, 5800, 0, 3, 1, 1, 0, 2, 8, 8, 256});
-    run_gemm_case({0, 160, 0, PFD_ACT_SILU, true, false, true, false, 5800, 0, 3, 2, 1, 0, 2, 10, 8, 128});
-    run_gemm_case({0, 320, 0, 0, true, true, false, false, 10800, 0, 3, 1, 1, 0, 1, 32, 32, 128});
-    run_gemm_case({0, 160, 0, 0, true, false, true, false, 10802, 0, 3, 1, 1, 0, 1, 64, 64, 128});
-    // round 3: rotated K walk (several M tiles, K tiles >= M tiles and < M tiles, split-K, conv wrap-around) and the
-    // loader-wave kernels (5800 / 5700 = 256-row tile, 10800 / 10600 = patch kernel with two / three weight stages)
-    for (int v : {5800, 5700}) {   // 58 = two operand stages, 57 = the 3-stage ring (the default)
-      run_gemm_case({1100, 320, 1024, 0, true, true, true, false, v});
-      run_gemm_case({700, 640, 192, PFD_ACT_GELU, true, false, true, false, v});
-      run_gemm_case({600, 320, 2048, 0, true, true, false, false, v + 2});                       // split-K 2
-      run_gemm_case({0, 320, 0, 0, true, true, false, false, v, 0, 3, 1, 1, 0, 3, 16, 16, 128});   // conv, 3 M tiles
-      run_gemm_case({0, 160, 0, PFD_ACT_SILU, true, false, true, false, v, 0, 3, 2, 1, 0, 5, 20, 16, 64});  // stride 2
-      run_gemm_case({0, 160, 0, 0, true, false, false, false, v, 0, 3, 1, 1, 1, 2, 9, 12, 64});   // upsample
-      run_gemm_case({600, 256, 512, 0, true, true, false, false, v});                            // 128-wide tiles
-    }
-    for (int v : {10800, 10600}) {
-      run_gemm_case({0, 320, 0, 0, true, true, true, false, v, 0, 3, 1, 1, 0, 2, 32, 32, 128});
-      run_gemm_case({0, 160, 0, PFD_ACT_SILU, true, false, true, false, v, 0, 3, 1, 1, 0, 1, 64, 64, 256});
-      run_gemm_case({0, 320, 0, 0, true, true, false, false, v, 0, 3, 1, 1, 0, 3, 16, 16, 320});
-      run_gemm_case({0, 160, 0, 0, true, false, false, false, v + 2, 0, 3, 1, 1, 0, 2, 16, 16, 512});  // split over cb
-    }
-    run_gemm_case({600, 640, 320, PFD_ACT_GEGLU, true, false, false, false, 9400});   // 256 x 320 GEGLU tile
-    run_gemm_case({300, 320, 64, PFD_ACT_GEGLU, false, false, false, false, 9400});
-    for (int v : {3200, 3300, 3400, 3500, 5400, 5100, 5300, 9200, 9300}) {   // rotated walk over several M tiles; 8-wave small tiles
-      run_gemm_case({1100, 320, 1024, 0, true, true, true, false, v});
-      run_gemm_case({0, 160, 0, 0, true, true, false, false, v, 0, 3, 1, 1, 0, 3, 16, 16, 128});
-      run_gemm_case({900, 320, 1536, 0, true, false, false, false, v + 3});
-    }
-    // GroupNorm(+SiLU) prologue of the patch kernel == pfd_groupnorm_f16 followed by the plain convolution, bit for bit
-    run_gn_conv_case(2, 16, 16, 64, 0, 160, PFD_ACT_SILU, false);
-    run_gn_conv_case(1, 32, 32, 128, 64, 320, PFD_ACT_SILU, true);
-    run_gn_conv_case(2, 64, 64, 64, 128, 160, PFD_ACT_NONE, true);
-    run_gn_conv_case(3, 32, 32, 320, 0, 320, PFD_ACT_SILU, true);
-    run_gemm_case({0, 160, 0, PFD_ACT_SILU, true, false, false, false, 0, 0, 3, 2, 1, 0, 2, 10, 8, 128});  // stride 2
-    run_gemm_case({0, 160, 0, 0, true, true, false, false, 3402, 0, 3, 1, 1, 1, 1, 5, 6, 128});           // upsample + split
-    run_gemm_case({0, 320, 0, 0, true, false, false, false, 0, 8, 3, 2, 0, 0, 1, 9, 9, 64});               // pad 0, ld+8
-    run_gemm_case({0, 160, 0, 0, true, false, false, false, 0, 0, 1, 1, 0, 0, 2, 6, 6, 128});              // 1x1 as conv
-    run_ups_fold_cases();
-    run_narrow_conv_cases();
-
-    run_gemm_case({0, 160, 0, PFD_ACT_SILU, true, true, true, false, 0, 0, 3, 1, 1, 0, 1, 16, 48, 128});   // patch kernel, 2-D tiles
-    run_gemm_case({0, 320, 0, 0, true, true, true, false, 0, 0, 3, 1, 1, 0, 2, 8, 96, 64});
-    run_ln_fold_suite();
-    run_attn_case(2, 2, 128, 128, 40, true);
-    run_attn_case(1, 2, 300, 148, 40, false);    // ragged queries and keys (2 full tiles + 20 keys)
-    run_attn_case(2, 2, 512, 256, 40, true);     // full tiles only
-    run_attn_case(1, 1, 256, 40, 40, false);     // a single ragged tile
-    run_attn_case(1, 2, 520, 1000, 40, false);   // 15 full tiles + 40 keys
-    run_attn_case(1, 2, 77, 64, 40, true);       // exactly one full tile
-    run_attn_case(1, 2, 200, 148, 40, false);
-    run_attn_case(2, 2, 64, 64, 80, true);
-    run_attn_case(1, 2, 144, 256, 96, false);
-    run_attn_case(1, 3, 148, 148, 96, false);
-    run_attn_case(2, 2, 64, 148, 160, false);
-    run_attn_case(1, 1, 256, 320, 160, true);
-    run_attn_case(2, 1, 256, 256, 512, false);   // VAE mid-block attention (attention512_kernel)
-    run_attn_case(1, 1, 200, 96, 512, false);
-
-    run_swin_case(1, 14, 17, 2, 0);
-    run_swin_case(1, 14, 17, 2, 6);
-    run_swin_case(2, 24, 24, 1, 6);
-    run_swin_case(1, 8, 8, 3, 6);
-
-    run_gn_case(2, 64, 320, 0, 32, PFD_ACT_SILU, 1e-5f);
-    run_gn_case(2, 100, 64, 32, 32, PFD_ACT_NONE, 1e-6f);   // groups straddle the concat seam
-    run_gn_case(1, 50, 1280, 1280, 32, PFD_ACT_SILU, 1e-5f);  // two vec slots per thread
-    run_gn_case(2, 1024, 128, 0, 32, PFD_ACT_SILU, 1e-6f);
-    run_gn_case(1, 16, 1920, 0, 32, PFD_ACT_SILU, 1e-5f);
-    // single-launch small-slab form ((C/G) % 4 == 0, slab <= 32 K elements, >= 128 blocks)
-    run_gn_case(4, 64, 1280, 0, 32, PFD_ACT_SILU, 1e-5f);
-    run_gn_case(4, 256, 1280, 1280, 32, PFD_ACT_SILU, 1e-5f);
-    run_gn_case(8, 128, 1024, 0, 32, PFD_ACT_NONE, 1e-6f);
-    run_gn_case(4, 100, 1280, 640, 32, PFD_ACT_SILU, 1e-5f);   // cpg 60: groups straddle the seam
-
-    run_ln_case(37, 320, 0, 0, 0, 0);
-    run_ln_case(10, 1280, 0, 0, 0, 0);
-    run_ln_case(5, 3072, 0, 0, 0, 0);
-    run_ln_case(2 * 4 * 3, 4 * 96, 1, 2, 7, 5);
-    run_ln_case(8195, 320, 0, 0, 0, 0);    // multi-row form (M >= 8192), ragged last wave
-    run_ln_case(8192, 640, 0, 0, 0, 0);
-    run_ln_case(8193, 1280, 0, 0, 0, 0);
-    run_softmax_case(5, 4096, 0.044f);
-    run_softmax_case(3, 1152, 0.1f);
-    run_softmax_case(2, 36864, 0.044f);   // long-row form (N > 16384)
-    run_softmax_case(2, 16392, 0.05f);
-    run_elementwise();
-    run_image();
-    printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
-  }
-
-  if (bench || only_bench) {
-    // UNet-shaped problems at C2 (UNet batch 8)
-    for (int t : {5400, 10900, 5400, 10900}) {   // gather conv vs patch conv
-      bench_gemm("PATCH conv3x3 320->320 @64^2", 0, 320, 0, 3, 8, 64, 320, t);
-      bench_gemm("PATCH conv3x3 960->320 @64^2", 0, 320, 0, 3, 8, 64, 960, t);
-      bench_gemm("PATCH conv3x3 640->640 @32^2", 0, 640, 0, 3, 8, 32, 640, t == 5400 ? 5402 : t);
-      bench_gemm("PATCH conv3x3 1280->1280 @16^2", 0, 1280, 0, 3, 8, 16, 1280, t == 5400 ? 3404 : t);
-    }
-    for (int rep = 0; rep < 1; ++rep)
-      for (int t : {5400, 3400}) {
-        bench_gemm("conv3x3 320->320 @64^2", 0, 320, 0, 3, 8, 64, 320, t);
-        bench_gemm("linear qkv 320->960 @64^2", 32768, 960, 320, 0, 0, 0, 0, t);
-        bench_gemm("linear 1280->320 @64^2", 32768, 320, 1280, 0, 0, 0, 0, t);
-        bench_gemm("conv3x3 640->640 @32^2", 0, 640, 0, 3, 8, 32, 640, t);
+int main(int argc, char** argv) {
+  const char* flag = argc > 1 ? argv[1] : "";
+  for (const Mode& m : kModes)
+    if (!strcmp(flag, m.flag) || (m.alias && !strcmp(flag, m.alias))) {
+      if (m.cases) {
+        m.cases(argc - 2, argv + 2);
+        printf("SELFTEST %d/%d passed, %d failed\n", g_total - g_fail, g_total, g_fail);
       }
-    for (int t : {5400, 5402, 5403, 3402, 0}) bench_gemm("conv3x3 640->640 @32^2", 0, 640, 0, 3, 8, 32, 640, t);
-    for (int t : {5400, 5402, 0}) bench_gemm("conv3x3 1920->640 @32^2", 0, 640, 0, 3, 8, 32, 1920, t);
-    for (int t : {3400, 3200, 3402, 3404, 3202, 0}) bench_gemm("conv3x3 1280->1280 @16^2", 0, 1280, 0, 3, 8, 16, 1280, t);
-    for (int t : {3200, 3204, 3208, 3404, 3408, 0}) bench_gemm("conv3x3 1280->1280 @8^2", 0, 1280, 0, 3, 8, 8, 1280, t);
-    for (int t : {5400, 3400, 0}) bench_gemm("linear qkv 320->960 @64^2", 32768, 960, 320, 0, 0, 0, 0, t);
-    for (int t : {5400, 3400, 0}) bench_gemm("linear 1280->320 @64^2", 32768, 320, 1280, 0, 0, 0, 0, t);
-    for (int t : {5400, 3400, 0}) bench_gemm("linear 320->2560 @64^2", 32768, 2560, 320, 0, 0, 0, 0, t);
-    for (int t : {5400, 3400, 3200, 0}) bench_gemm("linear 1280->10240 @16^2", 2048, 10240, 1280, 0, 0, 0, 0, t);
-    bench_gemm("square-ish 8192x5120x4096", 8192, 5120, 4096, 0, 0, 0, 0, 5400);
-    for (int t : {22, 21}) {
-      bench_gemm("conv3x3 640->640 @32^2", 0, 640, 0, 3, 8, 32, 640, t);
-      bench_gemm("conv3x3 1280->1280 @16^2", 0, 1280, 0, 3, 8, 16, 1280, t);
+      return g_fail + (m.tool ? m.tool(argc - 2, argv + 2) : 0);
     }
-    for (int t : {22, 21, 12, 11}) bench_gemm("conv3x3 1280->1280 @8^2", 0, 1280, 0, 3, 8, 8, 1280, t);
-    bench_gemm("conv3x3 2560->1280 @16^2", 0, 1280, 0, 3, 8, 16, 2560, 0);
-    bench_gemm("conv3x3 960->320 @64^2", 0, 320, 0, 3, 8, 64, 960, 0);
-    bench_gemm("linear qk 320->640 @64^2", 32768, 640, 320, 0, 0, 0, 0, 0);
-    bench_gemm("linear geglu-in 320->2560", 32768, 2560, 320, 0, 0, 0, 0, 0);
-    bench_gemm("linear ff-out 1280->320", 32768, 320, 1280, 0, 0, 0, 0, 0);
-    bench_gemm("linear 640->5120 @32^2", 8192, 5120, 640, 0, 0, 0, 0, 0);
-    bench_gemm("linear 1280->10240 @16^2", 2048, 10240, 1280, 0, 0, 0, 0, 0);
-    bench_gemm("vae conv3x3 128->128 @512^2 (B1)", 0, 128, 0, 3, 1, 512, 128, 0);
-    bench_gemm("vae conv3x3 512->512 @64^2 (B4)", 0, 512, 0, 3, 4, 64, 512, 0);
-    bench_gemm("square 4096^3", 4096, 4096, 4096, 0, 0, 0, 0, 22);
-    bench_attn("self-attn 64^2 d40", 8, 8, 4096, 4096, 40);
-    bench_attn("self-attn 32^2 d80", 8, 8, 1024, 1024, 80);
-    bench_attn("self-attn 16^2 d160", 8, 8, 256, 256, 160);
-    bench_attn("cross-attn 64^2 d40", 8, 8, 4096, 148, 40);
-    bench_attn("seecoder cross d96", 1, 8, 144, 4096, 96);
-    bench_gn("groupnorm+silu 320 @64^2", 8, 4096, 320);
-    bench_gn("groupnorm+silu 1280 @16^2", 8, 256, 1280);
-    bench_gn("groupnorm+silu 128 @512^2", 4, 262144, 128);
-  }
-  return g_fail;
+  printf("usage: selftest [mode]     exit status = number of failed cases\n");
+  for (const Mode& m : kModes) printf("  %-15s %-10s  %s\n", m.flag[0] ? m.flag : "(no mode)", m.alias ? m.alias : "", m.help);
+  return strcmp(flag, "--help") ? 2 : 0;
 }

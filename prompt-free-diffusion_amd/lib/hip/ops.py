@@ -67,7 +67,7 @@ LN_FOLD = True
 
 
 # One record per GEMM / conv launch: THE field list of profiles/unet_c2_gemm_shapes.txt.  The writer below, the readers in
-# tests/test_hip_kernels_fullsize.py (parse_launch_records) and csrc/selftest.cpp (--replay: 19, 22 or 24 integers per line) follow
+# tests/test_hip_kernels_fullsize.py (parse_launch_records) and csrc/selftest_replay.cpp (--replay: 19, 22 or 24 integers per line) follow
 # it; tests/test_host.py parses the tracked file with it on CPU, so a regenerated file cannot break a GPU-only test unseen.
 TRACE_FIELDS = ("M", "N", "K", "act", "has_bias", "has_rowvec", "has_res", "bias_per_row",
                 "ksize", "stride", "pad", "ups", "B", "H", "W", "Cin", "Ho", "Wo", "rows_per_rv",
