@@ -400,6 +400,17 @@ int pfd_philox_normal_f32(const int64_t* key, int32_t step, float* out, int32_t 
 int pfd_cfg_ddim_step_rng(const void* eps, int32_t nb, const float* x, const int64_t* key, int32_t step,
                           float noise_mul, const float* coef, float* x_prev, float* pred_x0, void* xin_next,
                           int32_t rep, int32_t B, int32_t C, int32_t h, int32_t w, pfd_stream_t stream);
+/* pfd_cfg_ddim_step / pfd_cfg_ddim_step_rng with one guidance scale PER SAMPLE: scale, device fp32 [B], takes the
+ * place of coef[4] (which is ignored) -- e = e_u + scale[b]*(e_c - e_u), or e = scale[b]*eps at nb = 1; the rest of the
+ * arithmetic is the two kernels' own, in their order.  The reference's combine (ddim.py:145-152) has one scale because
+ * one `sample()` call is one request; a batch coalesced from several requests has one per request.  Noise: key (device
+ * int64 [B, 2], with step and noise_mul as in pfd_cfg_ddim_step_rng) or noise (fp32 NCHW tensor) or neither; both is
+ * PFD_EINVAL, as is scale == NULL.  Sample b's outputs are a function of sample b's inputs only (eps, x, noise or key
+ * row, scale[b]).  Every other operand as in pfd_cfg_ddim_step. */
+int pfd_cfg_ddim_step_ps(const void* eps, int32_t nb, const float* x, const float* noise, const int64_t* key,
+                         int32_t step, float noise_mul, const float* coef, const float* scale, float* x_prev,
+                         float* pred_x0, void* xin_next, int32_t rep, int32_t B, int32_t C, int32_t h, int32_t w,
+                         pfd_stream_t stream);
 /* y = a + b (f16, fp32 add), n elements; b may be NULL (copy). */
 int pfd_add_f16(const void* a, const void* b, void* y, int64_t n, pfd_stream_t stream);
 /* y = alpha*a + beta*b (f16 storage, fp32 math), n elements; b may be NULL (y = alpha*a).  The

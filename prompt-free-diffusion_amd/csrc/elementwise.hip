@@ -89,12 +89,16 @@ __global__ void timestep_embedding_kernel(const int64_t* __restrict__ t, half_t*
   out[i] = (half_t)v;
 }
 
+// PS (per-sample guidance scale, pfd_cfg_ddim_step_ps): scale_ps[b] in place of coef[4]; nothing else differs, and the
+// PS = false instantiation never reads scale_ps.
+template <bool PS>
 __global__ void cfg_ddim_kernel(const half_t* __restrict__ eps, int nb, const float* __restrict__ x,
                                 const float* __restrict__ noise, const float* __restrict__ coef,
                                 float* __restrict__ x_prev, float* __restrict__ pred_x0,
-                                half_t* __restrict__ xin_next, int rep, int B, int C, int h, int w) {
+                                half_t* __restrict__ xin_next, int rep, int B, int C, int h, int w,
+                                const float* __restrict__ scale_ps) {
   const long n = (long)B * C * h * w;
-  const float a_t = coef[0], a_prev = coef[1], sigma = coef[2], s1mat = coef[3], scale = coef[4];
+  const float a_t = coef[0], a_prev = coef[1], sigma = coef[2], s1mat = coef[3], scale_all = PS ? 0.f : coef[4];
   const float isq_at = 1.0f / sqrtf(a_t);
   const float sq_aprev = sqrtf(a_prev);
   const float dir = sqrtf(fmaxf(1.0f - a_prev - sigma * sigma, 0.f));
@@ -107,6 +111,7 @@ __global__ void cfg_ddim_kernel(const half_t* __restrict__ eps, int nb, const fl
     const int c = (int)(t % C);
     const int b = (int)(t / C);
     const long ei = (((long)b * h + yh) * w + xw) * C + c;  // NHWC
+    const float scale = PS ? scale_ps[b] : scale_all;
     float e;
     if (nb == 2) {
       const float eu = (float)eps[ei];
@@ -153,18 +158,19 @@ __global__ void philox_normal_kernel(const int64_t* __restrict__ key, int step, 
 
 // cfg_ddim_kernel with the noise evaluated in place: thread = four consecutive NCHW elements of ONE sample = one Philox
 // call.  VEC (w % 4 == 0, 16-byte aligned x / x_prev / pred_x0): the four share a row, 16-byte accesses; otherwise the
-// scalar path computes the same values.  After `nz` the arithmetic is cfg_ddim_kernel's, in its order.
-template <bool VEC>
+// scalar path computes the same values.  After `nz` the arithmetic is cfg_ddim_kernel's, in its order.  PS as there: the
+// four elements of a thread belong to one sample, so scale_ps[b] is read once per quad.
+template <bool VEC, bool PS>
 __global__ void cfg_ddim_rng_kernel(const half_t* __restrict__ eps, int nb, const float* __restrict__ x,
                                     const int64_t* __restrict__ key, int step, float noise_mul,
                                     const float* __restrict__ coef, float* __restrict__ x_prev,
                                     float* __restrict__ pred_x0, half_t* __restrict__ xin_next, int rep, int B, int C,
-                                    int h, int w) {
+                                    int h, int w, const float* __restrict__ scale_ps) {
   const long ns = (long)C * h * w;
   const long n = (long)B * ns;
   const long nq = (ns + 3) >> 2;
   const long total = (long)B * nq;
-  const float a_t = coef[0], a_prev = coef[1], sigma = coef[2], s1mat = coef[3], scale = coef[4];
+  const float a_t = coef[0], a_prev = coef[1], sigma = coef[2], s1mat = coef[3], scale_all = PS ? 0.f : coef[4];
   const float isq_at = 1.0f / sqrtf(a_t);
   const float sq_aprev = sqrtf(a_prev);
   const float dir = sqrtf(fmaxf(1.0f - a_prev - sigma * sigma, 0.f));
@@ -173,6 +179,7 @@ __global__ void cfg_ddim_rng_kernel(const half_t* __restrict__ eps, int nb, cons
     const long q = i - (long)b * nq;
     const long e0 = q * 4;
     const long base = (long)b * ns + e0;
+    const float scale = PS ? scale_ps[b] : scale_all;
     float z[4], xv[4], xp4[4], p04[4];
     pfd_philox_normal4(key[2 * b], key[2 * b + 1], step, (uint32_t)q, z);
     if (VEC) {
@@ -395,8 +402,9 @@ extern "C" int pfd_cfg_ddim_step(const void* eps, int32_t nb, const float* x, co
   if (nb < 1 || nb > 2 || B <= 0 || C <= 0 || h <= 0 || w <= 0 || (xin_next && (rep < 1 || rep > 2))) return PFD_EINVAL;
   const long n = (long)B * C * h * w;
   PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
-  hipLaunchKernelGGL(cfg_ddim_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const half_t*)eps, nb, x, noise, coef, x_prev, pred_x0, (half_t*)xin_next, rep, B, C, h, w);
+  hipLaunchKernelGGL(cfg_ddim_kernel<false>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const half_t*)eps, nb, x, noise, coef, x_prev, pred_x0, (half_t*)xin_next, rep, B, C, h, w,
+                     (const float*)nullptr);
   return pfd_check_launch("pfd_cfg_ddim_step");
 }
 
@@ -428,14 +436,43 @@ extern "C" int pfd_cfg_ddim_step_rng(const void* eps, int32_t nb, const float* x
                                   reinterpret_cast<uintptr_t>(pred_x0)) & 15);
   PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
   if (vec)
-    hipLaunchKernelGGL(cfg_ddim_rng_kernel<true>, dim3(grid_for((long)B * nq, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)eps, nb, x, key, step, noise_mul, coef, x_prev, pred_x0, (half_t*)xin_next, rep,
-                       B, C, h, w);
-  else
-    hipLaunchKernelGGL(cfg_ddim_rng_kernel<false>, dim3(grid_for((long)B * nq, 256)), dim3(256), 0,
+    hipLaunchKernelGGL((cfg_ddim_rng_kernel<true, false>), dim3(grid_for((long)B * nq, 256)), dim3(256), 0,
                        (hipStream_t)stream, (const half_t*)eps, nb, x, key, step, noise_mul, coef, x_prev, pred_x0,
-                       (half_t*)xin_next, rep, B, C, h, w);
+                       (half_t*)xin_next, rep, B, C, h, w, (const float*)nullptr);
+  else
+    hipLaunchKernelGGL((cfg_ddim_rng_kernel<false, false>), dim3(grid_for((long)B * nq, 256)), dim3(256), 0,
+                       (hipStream_t)stream, (const half_t*)eps, nb, x, key, step, noise_mul, coef, x_prev, pred_x0,
+                       (half_t*)xin_next, rep, B, C, h, w, (const float*)nullptr);
   return pfd_check_launch("pfd_cfg_ddim_step_rng");
+}
+
+extern "C" int pfd_cfg_ddim_step_ps(const void* eps, int32_t nb, const float* x, const float* noise, const int64_t* key,
+                                    int32_t step, float noise_mul, const float* coef, const float* scale,
+                                    float* x_prev, float* pred_x0, void* xin_next, int32_t rep, int32_t B, int32_t C,
+                                    int32_t h, int32_t w, pfd_stream_t stream) {
+  if (!eps || !x || !coef || !scale || !x_prev || !pred_x0 || (noise && key) || (key && step < 0)) return PFD_EINVAL;
+  if (nb < 1 || nb > 2 || B <= 0 || C <= 0 || h <= 0 || w <= 0 || (xin_next && (rep < 1 || rep > 2))) return PFD_EINVAL;
+  const long ns = (long)C * h * w;
+  if (key && ns > ((long)1 << 34)) return PFD_ESHAPE;
+  PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
+  if (!key) {
+    hipLaunchKernelGGL(cfg_ddim_kernel<true>, dim3(grid_for((long)B * ns, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)eps, nb, x, noise, coef, x_prev, pred_x0, (half_t*)xin_next, rep, B, C, h, w,
+                       scale);
+    return pfd_check_launch("pfd_cfg_ddim_step_ps");
+  }
+  const long nq = (ns + 3) >> 2;
+  const bool vec = !(w & 3) && !((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_prev) |
+                                  reinterpret_cast<uintptr_t>(pred_x0)) & 15);
+  if (vec)
+    hipLaunchKernelGGL((cfg_ddim_rng_kernel<true, true>), dim3(grid_for((long)B * nq, 256)), dim3(256), 0,
+                       (hipStream_t)stream, (const half_t*)eps, nb, x, key, step, noise_mul, coef, x_prev, pred_x0,
+                       (half_t*)xin_next, rep, B, C, h, w, scale);
+  else
+    hipLaunchKernelGGL((cfg_ddim_rng_kernel<false, true>), dim3(grid_for((long)B * nq, 256)), dim3(256), 0,
+                       (hipStream_t)stream, (const half_t*)eps, nb, x, key, step, noise_mul, coef, x_prev, pred_x0,
+                       (half_t*)xin_next, rep, B, C, h, w, scale);
+  return pfd_check_launch("pfd_cfg_ddim_step_ps");
 }
 
 extern "C" int pfd_add_f16(const void* a, const void* b, void* y, int64_t n, pfd_stream_t stream) {

@@ -818,6 +818,77 @@ static void run_softmax_case(int R, int N, float scale) {
 }
 
 // ------------------------------------------------------------------ elementwise
+// Philox4x32-10 + Box-Muller on the host in fp64: the specification of include/pfd_hip.h (pfd_philox_normal_f32)
+static void host_philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+    c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+}
+static double host_normal(int64_t seed, int64_t sid, int step, long e) {
+  uint32_t c[4] = {(uint32_t)(e >> 2), (uint32_t)step, (uint32_t)((uint64_t)sid & 0xffffffffu), 0u};
+  host_philox(c, (uint32_t)((uint64_t)seed & 0xffffffffu), (uint32_t)((uint64_t)seed >> 32));
+  const int j = (int)(e & 3);
+  const double u = ((c[j & 2] >> 8) + 1) * ldexp(1.0, -24), v = (c[(j & 2) + 1] >> 8) * ldexp(1.0, -24);
+  const double rad = sqrt(-2.0 * log(u)), ang = 2.0 * 3.14159265358979323846 * v;
+  return rad * ((j & 1) ? sin(ang) : cos(ang));
+}
+
+// pfd_cfg_ddim_step_ps (one guidance scale per sample) against the closed formula in fp64.  noise_mode 0: none, 1: a noise
+// tensor, 2: the key (step 7, noise_mul 0.5).  coef[4] is set to a value no sample uses: it must be ignored.
+static void run_cfg_ddim_ps_case(int B, int C, int h, int w, int nb, int rep, int noise_mode) {
+  const long ns = (long)C * h * w;
+  const size_t n = (size_t)B * ns;
+  const float scales[3] = {1.5f, 2.0f, 7.25f};
+  auto eps = rand_h((size_t)nb * n, 1.5f);
+  auto x = rand_f(n, 2.f), nz = rand_f(n, 1.f);
+  std::vector<float> coef = {0.45f, 0.52f, 0.1f, sqrtf(1 - 0.45f), -99.f}, sc(scales, scales + B);
+  std::vector<int64_t> key = {-1, 3, (1ll << 40) + 12345, 7, 20, 1};
+  Dev<h16> de(eps), dxin((size_t)rep * n);
+  Dev<float> dx(x), dn(nz), dc(coef), ds(sc), dxp(n), dp0(n);
+  Dev<int64_t> dk(key);
+  const int rc = pfd_cfg_ddim_step_ps(de.p, nb, dx.p, noise_mode == 1 ? dn.p : nullptr, noise_mode == 2 ? dk.p : nullptr, 7,
+                                      0.5f, dc.p, ds.p, dxp.p, dp0.p, dxin.p, rep, B, C, h, w, nullptr);
+  const int rc_null = pfd_cfg_ddim_step_ps(de.p, nb, dx.p, nullptr, nullptr, 7, 0.5f, dc.p, nullptr, dxp.p, dp0.p, dxin.p,
+                                           rep, B, C, h, w, nullptr);
+  const int rc_both = pfd_cfg_ddim_step_ps(de.p, nb, dx.p, dn.p, dk.p, 7, 0.5f, dc.p, ds.p, dxp.p, dp0.p, dxin.p, rep, B,
+                                           C, h, w, nullptr);
+  auto gxp = dxp.get(), gp0 = dp0.get();
+  auto gxin = dxin.get();
+  std::vector<double> rxp(n), rp0(n), rxin((size_t)rep * n);
+  for (int b = 0; b < B; ++b) for (int c = 0; c < C; ++c) for (int y = 0; y < h; ++y) for (int xx = 0; xx < w; ++xx) {
+    const long el = ((long)c * h + y) * w + xx;
+    const size_t i = (size_t)b * ns + el, ei = (((size_t)b * h + y) * w + xx) * C + c;
+    const double s = (double)scales[b];
+    const double e = nb == 2 ? (double)eps[ei] + s * ((double)eps[n + ei] - (double)eps[ei]) : (double)eps[ei] * s;
+    const double z = noise_mode == 1 ? (double)nz[i] : noise_mode == 2 ? 0.5 * host_normal(key[2 * b], key[2 * b + 1], 7, el) : 0.0;
+    const double p0 = (x[i] - sqrt(1 - 0.45) * e) / sqrt(0.45);
+    const double xp = sqrt(0.52) * p0 + sqrt(1 - 0.52 - 0.01) * e + 0.1 * z;
+    rxp[i] = xp; rp0[i] = p0;
+    for (int r = 0; r < rep; ++r) rxin[r * n + ei] = xp;
+  }
+  char tag[96];
+  snprintf(tag, sizeof tag, "cfg_ddim_ps B%d C%d %dx%d nb%d rep%d noise%d", B, C, h, w, nb, rep, noise_mode);
+  ++g_total;
+  if (rc_null != PFD_EINVAL || rc_both != PFD_EINVAL) {
+    ++g_fail;
+    printf("FAIL %-58s scale=NULL rc=%d, noise+key rc=%d\n", tag, rc_null, rc_both);
+  }
+  report(std::string(tag) + " x_prev rc=" + std::to_string(rc), gxp, rxp, 2e-5, 2e-5);
+  report(std::string(tag) + " pred_x0", gp0, rp0, 2e-5, 2e-5);
+  report(std::string(tag) + " xin_next", gxin, rxin, 3e-3, 2e-3);
+}
+
+static void run_cfg_ddim_ps_cases() {
+  const int shapes[3][4] = {{3, 4, 8, 8}, {2, 4, 5, 6}, {3, 3, 3, 3}};   // 16-byte path; w % 4 != 0; a sample's last quad has a tail
+  for (const auto& s : shapes)
+    for (int nb = 1; nb <= 2; ++nb)
+      for (int rep = 1; rep <= 2; ++rep)
+        for (int mode = 0; mode < 3; ++mode) run_cfg_ddim_ps_case(s[0], s[1], s[2], s[3], nb, rep, mode);
+}
+
 static void run_elementwise() {
   {  // layout conversions
     const int B = 2, C = 4, H = 9, W = 7, rep = 2;
@@ -895,22 +966,8 @@ static void run_elementwise() {
     report("cfg_ddim xin_next", gxin, rxin, 3e-3, 2e-3);
   }
   {  // seeded noise (Philox4x32-10 + Box-Muller, include/pfd_hip.h) alone and inside the cfg + ddim step; host reference = the specification in fp64
-    auto philox = [](uint32_t c[4], uint32_t k0, uint32_t k1) {
-      for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-      }
-    };
-    auto normal = [&](int64_t seed, int64_t sid, int step, long e) {
-      uint32_t c[4] = {(uint32_t)(e >> 2), (uint32_t)step, (uint32_t)((uint64_t)sid & 0xffffffffu), 0u};
-      philox(c, (uint32_t)((uint64_t)seed & 0xffffffffu), (uint32_t)((uint64_t)seed >> 32));
-      const int j = (int)(e & 3);
-      const double u = ((c[j & 2] >> 8) + 1) * ldexp(1.0, -24), v = (c[(j & 2) + 1] >> 8) * ldexp(1.0, -24);
-      const double rad = sqrt(-2.0 * log(u)), ang = 2.0 * 3.14159265358979323846 * v;
-      return rad * ((j & 1) ? sin(ang) : cos(ang));
-    };
+    auto philox = host_philox;
+    auto normal = host_normal;
     uint32_t kat[4] = {0x243f6a88u, 0x85a308d3u, 0x13198a2eu, 0x03707344u};
     philox(kat, 0xa4093822u, 0x299f31d0u);
     ++g_total;
@@ -958,6 +1015,7 @@ static void run_elementwise() {
       report(tag + " xin_next", gxin, rxin, 3e-3, 2e-3);
     }
   }
+  run_cfg_ddim_ps_cases();
   {  // add, add_rowvec
     const long n = 1003;
     auto a = rand_h(n + 5), b = rand_h(n + 5);

@@ -85,6 +85,8 @@ SIGNATURES = {
     "pfd_philox_normal_f32": (_i32, [_vp, _i32, _vp, _i32, _i64, _vp]),
     "pfd_cfg_ddim_step_rng": (_i32, [_vp, _i32, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32,
                                      _vp]),
+    "pfd_cfg_ddim_step_ps": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
+                                    _i32, _vp]),
     "pfd_add_f16": (_i32, [_vp, _vp, _vp, _i64, _vp]),
     "pfd_axpby_f16": (_i32, [_vp, _f32, _vp, _f32, _vp, _i64, _vp]),
     "pfd_add_rowvec_f16": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp]),

@@ -794,12 +794,26 @@ def philox_normal(key, step, n_per_sample):
     return out
 
 
-def cfg_ddim_step(eps, nb, x, coef, *, noise=None, want_next=True, rep=None, noise_key=None, step=None, noise_mul=1.0):
+def guidance_scale_rows(scale, B, device):
+    """the per-sample guidance scales of cfg_ddim_step, checked: a contiguous float32 tensor [B] on the GPU (the step
+    runs inside a captured loop, so nothing is converted or copied here: DDIMSampler moves the vector once per request)"""
+    if not (torch.is_tensor(scale) and scale.dtype == torch.float32 and tuple(scale.shape) == (B,) and
+            scale.is_contiguous()):
+        raise ValueError(f"a per-sample guidance scale must be a contiguous float32 tensor [{B}]")
+    if not scale.is_cuda or scale.device != torch.device(device):
+        raise ValueError(f"a per-sample guidance scale must live on {device}, next to x")
+    return scale
+
+
+def cfg_ddim_step(eps, nb, x, coef, *, noise=None, want_next=True, rep=None, noise_key=None, step=None, noise_mul=1.0,
+                  scale=None):
     """Fused CFG combine + DDIM update.  eps NHWC f16 [nb*B,h,w,C]; x NCHW fp32 [B,C,h,w];
     coef fp32[5] device.  Returns (x_prev fp32 NCHW, pred_x0 fp32 NCHW, xin_next f16 NHWC|None);
     xin_next holds `rep` copies of the batch (default nb: the CFG-doubled UNet input).
     noise: fp32 NCHW tensor added as sigma * noise, or -- noise_key int64 [B,2] (seed, sample_id), step, noise_mul --
-    the seeded noise sigma * noise_mul * z(key[b], step, element) evaluated inside the kernel (philox_normal)."""
+    the seeded noise sigma * noise_mul * z(key[b], step, element) evaluated inside the kernel (philox_normal).
+    scale: fp32 [B] tensor, the guidance scale of sample b in place of coef[4] (pfd_cfg_ddim_step_ps; with noise,
+    noise_key or neither).  None: coef[4] for the whole batch."""
     B, Cc, h, w = x.shape
     rep = nb if rep is None else rep
     if noise_key is not None:
@@ -808,9 +822,18 @@ def cfg_ddim_step(eps, nb, x, coef, *, noise=None, want_next=True, rep=None, noi
         if step is None:
             raise ValueError("cfg_ddim_step: noise_key needs the DDIM step index (step=)")
         noise_key = noise_key_rows(noise_key, B, x.device)
+    if scale is not None:
+        scale = guidance_scale_rows(scale, B, x.device)
     x_prev = torch.empty_like(x)
     pred_x0 = torch.empty_like(x)
     xin = torch.empty((rep * B, h, w, Cc), dtype=torch.float16, device=x.device) if want_next else None
+    if scale is not None:
+        rc = _lib().pfd_cfg_ddim_step_ps(eps.data_ptr(), nb, x.data_ptr(), _ptr(noise), _ptr(noise_key),
+                                         0 if step is None else int(step), float(noise_mul), coef.data_ptr(),
+                                         scale.data_ptr(), x_prev.data_ptr(), pred_x0.data_ptr(), _ptr(xin), rep, B, Cc,
+                                         h, w, _stream())
+        _b.check(rc, "pfd_cfg_ddim_step_ps")
+        return x_prev, pred_x0, xin
     if noise_key is not None:
         rc = _lib().pfd_cfg_ddim_step_rng(eps.data_ptr(), nb, x.data_ptr(), noise_key.data_ptr(), int(step),
                                           float(noise_mul), coef.data_ptr(), x_prev.data_ptr(), pred_x0.data_ptr(),

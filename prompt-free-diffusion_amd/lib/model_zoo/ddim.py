@@ -23,12 +23,38 @@ the per-step noise of eta > 0 (:166) a function of (key row, step index, element
 (pfd_cfg_ddim_step_rng, lib/noise.py) instead of a draw from the global generator: such a schedule is captured
 and replayed as a hipGraph like eta = 0, and a sample's result does not depend on the batch it rides in.
 Without the key every path is the reference's: `noise_like` from the global generator, eager launches.
+
+Per-sample guidance scale (opt-in): c_info['unconditional_guidance_scale'] may be a tensor or a sequence of `bs`
+numbers instead of one number.  Sample b is then combined with its own scale inside the step kernel
+(pfd_cfg_ddim_step_ps); CFG is always on (nb = 2, also for an entry of 1.0), and the captured graph is keyed on the
+shape only, the vector being one more static input: one graph serves every mixture of scales.  With one number every
+path, graph key and result is what it was.
 """
 import numpy as np
 import torch
 
 from ..hip import ops
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps, noise_like
+
+
+_PER_SAMPLE = 'per-sample scale'   # stands in the graph key where a batch-wide scale puts its value
+
+
+def is_per_sample(scale):
+    """a tensor or a sequence of numbers; one number (python / numpy scalar, 0-d tensor) is the reference's batch-wide scale"""
+    if torch.is_tensor(scale):
+        return scale.dim() > 0
+    return isinstance(scale, (list, tuple, np.ndarray)) and np.ndim(scale) > 0
+
+
+def per_sample_scale(scale, bs, device):
+    """None for one number, else the fp32 [bs] vector on `device` of a tensor or sequence of bs numbers"""
+    if not is_per_sample(scale):
+        return None
+    v = scale.detach() if torch.is_tensor(scale) else torch.as_tensor(np.asarray(scale, dtype=np.float64))
+    if tuple(v.shape) != (bs,):
+        raise ValueError(f"a per-sample guidance scale needs {bs} numbers, one per sample: got shape {tuple(v.shape)}")
+    return v.to(device=device, dtype=torch.float32).contiguous()
 
 
 class DDIMSampler(object):
@@ -117,7 +143,12 @@ class DDIMSampler(object):
         scale = c_info['unconditional_guidance_scale']
         uc = c_info.get('unconditional_conditioning', None)
         cond = c_info['conditioning']
-        cfg = not ((scale == 1.) or (uc is None))
+        sps = per_sample_scale(scale, bs, device)     # moved to the device once per request
+        if sps is not None:
+            if uc is None:
+                raise ValueError("a per-sample guidance scale needs c_info['unconditional_conditioning']")
+            scale = 1.0                               # column 4 of the coefficient table: not read on this path
+        cfg = sps is not None or not ((scale == 1.) or (uc is None))
         if cfg and uc.shape[0] == 1 and cond.shape[0] > 1:
             # app.py:239-241 loads ONE fixed unconditional context (SeeCoder-Anime) whatever n_samples is; the
             # reference's torch.cat below then fails for n_samples > 1 -- broadcast it instead
@@ -152,7 +183,8 @@ class DDIMSampler(object):
             t_table = t_col.repeat(1, nb * n)
             zl = n if zero_lead else 0
 
-            def run_loop(x, c_in, hint, nkey=None):
+            def run_loop(x, c_in, hint, nkey=None, sps=None):
+                ps = {} if sps is None else {'scale': sps}
                 from .controlnet import PreparedHint
                 ctx = model.prepare_context(c_in)
                 ctx.zero_lead = zl
@@ -180,10 +212,10 @@ class DDIMSampler(object):
                         noise = noise.contiguous()
                     if keyed:     # sigma * temperature * z(key row, index, element), drawn inside the kernel
                         x, pred_x0, xin = ops.cfg_ddim_step(eps, nb, x, coef[index], want_next=True, rep=rep,
-                                                            noise_key=nkey, step=index, noise_mul=temperature)
+                                                            noise_key=nkey, step=index, noise_mul=temperature, **ps)
                     else:
                         x, pred_x0, xin = ops.cfg_ddim_step(eps, nb, x, coef[index], noise=noise, want_next=True,
-                                                            rep=rep)
+                                                            rep=rep, **ps)
                     if index % log_every_t == 0 or index == total_steps - 1:
                         inter_xt.append(x)
                         inter_x0.append(pred_x0)
@@ -199,7 +231,7 @@ class DDIMSampler(object):
             # (Round 4 also cut the batch into concurrent sub-batch graphs on their own streams: 520 -> 646 ms per batch at
             #  C2, profiles/r04_lanes_ab.log -- removed in round 5.)
             key = (tuple(x.shape), tuple(c_in.shape), None if hint is None else tuple(hint.shape), total_steps,
-                   float(scale), nb, x_type, c_type, int(log_every_t), zero_lead,
+                   float(scale) if sps is None else _PER_SAMPLE, nb, x_type, c_type, int(log_every_t), zero_lead,
                    bool(self.share_cfg_prefix), hash(np.asarray(timesteps).tobytes()), self._weights_signature(),
                    None if nkey is None else (float(temperature), hash(np.asarray(self.ddim_sigmas).tobytes())))
             ent = self._graphs.pop(key, None)
@@ -208,22 +240,24 @@ class DDIMSampler(object):
                     torch.cuda.synchronize()   # never drop a graph whose replay may still be in flight
                     self._graphs.pop(next(iter(self._graphs)))   # least recently used (a server varies batch size and
                 run_loop, t_table = make_loop(bs)                 # scale per request: keep the others)
-                ent = self._capture(run_loop, x, c_in, hint, (coef, t_table), nkey)
+                ent = self._capture(run_loop, x, c_in, hint, (coef, t_table), nkey, sps)
             self._graphs[key] = ent            # (re-)inserted last = most recently used
-            g, sx, sc, sh, outs, _keep, sk = ent
+            g, sx, sc, sh, outs, _keep, sk, ss = ent
             sx.copy_(x)
             sc.copy_(c_in)
             if sh is not None:
                 sh.copy_(hint)
             if sk is not None:
                 sk.copy_(nkey)
+            if ss is not None:
+                ss.copy_(sps)
             g.replay()
             xf = outs[0].clone()               # static output buffers of the graph
             ixt = [t.clone() for t in outs[1]]
             ix0 = [t.clone() for t in outs[2]]
         else:
             run_loop, _ = make_loop(bs)
-            xf, ixt, ix0 = run_loop(x, c_in, hint, nkey)
+            xf, ixt, ix0 = run_loop(x, c_in, hint, nkey, sps)
         intermediates = {'pred_xt': [t.to(dtype) for t in ixt], 'pred_x0': [t.to(dtype) for t in ix0]}
         out = xf.to(dtype)
         x_info['x'] = out
@@ -247,6 +281,9 @@ class DDIMSampler(object):
         model = self.model
         scale = None
         for ci in c_info_list:
+            if is_per_sample(ci['unconditional_guidance_scale']):
+                raise ValueError("a per-sample guidance scale is out of scope for multi-context sampling: give one "
+                                 "number, the same for every context")
             if scale is None:
                 scale = ci['unconditional_guidance_scale']
             else:
@@ -344,7 +381,8 @@ class DDIMSampler(object):
     def enable_graph(self, on=True):
         """Replay the whole DDIM trajectory as one captured hipGraph (eta = 0, or any eta with the seeded noise of
         x_info['noise_key']).  The graph is
-        keyed by shapes / step count / guidance scale / the identity+version of every model
+        keyed by shapes / step count / guidance scale (one number; a per-sample vector is a static input instead) /
+        the identity+version of every model
         parameter, so a weight hot-swap (app.py:139-177) re-captures instead of replaying stale
         packed weights.  Static input buffers are owned by the sampler."""
         self.use_graph = bool(on)
@@ -355,22 +393,23 @@ class DDIMSampler(object):
         from ..hip.layers import generation
         return hash((generation(),) + tuple((p.data_ptr(), p._version) for p in self.model.parameters()))
 
-    def _capture(self, run_loop, x, c_in, hint, keep, nkey=None):
+    def _capture(self, run_loop, x, c_in, hint, keep, nkey=None, sps=None):
         from ..hip import binding
         binding.prof_enable(False)  # event timing cannot be captured
         sx, sc = x.clone(), c_in.clone()
         sh = hint.clone() if hint is not None else None
         sk = nkey.clone() if nkey is not None else None
+        ss = sps.clone() if sps is not None else None
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):     # warm-up outside capture: packs weights, sizes the allocator
-            run_loop(sx, sc, sh, sk)
+            run_loop(sx, sc, sh, sk, ss)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            outs = run_loop(sx, sc, sh, sk)
-        return g, sx, sc, sh, outs, keep, sk
+            outs = run_loop(sx, sc, sh, sk, ss)
+        return g, sx, sc, sh, outs, keep, sk, ss
 
     @ops.serialised
     @torch.no_grad()
@@ -383,7 +422,13 @@ class DDIMSampler(object):
         b = x.shape[0]
         scale = c_info['unconditional_guidance_scale']
         uc = c_info.get('unconditional_conditioning', None)
-        cfg = not ((scale == 1.) or (uc is None))
+        sps = per_sample_scale(scale, b, x.device)
+        if sps is not None:
+            if uc is None:
+                raise ValueError("a per-sample guidance scale needs c_info['unconditional_conditioning']")
+            scale = 1.0
+        ps = {} if sps is None else {'scale': sps}
+        cfg = sps is not None or not ((scale == 1.) or (uc is None))
         nb = 2 if cfg else 1
         if cfg:
             c_in = torch.cat([uc, c_info['conditioning']])
@@ -405,11 +450,11 @@ class DDIMSampler(object):
             raise ValueError("noise_dropout > 0 is not available with x_info['noise_key']")
         if nkey is not None and float(sig) != 0.:
             x_prev, pred_x0, _ = ops.cfg_ddim_step(eps, nb, xf, coef, want_next=False, noise_key=nkey, step=index,
-                                                   noise_mul=temperature)
+                                                   noise_mul=temperature, **ps)
             return x_prev.to(x.dtype), pred_x0.to(x.dtype)
         if float(sig) != 0.:
             noise = (noise_like(xf, repeat_noise) * temperature).contiguous()
             if noise_dropout > 0.:
                 noise = torch.nn.functional.dropout(noise, p=noise_dropout).contiguous()
-        x_prev, pred_x0, _ = ops.cfg_ddim_step(eps, nb, xf, coef, noise=noise, want_next=False)
+        x_prev, pred_x0, _ = ops.cfg_ddim_step(eps, nb, xf, coef, noise=noise, want_next=False, **ps)
         return x_prev.to(x.dtype), pred_x0.to(x.dtype)

@@ -67,6 +67,17 @@ def shard_noise_keys(n_global, seed, rank, world_size):
     return torch.from_numpy(sample_keys(seed, rank * n, n))
 
 
+def shard_scales(scales, rank, world_size):
+    """rank's entries of the per-sample guidance scales of the GLOBAL batch (the contiguous split of shard_xT and
+    shard_noise_keys: sample j keeps its scale whatever P is), fp32 [n_local] on the CPU"""
+    v = torch.as_tensor(scales).detach().to(device='cpu', dtype=torch.float32).reshape(-1)
+    n_global = v.shape[0]
+    if n_global % world_size:
+        raise ValueError(f"{n_global} guidance scales do not divide over {world_size} ranks")
+    n = n_global // world_size
+    return v[rank * n:(rank + 1) * n].clone()
+
+
 def force_collective():
     """PFD_FORCE_COLLECTIVE=1 with an initialised process group: the collectives run even at world size 1 -- the
     one-GPU RCCL smoke (tests/test_hip_parity.py::test_rccl_one_rank_collectives, `bench.py --gpus 1` under that
@@ -225,9 +236,20 @@ class PromptFreePipeline:
         (height, width) first.
         device_noise: the per-step noise of eta > 0 is the seeded counter-based noise of lib/noise.py, sample j of the
         GLOBAL batch keyed (seed, j), evaluated inside the DDIM step kernel: the result does not depend on the world
-        size (like x_T) and the loop replays as a hipGraph.  False: the reference's draw from the global generator."""
+        size (like x_T) and the loop replays as a hipGraph.  False: the reference's draw from the global generator.
+        scale: one number, or a sequence / tensor of n_global numbers: sample j of the GLOBAL batch is guided with
+        scale[j] (pfd_cfg_ddim_step_ps; CFG is then on for every sample, also one whose scale is 1).
+        control: [1,3,H,W] is one hint shared by all samples; [n_local,3,H,W] is one hint PER SAMPLE of this rank."""
+        from .model_zoo.ddim import is_per_sample
         P, r = self.world_size, self.rank
         dev = self.net.device
+        if is_per_sample(scale):     # checked before anything touches the device
+            if tuple(torch.as_tensor(scale).shape) != (n_global,):
+                raise ValueError(f"scale must be one number or {n_global} numbers, one per sample of the global batch")
+            scale = shard_scales(scale, r, P)
+        if torch.is_tensor(control) and control.dim() == 4 and control.shape[0] not in (1, n_global // P):
+            raise ValueError(f"control must be [1, 3, H, W] (shared) or [{n_global // P}, 3, H, W] (one hint per local "
+                             f"sample): got {control.shape[0]} hints")
         u8_image, u8_control = image_io.wants_ingest(image), control is not None and image_io.wants_ingest(control)
         if u8_image:                 # checked before anything touches the device
             image_io.check_u8_picture(image, 'image', min_side=32)

@@ -13,6 +13,12 @@ model with no lock and one request = one `sampler.sample` of `n_sample_image` sa
     versions, so the next batch re-packs / re-captures;
   * returns packed uint8 HWC images (`ToPILImage`'s arithmetic on the device, pfd_image_u8_f16) or the
     float images, through `concurrent.futures.Future`s.
+
+`mixed_batches=True` (opt-in) takes two entries out of that list.  The guidance scale becomes per-sample
+(pfd_cfg_ddim_step_ps): the key keeps only "scale == 1" (those requests keep the cheaper half-size batch without CFG
+among themselves), every other batch runs with a scale vector and one captured graph per shape whatever the scales
+are.  ControlNet requests share a batch with other ControlNet requests, each sample with its own hint.  Still per
+batch: output size, steps, eta, noise kind, output kind, with / without control, unconditional-context kind.
 """
 import queue
 import threading
@@ -26,14 +32,17 @@ from .pipeline import PromptFreePipeline, shard_noise_keys, shard_xT
 
 class _Request:
     __slots__ = ("image", "n", "height", "width", "steps", "scale", "eta", "seed", "control", "uncond", "as_uint8",
-                 "device_noise", "future")
+                 "device_noise", "future", "mixed")
 
     def __init__(self, **kw):
         for k in self.__slots__:
             setattr(self, k, kw.get(k))
 
     def key(self):
-        """requests with equal keys can share one DDIM batch"""
+        """requests with equal keys can share one DDIM batch (mixed: any two scales other than 1 can)"""
+        if self.mixed:
+            return (self.height, self.width, self.steps, float(self.scale) == 1.0, float(self.eta),
+                    self.control is None, self.uncond is None, bool(self.as_uint8), bool(self.device_noise))
         return (self.height, self.width, self.steps, float(self.scale), float(self.eta), self.control is None,
                 self.uncond is None, bool(self.as_uint8), bool(self.device_noise))
 
@@ -41,13 +50,17 @@ class _Request:
         """eta > 0 WITHOUT device_noise draws its noise from the global RNG inside the loop (ddim.py:166): batched with
         other requests the draw -- and so the result for a given seed -- would depend on the company; such requests run
         alone, seeded.  With device_noise the noise of sample j is a function of (request seed, j, step, element)
-        (lib/noise.py), whatever it is batched with: shareable at any eta.  ControlNet requests always run alone."""
-        return (float(self.eta) == 0.0 or bool(self.device_noise)) and self.control is None
+        (lib/noise.py), whatever it is batched with: shareable at any eta.  ControlNet requests always run alone, unless
+        the server mixes batches: then they share with each other (`control is None` is part of the key)."""
+        return (float(self.eta) == 0.0 or bool(self.device_noise)) and (self.control is None or bool(self.mixed))
 
 
 class PromptFreeServer:
-    def __init__(self, net, use_graph=True, max_batch=8, max_wait_s=0.0):
+    def __init__(self, net, use_graph=True, max_batch=8, max_wait_s=0.0, mixed_batches=False):
+        """mixed_batches: requests that differ in guidance scale (other than scale 1) or in control picture share a
+        batch; see the module docstring.  False: one scale per batch, ControlNet requests alone."""
         self.net = net
+        self.mixed_batches = bool(mixed_batches)
         self.pipe = PromptFreePipeline(net)
         self.pipe.enable_graph(use_graph)
         self.max_batch, self.max_wait_s = int(max_batch), float(max_wait_s)
@@ -93,7 +106,7 @@ class PromptFreeServer:
             raise ValueError(f"control must be a float tensor [1, 3, {height}, {width}] or a uint8 picture [h, w, 3]")
         r = _Request(image=image, n=int(n_samples), height=int(height), width=int(width), steps=int(steps),
                      scale=scale, eta=eta, seed=int(seed), control=control, uncond=uncond, as_uint8=as_uint8,
-                     device_noise=bool(device_noise), future=Future())
+                     device_noise=bool(device_noise), future=Future(), mixed=self.mixed_batches or None)
         self._q.put(r)
         return r.future
 
@@ -140,7 +153,7 @@ class PromptFreeServer:
                 except queue.Empty:
                     break
                 if nxt is None or isinstance(nxt, tuple) or nxt.key() != item.key() or \
-                        total + nxt.n > self.max_batch or nxt.control is not None:
+                        total + nxt.n > self.max_batch or (nxt.control is not None and not self.mixed_batches):
                     pending = nxt                   # order is preserved: it starts the next round
                     if nxt is None:
                         pending = None
@@ -199,7 +212,17 @@ class PromptFreeServer:
             cond, uncond, xT = torch.cat(conds), torch.cat(unconds), torch.cat(xts).to(dev)
             c_info = {'type': 'image', 'conditioning': cond, 'unconditional_conditioning': uncond,
                       'unconditional_guidance_scale': r0.scale}
-            if r0.control is not None:
+            per_sample = bool(r0.mixed) and float(r0.scale) != 1.0    # the scale-1 key keeps the batch without CFG
+            if per_sample:                                            # fp32 [N]: r.scale for each of r's samples, batch order
+                c_info['unconditional_guidance_scale'] = torch.tensor(
+                    [float(r.scale) for r in batch for _ in range(r.n)], dtype=torch.float32)
+            if r0.control is not None and r0.mixed:
+                # one hint per sample [N,3,H,W]: every request's picture is ingested on its own (uint8 pictures may
+                # differ in source size) and repeated over the request's samples
+                hints = [(self.pipe.ingest(r.control, (r.height, r.width), 'control') if image_io.wants_ingest(r.control)
+                          else r.control.to(dev)).expand(r.n, -1, -1, -1) for r in batch]
+                c_info['control'] = torch.cat(hints)
+            elif r0.control is not None:
                 c_info['control'] = (self.pipe.ingest(r0.control, (r0.height, r0.width), 'control')
                                      if image_io.wants_ingest(r0.control) else r0.control.to(dev))
             x_info = {'type': 'image', 'xt': xT}
