@@ -72,6 +72,10 @@ const char* pfd_last_error(void);
  *                nothing launched and nothing written (callers run ups=1 with the 9-tap weight).
  *                W is [N][ksize*ksize*Cin] (tap-major, channel-minor), ldw its row stride.
  *   epi(v) = act(v + bias[n or m] + rowvec[(m / rows_per_rv)*ldrv + n]) + R[m*ldr + n]
+ *                Rounding: the contraction and the activation are fp32.  Without a residual the result is rounded to f16
+ *                once.  With one, the wide-tile kernels stage act(...) as f16 (the LDS image of the output tile) and their
+ *                store pass adds R in fp32 and rounds again: two roundings, at most 2^-11 |act(...)| more than one.  The
+ *                register-staged kernel and the split-K reductions add R in fp32 and round once.
  *
  * Replaces: nn.Linear / 1x1 nn.Conv2d everywhere on the path (attention.py:169-176,
  * 47-51, 60-67, 329-347; swin.py:88-90,171-173,322; seecoder.py:74-77,216-218,358;

@@ -290,7 +290,7 @@ def wide_tile_ok(N, K):
 
 def gemm(a, w, *, bias=None, rowvec=None, rows_per_rv=1, res=None, act=ACT_NONE, out=None,
          bias_per_row=False, n=None, k=None, tile=0, out_t=None, n_split=None, ln=None, ln_out=None,
-         a2=None, zero_rows=0, gn_out=False, res_rows=None):
+         a2=None, zero_rows=0, gn_out=False, res_rows=None, w_tiled=False):
     """out[M, N] = epi(a[M, K] @ w[N, K]^T); see pfd_gemm_f16 in include/pfd_hip.h.
     a2: second source of the contraction -- the operand is the virtual column concat [a | a2] (K = Ka + Ka2; the
     1x1 skip convolution over a skip concat).  zero_rows: that many all-zero operand rows come in front of a's rows
@@ -302,7 +302,9 @@ def gemm(a, w, *, bias=None, rowvec=None, rows_per_rv=1, res=None, act=ACT_NONE,
     out_t / n_split: columns >= n_split go, transposed, to out_t[N - n_split, M] (wide-tile path only).
     ln = (stats, colsum, eps): LayerNorm of `a` folded into the contraction (w is the gamma-scaled weight, bias is b';
     PfdGemmDesc.ln_stats).  ln_out: True (allocate) or a float32 [M, N/160, 2] tensor -> the partial row sums of the
-    OUTPUT are written there and (out, stats) is returned."""
+    OUTPUT are written there and (out, stats) is returned.
+    w_tiled: `w` holds the K-tile-contiguous pack of the [N, K] weight (PfdGemmDesc.w_tiled; the caller packs it) -- a contiguous
+    [N, K] tensor whose memory is [N / T][K / 64][T][64], T = 160 if N % 160 == 0 else 128.  Wide-tile kernels only."""
     _chk16(a, "gemm A")
     _chk16(w, "gemm W")
     M, Ka, lda = _rows(a)
@@ -339,6 +341,10 @@ def gemm(a, w, *, bias=None, rowvec=None, rows_per_rv=1, res=None, act=ACT_NONE,
         d.Ct, d.ldct, d.n_split = out_t.data_ptr(), out_t.stride(0), n_split
     d.rows_per_rv, d.act, d.bias_per_row = rows_per_rv, act, 1 if bias_per_row else 0
     d.ksize = 0
+    if w_tiled:
+        if not w.is_contiguous() or (N % 160 and N % 128) or K % 64 or (Nw, Kw) != (N, K):
+            raise ValueError(f"gemm: w_tiled takes the contiguous pack of a whole [N, K] weight, N % 160 == 0 or N % 128 == 0 (w {tuple(w.shape)})")
+        d.w_tiled = 1
     if a2 is not None:
         d.A2, d.lda2, d.k_split = a2.data_ptr(), lda2, Ka
     d.zero_rows = zero_rows
@@ -393,7 +399,7 @@ def ups_fold_declined(key):
 
 
 def conv(x, w, ksize, *, stride=1, pad=None, ups=False, bias=None, rowvec=None, res=None, act=ACT_NONE,
-         out=None, tile=0, out_hw=None, rows_per_rv=None, gn=None, gn_out=False, gn_fuse=None):
+         out=None, tile=0, out_hw=None, rows_per_rv=None, gn=None, gn_out=False, gn_fuse=None, w_tiled=False):
     """Implicit-GEMM convolution of an NHWC image x[B,H,W,Cin] (Cin % 64 == 0) with packed
     weights w[N, ksize*ksize*Cin]; returns [B,Ho,Wo,N].  rowvec: [B, N] per-sample vector.
     ups: False | True (nearest-2x upsample fused into the gather of the 9-tap weight, PfdGemmDesc.ups = 1) | 2 (the same
@@ -404,7 +410,8 @@ def conv(x, w, ksize, *, stride=1, pad=None, ups=False, bias=None, rowvec=None, 
     (table from groupnorm_table; see PfdGemmDesc.gn_table) -- x is then the UN-normalised tensor.
     gn_fuse = (gamma, beta, eps, silu, keep_raw): GroupNorm(32)(+SiLU) of the OUTPUT inside the launch's split-K reduction
     (PfdGemmDesc.gnf_y, ABI 9).  Returns (raw | None, normalised) when the library serves it, else None with NOTHING launched
-    (a problem it does not split, a width the fused reduction is not built for): the caller runs conv + groupnorm."""
+    (a problem it does not split, a width the fused reduction is not built for): the caller runs conv + groupnorm.
+    w_tiled: `w` holds the K-tile-contiguous pack of the weight (PfdGemmDesc.w_tiled, as for gemm); not with ups=2."""
     _chk16(x, "conv x")
     _chk16(w, "conv W")
     B, H, W_, Cin = x.shape
@@ -460,6 +467,10 @@ def conv(x, w, ksize, *, stride=1, pad=None, ups=False, bias=None, rowvec=None, 
     d.rows_per_rv, d.act, d.bias_per_row = (Ho * Wo if rows_per_rv is None else rows_per_rv), act, 0
     d.ksize, d.stride, d.pad, d.ups = ksize, stride, pad, 2 if phase else 1 if ups else 0
     d.B, d.H, d.Wd, d.Cin, d.Ho, d.Wo = B, H, W_, Cin, Ho, Wo
+    if w_tiled:
+        if phase or not w.is_contiguous() or (N % 160 and N % 128):
+            raise ValueError(f"conv: w_tiled takes the contiguous pack of a 9-tap weight, N % 160 == 0 or N % 128 == 0 (w {tuple(w.shape)})")
+        d.w_tiled = 1
     if gn is not None:
         d.gn_table, d.gn_c1, d.gn_act = table.data_ptr(), C1, ACT_SILU if gn_silu else ACT_NONE
         if x2 is not None:

@@ -4,6 +4,8 @@ compares the HIP kernels with them) and the fused attention family (tests/test_a
 section).  Everything here is torch on whatever device the operands live on; nothing imports the
 native library.  A plain module, not a conftest: the two test files import it by name."""
 import functools
+import re
+import zlib
 
 import torch
 import torch.nn.functional as F
@@ -472,3 +474,669 @@ def attention_densified(p):
     vt = torch.zeros((C, B, Nkp), dtype=torch.float16)
     vt[:, :, :Nk] = V.permute(1, 3, 0, 2).reshape(C, B, Nk)
     return q, k, vt.reshape(-1), dict(ldq=C, ldk=C, ldvt=B * Nkp, q_bs=Nq * C, k_bs=Nk * C, vt_bs=Nkp)
+
+
+# ------------------------------------------------------------------------------------------------
+# GEMM / convolution (pfd_gemm_f16: csrc/gemm_glds.hip, csrc/gemm_conv.hip): reference, bound, mutants, cases and operands
+# (tests/test_gemm_kernels_cpu.py pins and qualifies them, tests/test_gemm_kernels_gpu.py uses them)
+# ------------------------------------------------------------------------------------------------
+ACT_NONE, ACT_GELU, ACT_RELU, ACT_SILU, ACT_GEGLU = 0, 1, 2, 3, 4          # PFD_ACT_* of include/pfd_hip.h
+GEMM_MUTANTS = ("last_k_dropped", "pad_tap_reads_edge", "pad_before_normalise", "tap_crosses_sample", "rowvec_row_by_tile",
+                "residual_no_wrap", "residual_wrap_off_by_one", "zero_rows_rounded_to_tile", "bias_after_act",
+                "geglu_halves_swapped", "ups_gather_ceil", "k_split_second_source_offset", "ln_mean_of_first_part",
+                "tail_transposed_without_bias")
+GEMM_CLASSES = ("lin160", "lin128", "geglu", "reg", "abi", "conv", "patch", "narrow")
+# the Lipschitz constants of the activations: max |gelu'| = 1.1290 (at x = 1.4142...), max |silu'| = 1.0998 (at x = 2.3994)
+_ACT_LIP = {ACT_NONE: 1.0, ACT_GELU: 1.13, ACT_RELU: 1.0, ACT_SILU: 1.10, ACT_GEGLU: 1.13}
+
+
+def gemm_conv_operand(img, geom, mutant=None, pad_value=None):
+    """the operand matrix of the implicit convolution, from the header text: img [B, H, W, Cin] -> [B Ho Wo, ks ks Cin] with
+    m = (b, oy, ox), k = (ky, kx, ci) (tap-major, channel-minor), iy = oy * stride + ky - pad, out-of-range taps read 0 (or
+    pad_value [B, Cin]: the pad_before_normalise mutant), ups = 1 gathers iy >> 1 from the image upsampled 2x.
+    geom = (ks, stride, pad, ups, Ho, Wo)."""
+    ks, stride, pad, ups, Ho, Wo = geom
+    B, H, W, C = img.shape
+    Hin, Win = (2 * H, 2 * W) if ups else (H, W)
+    k = torch.arange(ks)
+    iy = torch.arange(Ho)[:, None] * stride + k[None] - pad              # [Ho, ks], coordinates of the (upsampled) image
+    ix = torch.arange(Wo)[:, None] * stride + k[None] - pad
+    vy, vx = (iy >= 0) & (iy < Hin), (ix >= 0) & (ix < Win)
+    if mutant == "pad_tap_reads_edge":
+        iy, ix = iy.clamp(0, Hin - 1), ix.clamp(0, Win - 1)
+        vy, vx = torch.ones_like(vy), torch.ones_like(vx)
+    if ups:
+        iy, ix = ((iy + 1) >> 1, (ix + 1) >> 1) if mutant == "ups_gather_ceil" else (iy >> 1, ix >> 1)
+    rows = torch.arange(B)[:, None, None] * H + iy[None]                  # [B, Ho, ks]: row of the stacked image [B H, W, C]
+    vrow = vy[None].expand(B, Ho, ks)
+    if mutant == "tap_crosses_sample" and not ups:
+        vrow = (rows >= 0) & (rows < B * H)                               # the row above sample b's first is b - 1's last
+    else:
+        rows = torch.arange(B)[:, None, None] * H + iy.clamp(0, H - 1)[None]
+    g = img.reshape(B * H, W, C)[rows.clamp(0, B * H - 1)]                # [B, Ho, ks, W, C]
+    g = g[:, :, :, ix.clamp(0, W - 1)]                                    # [B, Ho, ks, Wo, ks, C]
+    ok = (vrow[:, :, :, None, None] & vx[None, None, None]).unsqueeze(-1)
+    fill = torch.zeros((), dtype=img.dtype) if pad_value is None else pad_value.to(img.dtype)[:, None, None, None, None, :]
+    g = torch.where(ok.to(img.device), g, fill.to(img.device))
+    return g.permute(0, 1, 3, 2, 4, 5).reshape(B * Ho * Wo, ks * ks * C)
+
+
+def geglu_pack(wx, wg, g):
+    """rows [x (g rows) | gate (g rows)] per group of g outputs (pfd_gemm_geglu_group: g = 2 wide-tile, g = 32 register-staged);
+    works for the [N/2, K] weight halves and, with a trailing dimension of 1 squeezed by the caller, for the bias"""
+    n2 = wx.shape[0]
+    return torch.cat([wx.reshape(n2 // g, g, -1), wg.reshape(n2 // g, g, -1)], 1).reshape(2 * n2, -1)
+
+
+def geglu_unpack(w, g):
+    n = w.shape[0]
+    v = w.reshape(n // (2 * g), 2, g, -1)
+    return v[:, 0].reshape(n // 2, -1), v[:, 1].reshape(n // 2, -1)
+
+
+def w_tiled_pack(w, T):
+    """PfdGemmDesc.w_tiled: element (n, k) at (((n / T) * (K / 64) + k / 64) * T + n % T) * 64 + k % 64"""
+    N, K = w.shape
+    return w.reshape(N // T, T, K // 64, 64).permute(0, 2, 1, 3).contiguous().reshape(N, K)
+
+
+def gemm_slab_ranges(nk, splits):
+    """the K-tile (patch kernels: 64-channel block) ranges of the split-K slabs: slab s covers [s kt, min(nk, (s + 1) kt)),
+    kt = ceil(nk / splits); slabs that would start at or beyond nk do not exist (real_splits < splits)"""
+    kt = -(-nk // splits)
+    return [(s * kt, min(nk, (s + 1) * kt)) for s in range(-(-nk // kt))]
+
+
+def ln_out_ref(stored):
+    """PfdGemmDesc.ln_out: [M, N / 160, 2] = (sum, sum of squares) over the 160-column slices of the f16 values stored"""
+    M, N = stored.shape
+    v = stored.double().reshape(M, N // 160, 160)
+    return torch.stack([v.sum(-1), (v * v).sum(-1)], -1)
+
+
+def gn_out_ref(stored):
+    """PfdGemmDesc.gn_out: [M / 64, N / 160, 16, 2], slot (n % 160) / (N / 32) of tile n / 160 = (sum, sum of squares) over the
+    64 rows of the slab and the N / 32 channels of the group; the slots past 160 / (N / 32) are not written (returned as nan)"""
+    M, N = stored.shape
+    cpg = N // 32
+    v = stored.double().reshape(M // 64, 64, N // 160, 160 // cpg, cpg)
+    s = torch.stack([v.sum((1, 4)), (v * v).sum((1, 4))], -1)             # [slab, tile, group, 2]
+    out = torch.full((M // 64, N // 160, 16, 2), float("nan"), dtype=torch.float64, device=stored.device)
+    out[:, :, :160 // cpg] = s
+    return out
+
+
+def groupnorm32_ref(x, rows, gamma, beta, eps, silu):
+    """GroupNorm(32) (+ SiLU) of a token-major [B rows, N] tensor, fp64: statistics per (sample, group of N / 32 channels)"""
+    M, N = x.shape
+    v = x.double().reshape(M // rows, rows, 32, N // 32)
+    mean = v.mean((1, 3), keepdim=True)
+    var = (v * v).mean((1, 3), keepdim=True) - mean * mean
+    y = ((v - mean) / torch.sqrt(var + eps)).reshape(M, N) * gamma.double() + beta.double()
+    return F.silu(y) if silu else y
+
+
+def _gemm_operand(p, mutant, dtype, want_abs=False):
+    """the [M, K] operand of the contraction in `dtype` (rows below zero_rows are zeros) and, for the GroupNorm prologue,
+    E [M, K]: how far an operand element can move when the fp32 evaluation of the prologue rounds to the other fp16 neighbour"""
+    c = p["case"]
+    E = None
+    if c["kind"] == "conv":
+        x = p["A"]
+        if c["gn_pro"] is not None:
+            x = torch.cat([p["A"], p["A2"]], -1) if p["A2"] is not None else p["A"]
+            tab = p["gn_table"].to(dtype)                                # [B, 2, Cin]
+            v = activation_ref(x.to(dtype) * tab[:, None, None, 0] + tab[:, None, None, 1], ACT_SILU if c["gn_pro"][1] else ACT_NONE, dtype)
+            padv = None
+            if mutant == "pad_before_normalise":
+                padv = activation_ref(tab[:, 1], ACT_SILU if c["gn_pro"][1] else ACT_NONE, dtype).half().to(dtype)
+            if want_abs:
+                d = p["pro_delta"]
+                E = gemm_conv_operand(((v + d).half().double() - (v - d).half().double()).abs(), c["geom"])
+            X = gemm_conv_operand(v.half().to(dtype), c["geom"], mutant, padv)
+        else:
+            X = gemm_conv_operand(x.to(dtype), c["geom"], mutant)
+    else:
+        X = p["A"].to(dtype)
+        if p["A2"] is not None:
+            a2 = p["A2"].to(dtype)
+            if mutant == "k_split_second_source_offset":                   # A2 indexed by k instead of k - k_split
+                a2 = a2[:, (torch.arange(a2.shape[1]) + c["k_split"]) % a2.shape[1]]
+            X = torch.cat([X, a2], 1)
+        zr = c["zero_rows"]
+        if zr:
+            if mutant == "zero_rows_rounded_to_tile":
+                X = X.clone()
+                X[:min(-(-zr // 64) * 64, c["M"]) - zr] = 0
+            X = torch.cat([X.new_zeros((zr, X.shape[1])), X], 0)
+    if mutant == "last_k_dropped":
+        X = X.clone()
+        X[:, -1] = 0
+    return X, E
+
+
+def gemm_ref(p, mutant=None, dtype=torch.float64, parts=False):
+    """one formula, from the header text of PfdGemmDesc, on the fp16 operands of gemm_problem(case), on their device:
+        C[m, n] = act(sum_k X[m, k] W[n, k] + bias[n or m] + rowvec[m / rows_per_rv, n]) + R[m (- res_rows), n]
+    X the linear operand ([A | A2] with k_split, zero rows in front with zero_rows), the implicit-convolution gather or the
+    GroupNorm-prologue image; GEGLU x * gelu(gate) of the two logical halves; the LayerNorm fold as ((x - mean) rstd) W'^T + b'
+    with the statistics of x in `dtype`; columns >= n_split transposed (+ bias only).  Returns dict(out=[M, N_out]) plus out_t
+    ([N - n_split, M]) with a transposed tail; parts=True adds what gemm_allowance needs.  mutant: one of GEMM_MUTANTS."""
+    assert mutant is None or mutant in GEMM_MUTANTS
+    c = p["case"]
+    M, N, act = c["M"], c["N"], c["act"]
+    X, _ = _gemm_operand(p, mutant, dtype)
+    W = p["W"].to(dtype)
+    if c["ln"] is not None:
+        xs = X[:, :160] if mutant == "ln_mean_of_first_part" else X
+        mean = xs.mean(1, keepdim=True)
+        rstd = 1.0 / torch.sqrt((xs * xs).mean(1, keepdim=True) - mean * mean + c["ln_eps"])
+        X = (X - mean) * rstd
+    acc = X @ W.t()
+    m = torch.arange(M, device=acc.device)
+    bias = None if p["bias"] is None else (p["bias"].to(dtype)[:, None] if c["bias_per_row"] else p["bias"].to(dtype)[None, :])
+    rv = None
+    if p["rowvec"] is not None:
+        mi = (m // 64 * 64 if mutant == "rowvec_row_by_tile" else m) // c["rows_per_rv"]
+        rv = p["rowvec"].to(dtype)[mi]
+    pre = acc
+    if bias is not None and mutant != "bias_after_act":
+        pre = pre + bias
+    if rv is not None:
+        pre = pre + rv
+    if act == ACT_GEGLU:
+        px, pg = pre[:, :N // 2], pre[:, N // 2:]                          # W / bias of the problem are the logical [x | gate]
+        if mutant == "geglu_halves_swapped":
+            px, pg = pg, px
+        post = px * F.gelu(pg)
+    else:
+        post = activation_ref(pre, act, dtype)
+    if bias is not None and mutant == "bias_after_act":
+        post = post + (bias[:, :N // 2] if act == ACT_GEGLU else bias)
+    out = post
+    if p["R"] is not None:
+        r = p["R"].to(dtype)
+        rr = c["res_rows"]
+        if rr and rr != M:
+            if mutant == "residual_no_wrap":
+                r = torch.cat([r, r.new_zeros((M - rr, r.shape[1]))], 0)
+            elif mutant == "residual_wrap_off_by_one":
+                r = r[torch.where(m >= rr, (m - rr + 1).clamp(max=rr - 1), m)]
+            else:
+                r = r[torch.where(m >= rr, m - rr, m)]
+        out = post + r
+    res = {}
+    ns = c["n_split"]
+    if ns:
+        tail = acc[:, ns:] + (bias[:, ns:] if bias is not None and mutant != "tail_transposed_without_bias" else 0)
+        res["out_t"] = tail.t().contiguous()
+        out = out[:, :ns]
+    res["out"] = out
+    if parts:
+        res.update(X=X, pre=pre, post=post, acc=acc)
+    return res
+
+
+# The GPU bound, per element: |got - ref| <= round_once_bound(ref, a) = 2^-11 (|ref| + a) + a with the allowance a[m, n] =
+#   accumulation   c K 2^-24 S,  S = sum_k |x_k| |w_k| + |bias| + |rowvec| (an fp64 abs-GEMM).  The products of two fp16 values are
+#                  exact in fp32; a sum of K terms in ANY order is off by at most (K - 1) u sum |terms| (u = 2^-24, first order:
+#                  Higham, Accuracy and Stability, 4.2), bias and row vector add two more roundings; c = 2 doubles that because
+#                  the order and the rounding inside one MFMA are not documented (nobody has measured that factor: the GPU file
+#                  prints the share of `a` each case needs)
+#   activation     L times the above (L = the activation's Lipschitz constant, _ACT_LIP) plus the fp32 evaluation error of the
+#                  activation itself, fp32_allowance of the reference formula on the pre-activation values; GEGLU x * gelu(g):
+#                  the product rule, |gelu(g)| a_x + |x| L a_g (+ the fp32 allowance of the product)
+#   split-K        slabs are stored as fp16: sum_s 2^-11 |P_s| in front of the activation, P_s the fp64 partial sum over the
+#                  slab's K range (gemm_slab_ranges; the patch kernels split the 64-channel blocks, all nine taps each)
+#   staged value   FINDING of this section: the unsplit wide-tile kernels (epilogue_stage / epilogue_store of gemm_glds.hip) round
+#                  act(v + bias + rowvec) to fp16 into the LDS image of the tile BEFORE the store pass adds the residual in fp32
+#                  and rounds again -- 2^-11 |act(...)| where a residual is present (include/pfd_hip.h says so now).  The
+#                  register-staged kernel and the split-K reductions add the residual in fp32 and round once: no such term
+#   prologue       the GroupNorm prologue is evaluated in fp32 and rounded to fp16: where the fp64 value lies within the fp32
+#                  allowance of a rounding boundary the operand may be the other fp16 neighbour: sum_k E_k |w_k|
+#   LayerNorm fold the kernel forms rstd (x W'^T) - rstd mean s_n + b'_n: the two large terms cancel, so their errors count in
+#                  full: rstd c K u (sum |x| |W'| + |mean| |s_n|); mean and rstd come in fp32 from the partial sums as
+#                  sum / K and rsqrt(sq / K - mean^2 + eps): (P + 3) u relative on mean, the variance off by
+#                  (P + 4) u (sq / K + 2 mean^2), rstd by half of that over (var + eps) plus 4 u for rsqrtf; these multiply
+#                  |mean| |s_n| rstd and |ref - b'|
+#   final          round_once_bound: 2^-11 |ref| (one rounding of the result)
+_U = 2.0 ** -24
+ACC_C = 2.0
+
+
+def gemm_allowance(p, splits=1, wide=True):
+    """the per-element allowance tensor(s) of one case: dict(out=a [M, N_out], out_t=...) for round_once_bound / bound_ratio.
+    splits: the slab count of the launch (1 = unsplit); wide: a wide-tile kernel (the staged-value term applies)."""
+    c = p["case"]
+    M, N, K, act = c["M"], c["N"], c["K"], c["act"]
+    r = gemm_ref(p, parts=True)
+    Xraw, E = _gemm_operand(p, None, torch.float64, want_abs=True)
+    W = p["W"].double()
+    S = Xraw.abs() @ W.abs().t()
+    extra = torch.zeros_like(S)
+    if E is not None:
+        extra = extra + E @ W.abs().t()
+    if c["ln"] is not None:
+        P, ns_ = K // 160, (160 if c["ln"] == "rowstats" else 0)          # ns_: values summed in fp32 per partial sum
+        mean = Xraw.mean(1, keepdim=True)
+        mabs = Xraw.abs().mean(1, keepdim=True)
+        msq = (Xraw * Xraw).mean(1, keepdim=True)
+        var = msq - mean * mean
+        rstd = 1.0 / torch.sqrt(var + c["ln_eps"])
+        s_n = W.sum(1)[None]
+        d_mean = (P + 3) * _U * mean.abs() + ns_ * _U * mabs
+        d_var = (P + 4) * _U * (msq + 2 * mean * mean) + ns_ * _U * (msq + 2 * mean.abs() * mabs)
+        d_rstd_rel = 0.5 * d_var / (var + c["ln_eps"]) + 4 * _U
+        # ref - b' = rstd (x W'^T - mean s_n) = r["acc"]: rstd is one factor of it (d_rstd_rel relative), the accumulation and
+        # the product mean s_n count in full, mean's error is scaled by rstd |s_n| (s_n itself is fp32: one more u)
+        a_acc = rstd * ACC_C * K * _U * (S + mean.abs() * s_n.abs()) + rstd * s_n.abs() * (d_mean + _U * mean.abs()) \
+            + d_rstd_rel * r["acc"].abs()
+    else:
+        rstd = 1.0
+        a_acc = ACC_C * K * _U * S
+    S_b = torch.zeros_like(S)
+    if p["bias"] is not None:
+        b = p["bias"].double().abs()
+        S_b = S_b + (b[:, None] if c["bias_per_row"] else b[None, :])
+    if p["rowvec"] is not None:
+        S_b = S_b + p["rowvec"].double().abs()[torch.arange(M) // c["rows_per_rv"]]
+    a_pre = a_acc + ACC_C * K * _U * S_b + extra
+    if splits > 1:
+        if c["cls"] == "patch":
+            Cin = c["K"] // 9
+            cols = lambda lo, hi: torch.cat([torch.arange(t * Cin + lo * 64, t * Cin + hi * 64) for t in range(9)])
+            rng = [cols(lo, hi) for lo, hi in gemm_slab_ranges(Cin // 64, splits)]
+        else:
+            rng = [torch.arange(lo * 64, hi * 64) for lo, hi in gemm_slab_ranges(K // 64, splits)]
+        # (the slabs hold partial sums of x W'^T: the LayerNorm fold is applied behind the reduction, which scales them by rstd)
+        a_pre = a_pre + sum(2.0 ** -11 * (Xraw[:, i] @ W[:, i].t()).abs() for i in rng) * rstd
+    res = {}
+    ns = c["n_split"]
+    if ns:
+        res["out_t"] = a_pre[:, ns:].t().contiguous()
+    pre = r["pre"]
+    if act == ACT_GEGLU:
+        px, pg = pre[:, :N // 2], pre[:, N // 2:]
+        ax, ag = a_pre[:, :N // 2], a_pre[:, N // 2:]
+        e_act = fp32_allowance(F.gelu(pg), F.gelu(pg.float()))
+        a = F.gelu(pg).abs() * ax + px.abs() * (_ACT_LIP[act] * ag + e_act) + ax * (_ACT_LIP[act] * ag + e_act) \
+            + 4 * _U * r["post"].abs()
+    elif act == ACT_NONE:
+        a = a_pre
+    else:
+        a = _ACT_LIP[act] * a_pre + fp32_allowance(r["post"], activation_ref(pre.float(), act, torch.float32))
+    if wide and splits == 1 and p["R"] is not None:
+        a = a + 2.0 ** -11 * (r["post"].abs() + a)                        # the staged value (see above)
+    res["out"] = a[:, :ns] if ns else a
+    return res
+
+
+def _embed(data, rows_before, rows_after, c0, width, poison):
+    """`data` [rows, cols] as rows [rows_before, +rows) and columns [c0, +cols) of a buffer that holds the fp16 NaN patterns
+    of _POISON (or zeros) everywhere else; returns the buffer"""
+    rows, cols = data.shape
+    n = (rows_before + rows + rows_after) * width
+    buf = (_poisoned(n) if poison else torch.zeros(n, dtype=torch.float16)).view(-1, width)
+    buf[rows_before:rows_before + rows, c0:c0 + cols] = data
+    return buf
+
+
+# ---- cases: one table; every entry names the forced tile code (0 = the heuristic) and the kernel instantiation it is meant to
+# reach, in the spelling of `emu_gemm --dispatch` (tests/test_gemm_kernels_cpu.py checks both against the dispatcher) ----
+def wide_tile(v, s=0):
+    """tile code of pfd_gemm_f16_ex: wide-tile variant v with split-K factor s (0 = heuristic for either)"""
+    return 1000 + 100 * v + s
+
+
+def wide_kernel_name(v, conv, nt):
+    """the instantiation behind a forced wide-tile variant (the variant switches at the end of pfd_gemm160_try, restated)"""
+    b = "true" if conv else "false"
+    g160 = {22: (2, 2, 2), 23: (2, 2, 4), 24: (2, 4, 2), 25: (2, 4, 3), 41: (4, 1, 2), 43: (4, 1, 4), 82: (4, 2, 2), 83: (4, 2, 3),
+            44: (4, 4, 2)}
+    if v in g160:
+        wm, wmb, nbuf = g160[v]
+        return f"gemm160_kernel<{wm}, {wmb}, {b}, {nbuf}, {nt}>"
+    if v == 84:
+        return "gemm160_kernel<4, 4, false, 2, 10>"
+    if v in (47, 48):
+        return f"gemm160ws_kernel<{b}, {nt}, {3 if v == 47 else 2}, false>"
+    return {96: "conv3x3_patch_ws_kernel<0, 3>", 98: "conv3x3_patch_ws_kernel<0, 2>", 99: "conv3x3_patch_kernel"}[v]
+
+
+_GEMM_DEFAULTS = dict(kind="lin", act=ACT_NONE, bias=False, rowvec=False, rows_per_rv=1, res=False, bias_per_row=False, geom=None,
+                      image=None, k_split=0, zero_rows=0, res_rows=0, n_split=0, ln=None, ln_eps=1e-5, ln_out=False, gn_out=False,
+                      w_tiled=False, gn_pro=None, gnf=None, splits=1, reduce=None, tile=0, base_kernel=None, ldc_pad=16)
+EPI_NONE = dict()
+EPI_FULL = dict(bias=True, act=ACT_SILU, rowvec=True, rows_per_rv=100, res=True)
+EPI_GELU = dict(bias=True, act=ACT_GELU)
+EPI_RELU = dict(act=ACT_RELU)
+_EPI_NAMES = ((EPI_NONE, "plain"), (EPI_FULL, "silu-rv-res"), (EPI_GELU, "gelu"), (EPI_RELU, "relu"))
+
+
+def _epi_name(e):
+    return next(n for d, n in _EPI_NAMES if d is e)
+
+
+def _mk(cid, cls, kernel, M, N, K, **kw):
+    c = dict(_GEMM_DEFAULTS, id=cid, cls=cls, kernel=kernel, M=M, N=N, K=K)
+    assert not set(kw) - set(c), set(kw) - set(c)
+    c.update(kw)
+    return c
+
+
+def _wide(cid, cls, v, s, M, N, K, conv=False, **kw):
+    """a case under the forced wide-tile variant v (0: heuristic; `kernel=` then names what the heuristic takes) and split s"""
+    nt = 5 if N % 160 == 0 else 4
+    kernel = kw.pop("kernel", None) or wide_kernel_name(v, conv, nt)
+    nk = K // 64 if cls != "patch" else K // 9 // 64
+    s_eff = s or kw.get("hsplit", 0)            # hsplit: the split count the heuristic takes where the case forces none
+    kw.pop("hsplit", None)
+    splits = len(gemm_slab_ranges(nk, s_eff)) if s_eff > 1 else 1
+    if splits > 1 and "reduce" not in kw:
+        kw["reduce"] = "splitk_reduce_gn_kernel" if kw.get("gn_out") else "splitk_reduce_gnorm_kernel" if kw.get("gnf") is not None \
+            else "splitk_reduce_kernel"
+    return _mk(cid, cls, kernel, M, N, K, tile=wide_tile(v, s) if (v or s) else 0, splits=splits, **kw)
+
+
+def _conv_geom(B, H, W, Cin, ks=3, stride=1, pad=1, ups=0, out_hw=None):
+    Hin, Win = (2 * H, 2 * W) if ups else (H, W)
+    Ho, Wo = out_hw or ((Hin + 2 * pad - ks) // stride + 1, (Win + 2 * pad - ks) // stride + 1)
+    return dict(kind="conv", image=(B, H, W, Cin), geom=(ks, stride, pad, ups, Ho, Wo)), B * Ho * Wo, ks * ks * Cin, Ho * Wo
+
+
+def _build_gemm_cases():
+    cs = []
+    # what the heuristic takes below: 64-row tiles on eight waves (four at 128 columns), the 4-stage ring from 8 K tiles on
+    H41, H43, H22 = "gemm160_kernel<4, 1, false, 2, 5>", "gemm160_kernel<4, 1, false, 4, 5>", "gemm160_kernel<2, 2, false, 2, 4>"
+    # linear, 160-wide: M = 300 leaves a ragged last tile for every tile height, K = 64 / 128 fewer K tiles than ring stages
+    for v in (22, 23, 24, 25, 41, 43, 44, 82, 83, 48, 47, 0):
+        for (M, N, K) in ((1, 160, 64), (77, 160, 128), (300, 320, 320)):
+            for e in ((EPI_FULL,) if M != 300 else (EPI_NONE, EPI_FULL, EPI_GELU, EPI_RELU)):
+                cs.append(_wide(f"lin160-v{v}-{M}x{N}x{K}-{_epi_name(e)}", "lin160", v, 0, M, N, K, kernel=H41 if v == 0 else None, **e))
+    for s in (2, 4, 8):                                  # five K tiles: 3 + 2, 2 + 2 + 1, 1 x 5 (real_splits < splits)
+        for v, e in ((44, EPI_FULL), (41, EPI_NONE), (25, EPI_FULL), (0, EPI_GELU)):
+            cs.append(_wide(f"lin160-v{v}-split{s}-300x320x320-{_epi_name(e)}", "lin160", v, s, 300, 320, 320,
+                            kernel=H41 if v == 0 else None, **e))
+    # GEGLU: pairs (g = 2) on the wide-tile kernels, groups of 32 on the register-staged one
+    for v in (84, 44, 24, 22, 0):
+        cs.append(_wide(f"geglu-v{v}-300x640x320", "geglu", v, 0, 300, 640, 320, act=ACT_GEGLU, bias=True, kernel=H41 if v == 0 else None))
+    cs.append(_mk("geglu-reg-300x256x320", "geglu", "gemm_conv_kernel<2, 2, false>", 300, 256, 320, act=ACT_GEGLU, bias=True))
+    # 128-wide
+    for v in (44, 24, 22, 48, 47):
+        for (N, K) in ((256, 128), (384, 512)):
+            cs.append(_wide(f"lin128-v{v}-300x{N}x{K}-silu-rv-res", "lin128", v, 0, 300, N, K, **EPI_FULL))
+    cs.append(_wide("lin128-v0-300x384x128-plain", "lin128", 0, 0, 300, 384, 128, kernel=H22))
+    cs.append(_wide("lin128-v22-split2-300x256x512-gelu", "lin128", 22, 2, 300, 256, 512, **EPI_GELU))
+    # register-staged: ragged M and N, bias per row, all four activations
+    for t, (tm, tn) in ((22, (2, 2)), (21, (2, 1)), (12, (1, 2)), (11, (1, 1))):
+        k = f"gemm_conv_kernel<{tm}, {tn}, false>"
+        for e, extra in ((EPI_FULL, {}), ({22: EPI_NONE, 21: EPI_GELU, 12: EPI_RELU, 11: EPI_NONE}[t], dict(bias=True, bias_per_row=True))):
+            cs.append(_mk(f"reg-t{t}-301x200x192-{_epi_name(e)}{'-bias-per-row' if extra else ''}", "reg", k, 301, 200, 192, tile=t,
+                          **{**e, **extra}))
+    # ldc = N + 12 is no multiple of 8: the scalar store path of the register-staged kernel (every other case takes the 16-byte one)
+    cs.append(_mk("reg-t11-301x200x192-silu-rv-res-ldc212", "reg", "gemm_conv_kernel<1, 1, false>", 301, 200, 192, tile=11, ldc_pad=12,
+                  **EPI_FULL))
+    cs.append(_mk("reg-t0-301x200x192-silu-rv-res", "reg", "gemm_conv_kernel<1, 1, false>", 301, 200, 192, **EPI_FULL))
+    # ABI fields (linear)
+    for v in (0, 44, 22):
+        kn = dict(kernel=H41) if v == 0 else {}
+        cs.append(_wide(f"abi-ksplit64+64-v{v}", "abi", v, 0, 300, 320, 128, k_split=64, bias=True, **kn))
+        cs.append(_wide(f"abi-ksplit64+256-v{v}", "abi", v, 0, 300, 320, 320, k_split=64, **EPI_FULL, **kn))
+        cs.append(_wide(f"abi-zero100-v{v}", "abi", v, 0, 300, 320, 320, zero_rows=100, **EPI_FULL, **kn))
+        cs.append(_wide(f"abi-zero256-v{v}", "abi", v, 0, 300, 320, 320, zero_rows=256, **EPI_FULL, **kn))
+        cs.append(_wide(f"abi-res150-v{v}", "abi", v, 0, 300, 320, 320, res_rows=150, **EPI_FULL, **kn))
+        cs.append(_wide(f"abi-tail480-v{v}", "abi", v, 0, 200, 480, 128, n_split=320, bias=True, **kn))
+        cs.append(_wide(f"abi-tail384-v{v}", "abi", v, 0, 200, 384, 128, n_split=256, bias=True, **(dict(kernel=H22) if v == 0 else {})))
+    cs.append(_wide("abi-res150-zero150-split2", "abi", 24, 2, 300, 320, 320, res_rows=150, zero_rows=150, **EPI_FULL))
+    cs.append(_wide("abi-zero100-split2", "abi", 41, 2, 300, 320, 320, zero_rows=100, **EPI_FULL))
+    cs.append(_wide("abi-ksplit64+256-split4", "abi", 22, 4, 300, 320, 320, k_split=64, **EPI_FULL))
+    # LayerNorm fold (M = 77): statistics from fp64 sums rounded to fp32 ("f64"), from ops.ln_rowstats ("rowstats"), and with 4
+    # added to the row mean of x ("shifted": the two large terms cancel)
+    for K in (320, 640):
+        for v in (0, 44, 25):
+            kn = dict(kernel=H41 if K == 320 else H43) if v == 0 else {}
+            cs.append(_wide(f"abi-ln{K}-v{v}-plain", "abi", v, 0, 77, 320, K, ln="f64", bias=True, **kn))
+            cs.append(_wide(f"abi-ln{K}-v{v}-geglu", "abi", v, 0, 77, 640, K, ln="f64", bias=True, act=ACT_GEGLU, **kn))
+        cs.append(_wide(f"abi-ln{K}-tail", "abi", 0, 0, 77, 480, K, ln="f64", bias=True, n_split=320, kernel=H41 if K == 320 else H43))
+        cs.append(_wide(f"abi-ln{K}-ln_out", "abi", 0, 0, 77, 320, K, ln="f64", bias=True, ln_out=True, kernel=H41 if K == 320 else H43))
+        cs.append(_wide(f"abi-ln{K}-shifted", "abi", 24, 0, 77, 320, K, ln="shifted", bias=True))
+    cs.append(_wide("abi-ln320-rowstats", "abi", 0, 0, 77, 320, 320, ln="rowstats", bias=True, kernel=H41))
+    cs.append(_wide("abi-ln640-split2", "abi", 22, 2, 77, 320, 640, ln="f64", bias=True, act=ACT_GELU))
+    # side outputs
+    for N in (320, 640):
+        for s in (0, 2):
+            cs.append(_wide(f"abi-ln_out-128x{N}x320-split{s}", "abi", 44 if s else 0, s, 128, N, 320, ln_out=True, bias=True, res=True,
+                            kernel=None if s else H41))
+            cs.append(_wide(f"abi-gn_out-128x{N}x320-split{s}", "abi", 24 if s else 0, s, 128, N, 320, gn_out=True, bias=True, res=True,
+                            kernel=None if s else H41))
+    cs.append(_wide("abi-wtiled-300x320x320", "abi", 0, 0, 300, 320, 320, w_tiled=True, kernel=H41, **EPI_FULL))
+    cs.append(_wide("abi-wtiled-300x256x128", "abi", 0, 0, 300, 256, 128, w_tiled=True, kernel=H22, **EPI_FULL))
+    # implicit convolution (B = 2, N = 160)
+    conv_epi = dict(bias=True, act=ACT_SILU, rowvec=True, res=True)
+    geoms = (("s2p1-10x8", dict(H=10, W=8, stride=2)), ("s1p1-9x7", dict(H=9, W=7)), ("ups-5x6", dict(H=5, W=6, ups=1)),
+             ("s2p0-outhw-10x8", dict(H=10, W=8, stride=2, pad=0, out_hw=(5, 4))))
+    for v in (22, 24, 44, 41, 43, 82, 83, 23, 25, 48, 47, 0):
+        for Cin in (64, 128):                                # 128: two channel blocks per tap, a K tile is not a whole tap
+            for gname, g in geoms:
+                geo, M, K, hw = _conv_geom(2, g["H"], g["W"], Cin, 3, g.get("stride", 1), g.get("pad", 1), g.get("ups", 0), g.get("out_hw"))
+                # (the heuristic: 4-stage ring at nine K tiles; at 18 every 64-row tile form -- forced or not -- splits four ways,
+                #  5 + 5 + 5 + 3, and the heuristic keeps the ring for the stride-2 forms only)
+                hk = "gemm160_kernel<4, 1, true, 2, 5>" if Cin == 128 and g.get("stride", 1) == 1 else "gemm160_kernel<4, 1, true, 4, 5>"
+                cs.append(_wide(f"conv-v{v}-c{Cin}-{gname}", "conv", v, 0, M, 160, K, conv=True, rows_per_rv=hw, kernel=hk if v == 0 else None,
+                                hsplit=4 if Cin == 128 and v in (0, 22, 23, 41, 43) else 0, **conv_epi, **geo))
+    for v in (22, 24, 44, 48, 47):                       # the same on 128-wide tiles (the VAE's convolutions)
+        for gname, g in geoms[:2]:
+            geo, M, K, hw = _conv_geom(2, g["H"], g["W"], 64, 3, g.get("stride", 1))
+            cs.append(_wide(f"conv-n128-v{v}-c64-{gname}", "conv", v, 0, M, 128, K, conv=True, rows_per_rv=hw, **conv_epi, **geo))
+    # the 3x3 patch kernel: whole-row tiles, pixel tiles (pt_w 32 / 16), the two-block split of Cin = 192
+    for v in (99, 98, 96, 0):
+        for Cin in (128, 192):
+            for (B, H, W) in ((2, 16, 16), (1, 8, 32), (1, 4, 64), (1, 8, 96), (1, 16, 48)):
+                geo, M, K, hw = _conv_geom(B, H, W, Cin)
+                for s in ((0, 2) if Cin == 192 else (0,)):
+                    cs.append(_wide(f"patch-v{v}-c{Cin}-{B}x{H}x{W}" + (f"-split{s}" if s else ""), "patch", v, s, M, 160, K, conv=True,
+                                    rows_per_rv=hw, kernel="conv3x3_patch_ws_kernel<0, 3>" if v == 0 else None, **conv_epi, **geo))
+    for two in (False, True):
+        for silu in (False, True):
+            geo, M, K, hw = _conv_geom(1, 8, 32, 128)
+            cs.append(_wide(f"patch-prologue-{'64+64' if two else '128'}{'-silu' if silu else ''}", "patch", 0, 0, M, 160, K, conv=True,
+                            rows_per_rv=hw, gn_pro=(64 if two else 128, silu), kernel=f"conv3x3_patch_ws_kernel<{2 if silu else 1}, 2>", base_kernel="conv3x3_patch_ws_kernel<0, 3>",
+                            **conv_epi, **geo))
+    for keep in (True, False):
+        geo, M, K, hw = _conv_geom(4, 16, 16, 128)
+        cs.append(_wide(f"patch-gnf-{'raw-kept' if keep else 'raw-skipped'}", "patch", 0, 2, M, 640, K, conv=True, rows_per_rv=hw, gnf=keep,
+                        bias=True, rowvec=True, res=keep, kernel="conv3x3_patch_ws_kernel<0, 3>", **geo))
+    geo, M, K, hw = _conv_geom(2, 16, 16, 128)
+    cs.append(_wide("patch-wtiled-c128-2x16x16", "patch", 0, 0, M, 160, K, conv=True, rows_per_rv=hw, w_tiled=True,
+                    kernel="conv3x3_patch_ws_kernel<0, 3>", **conv_epi, **geo))
+    # narrow convolution (N <= 16): 64-pixel segments of an image row
+    for N in (4, 3):
+        for (B, H, W) in ((2, 9, 7), (1, 3, 70)):
+            geo, M, K, hw = _conv_geom(B, H, W, 64)
+            cs.append(_mk(f"narrow-n{N}-{B}x{H}x{W}", "narrow", "conv3x3_narrow_kernel", M, N, K, bias=True, rows_per_rv=hw, **geo))
+    assert len({c["id"] for c in cs}) == len(cs)
+    return cs
+
+
+GEMM_CASES = _build_gemm_cases()
+GEMM_CASE = {c["id"]: c for c in GEMM_CASES}
+
+
+def gemm_case_record(c):
+    """the 24 integers of lib.hip.ops.TRACE_FIELDS a launch of the case leaves (what a record cannot express -- LayerNorm fold,
+    transposed tail, prologue, tiled weights, ln_out -- is left out: the base record)"""
+    B, H, W, Cin = c["image"] or (0, 0, 0, 0)
+    ks, stride, pad, ups, Ho, Wo = c["geom"] or (0, 0, 0, 0, 0, 0)
+    gnf = 0 if c["gnf"] is None else 1 if c["gnf"] else 2
+    return (c["M"], c["N"], c["K"], c["act"], int(c["bias"]), int(c["rowvec"]), int(c["res"]), int(c["bias_per_row"]), ks, stride, pad,
+            ups, B, H, W, Cin, Ho, Wo, c["rows_per_rv"], c["k_split"], c["zero_rows"], int(c["gn_out"]), gnf, c["res_rows"])
+
+
+@functools.lru_cache(maxsize=None)
+def gemm_problem(cid):
+    """the seeded fp16 operands of one case (CPU): unit Gaussians against K^-0.5 weights, logical tensors only (gemm_operands
+    puts them into the poisoned buffers a launch sees).  Do not modify the result."""
+    c = GEMM_CASE[cid]
+    M, N, K = c["M"], c["N"], c["K"]
+    # (seeded from the id without its variant / split part: the cases of one problem share their operands, so the GPU file can
+    #  hold a forced variant against the heuristic and a split launch against the unsplit one)
+    g = torch.Generator().manual_seed(zlib.crc32(gemm_problem_key(cid).encode()))
+    rn = lambda *s: torch.randn(s, generator=g)
+    p = dict(case=c, A2=None, bias=None, rowvec=None, R=None, gn_table=None)
+    if c["kind"] == "conv":
+        B, H, W, Cin = c["image"]
+        c1 = c["gn_pro"][0] if c["gn_pro"] is not None else Cin
+        x = rn(B, H, W, Cin) + (0.5 if c["gn_pro"] is not None else 0.0)
+        p["A"] = x[..., :c1].half()
+        if c1 < Cin:
+            p["A2"] = x[..., c1:].half()
+        if c["gn_pro"] is not None:      # GroupNorm(32) table of the concat in fp64, rounded to fp32: scale = rstd gamma, shift = beta - mean scale
+            xc = x.half().double().reshape(B, H * W, 32, Cin // 32)
+            mean = xc.mean((1, 3), keepdim=True)
+            rstd = 1.0 / torch.sqrt((xc * xc).mean((1, 3), keepdim=True) - mean * mean + 1e-5)
+            gamma, beta = (1 + 0.2 * rn(Cin)).double().reshape(32, -1), (0.1 * rn(Cin)).double().reshape(32, -1)
+            scale = (rstd[:, 0] * gamma).reshape(B, Cin)
+            shift = (beta - mean[:, 0] * rstd[:, 0] * gamma).reshape(B, Cin)
+            p["gn_table"] = torch.stack([scale, shift], 1).float()
+            act = ACT_SILU if c["gn_pro"][1] else ACT_NONE
+            xx, tab = x.half(), p["gn_table"]
+            v64 = activation_ref(xx.double() * tab[:, None, None, 0].double() + tab[:, None, None, 1].double(), act, torch.float64)
+            v32 = activation_ref(xx.float() * tab[:, None, None, 0] + tab[:, None, None, 1], act, torch.float32)
+            p["pro_delta"] = fp32_allowance(v64, v32)
+    else:
+        zr = c["zero_rows"]
+        x = rn(M - zr, K) + (0.5 if c["ln"] is not None else 0.0) + (4.0 if c["ln"] == "shifted" else 0.0)
+        ks_ = c["k_split"] or K
+        p["A"] = x[:, :ks_].half()
+        if c["k_split"]:
+            p["A2"] = x[:, ks_:].half()
+    p["W"] = (rn(N, K) * K ** -0.5).half()                                # logical rows: [x | gate] halves for GEGLU
+    if c["bias"]:
+        p["bias"] = (0.5 * rn(M if c["bias_per_row"] else N)).half()
+    if c["rowvec"]:
+        p["rowvec"] = (0.5 * rn(-(-M // c["rows_per_rv"]), N)).half()
+    n_out = N // 2 if c["act"] == ACT_GEGLU else N
+    if c["res"]:
+        p["R"] = rn(c["res_rows"] or M, n_out).half()
+    if c["gnf"] is not None:
+        p["gnf_gamma"], p["gnf_beta"] = (1 + 0.2 * rn(N)).half(), (0.1 * rn(N)).half()
+    return p
+
+
+def gemm_problem_key(cid):
+    return re.sub(r"-(v\d+|t\d+|split\d+)(?=-|$)", "", cid)
+
+
+def gemm_ln_args(p):
+    """the ln_stats array (f32 [M, K / 160, 2]) of a LayerNorm-fold case from fp64 sums rounded to fp32, so that norm.hip is
+    not under test"""
+    x = p["A"].double()
+    M, K = x.shape
+    v = x.reshape(M, K // 160, 160)
+    return torch.stack([v.sum(-1), (v * v).sum(-1)], -1).float().contiguous()
+
+
+def gemm_operands(p, poison=True):
+    """what a launch of the case is handed (CPU tensors; the GPU file moves the buffers): dict of name -> (buffer, view spec).
+    A / A2 are the leading rows and a column slice of larger buffers; the rows in front, the rows behind and the columns outside
+    hold the NaN patterns of _POISON (zeros with poison=False); W has eight such rows behind N where N is no multiple of 64.
+    GEGLU weights / bias are packed for the serving kernel, w_tiled weights tiled, here, from the header's description."""
+    c = p["case"]
+    N, K = c["N"], c["K"]
+    o = {}
+
+    def put(name, data, rb=3, ra=5, c0=8, extra=16):
+        shp = data.shape
+        d2 = data.reshape(-1, shp[-1])
+        o[name] = (_embed(d2, rb, ra, c0, shp[-1] + extra, poison), (rb, d2.shape[0], c0, shp[-1], tuple(shp)))
+
+    # rows in front of the view: every virtual row below zero_rows (A / A2 point at row zero_rows: "never read"); for an image
+    # the row of pixels above the first one and the one behind the last (where a clamped or unmasked tap would land)
+    rb = max(3, c["zero_rows"]) if c["kind"] == "lin" else c["image"][2] + 3
+    ra = 5 if c["kind"] == "lin" else c["image"][2] + 5
+    put("A", p["A"], rb=rb, ra=ra)
+    if p["A2"] is not None:
+        put("A2", p["A2"], rb=rb, ra=ra, c0=16, extra=24)                 # lda2 != lda
+    W, bias = p["W"], p["bias"]
+    if c["act"] == ACT_GEGLU:
+        g = 2 if N % 160 == 0 else 32
+        W = geglu_pack(W[:N // 2], W[N // 2:], g)
+        if bias is not None:
+            bias = geglu_pack(bias[:N // 2, None], bias[N // 2:, None], g).reshape(-1)
+    if c["w_tiled"]:
+        W = w_tiled_pack(W, 160 if N % 160 == 0 else 128)
+    put("W", W, rb=0, ra=8 if N % 64 else 0, c0=0, extra=0)
+    o["bias"] = bias
+    return o
+
+
+def gemm_view(buf, spec):
+    rb, rows, c0, cols, shp = spec
+    return buf[rb:rb + rows].view(*shp[:-1], buf.shape[1])[..., c0:c0 + cols]
+
+
+def parse_dispatch_sweep(text):
+    """`emu_gemm --dispatch --sweep` output -> {(record, variant, splits): (return value, kernel, splits, kt_per_split, reduction kernel)}"""
+    out = {}
+    for line in text.splitlines():
+        m = re.match(r"^((?:-?\d+ ){24})v (\d+) s (\d+) -> (-?\d+)(.*)$", line)
+        if not m:
+            continue
+        rec = tuple(int(t) for t in m.group(1).split())
+        launches = [l.strip() for l in m.group(5).split(" | ")[1:]]
+        kern = sp = kt = red = None
+        if launches:
+            kern = launches[0].split(" grid ")[0]
+            sp, kt = int(re.search(r"splits=(\d+)", launches[0]).group(1)), int(re.search(r"kt_per_split=(\d+)", launches[0]).group(1))
+            red = launches[1].split(" grid ")[0] if len(launches) > 1 else None
+        out[(rec, int(m.group(2)), int(m.group(3)))] = (int(m.group(4)), kern, sp, kt, red)
+    return out
+
+
+def gemm_case_is_wide(c):
+    """served by the wide-tile kernels of csrc/gemm_glds.hip (else: the register-staged / narrow kernels of csrc/gemm_conv.hip)"""
+    return not c["kernel"].startswith(("gemm_conv_kernel<", "conv3x3_narrow_kernel"))
+
+
+def gemm_mutant_applies(mutant, c):
+    """does the wrong variant differ from the right one on a case of this kind at all?"""
+    conv = c["kind"] == "conv"
+    ks, stride, pad, ups, Ho, Wo = c["geom"] or (0, 0, 0, 0, 0, 0)
+    return {
+        "last_k_dropped": True,
+        "pad_tap_reads_edge": conv,
+        "pad_before_normalise": c["gn_pro"] is not None,
+        "tap_crosses_sample": conv and c["image"][0] > 1 and not ups and pad > 0,
+        "rowvec_row_by_tile": c["rowvec"] and c["rows_per_rv"] % 64 != 0 and c["M"] > c["rows_per_rv"],
+        "residual_no_wrap": c["res_rows"] > 0, "residual_wrap_off_by_one": c["res_rows"] > 0,
+        "zero_rows_rounded_to_tile": c["zero_rows"] % 64 != 0,
+        "bias_after_act": c["bias"] and c["act"] != ACT_NONE,
+        "geglu_halves_swapped": c["act"] == ACT_GEGLU,
+        "ups_gather_ceil": bool(ups),
+        "k_split_second_source_offset": c["k_split"] > 0,
+        "ln_mean_of_first_part": c["ln"] is not None,
+        "tail_transposed_without_bias": c["n_split"] > 0 and c["bias"],
+    }[mutant]
+
+
+def groupnorm32_allowance(x, rows, gamma, beta, eps, silu, dx=0.0):
+    """allowance of GroupNorm(32)(+SiLU) formed in fp32 from n = rows * N / 32 values per (sample, group): the sums are fp32 sums
+    of n values in a fixed order, n u sum |v| each (u = 2^-24), so mean moves by n u mean|x| and the variance E[x^2] - mean^2 by
+    n u (E[x^2] + 2 |mean| mean|x|); y = gamma xhat + beta moves by |gamma| (rstd d_mean + |xhat| d_var / (2 (var + eps))); plus the
+    fp32 evaluation (fp32_allowance of the same formula on the CPU).  dx: the input itself is only known to within dx per element
+    (the raw result is not stored): mean moves by dx, x - mean by 2 dx, rstd by 2 dx rstd relative -- |gamma| rstd 2 dx (1 + |xhat|)."""
+    M, N = x.shape
+    n = rows * (N // 32)
+    v = x.double().reshape(M // rows, rows, 32, N // 32)
+    mean, mabs, msq = v.mean((1, 3), keepdim=True), v.abs().mean((1, 3), keepdim=True), (v * v).mean((1, 3), keepdim=True)
+    var = msq - mean * mean
+    rstd = 1.0 / torch.sqrt(var + eps)
+    xhat = ((v - mean) * rstd).abs()
+    d_mean = n * _U * mabs
+    d_var = n * _U * (msq + 2 * mean.abs() * mabs)
+    a = rstd * d_mean + xhat * 0.5 * d_var / (var + eps) + rstd * 2 * dx * (1 + xhat)
+    a = a.reshape(M, N) * gamma.double().abs() * (1.10 if silu else 1.0)
+    y64 = groupnorm32_ref(x, rows, gamma, beta, eps, silu)
+    y32 = F.group_norm(x.float().reshape(M // rows, rows, N).permute(0, 2, 1), 32, gamma.float(), beta.float(), eps).permute(0, 2, 1)
+    y32 = (F.silu(y32) if silu else y32).reshape(M, N)
+    return a + fp32_allowance(y64, y32)

@@ -1,5 +1,7 @@
 """GPU (-m gpu): individual C-ABI entry points against plain fp32 torch formulas (these are
-floating-point kernels), including the ragged / edge shapes the path produces."""
+floating-point kernels), including the ragged / edge shapes the path produces.  The GEMM / convolution tests here hold whole
+tensors to `close`; tests/test_gemm_kernels_gpu.py holds every element of every kernel instantiation behind pfd_gemm_f16 to a
+derived bound against an fp64 reference."""
 import math
 
 import pytest
