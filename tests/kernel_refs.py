@@ -1,7 +1,8 @@
 """Plain fp64 references of single kernels of the library, and the seeded operands the kernel-level tests run them on: the
 SeeCoder side (tests/test_encoder_kernels_cpu.py pins the references to the oracle, tests/test_encoder_kernels_gpu.py
-compares the HIP kernels with them) and the fused attention family (tests/test_attention_kernels_{cpu,gpu}.py, the last
-section).  Everything here is torch on whatever device the operands live on; nothing imports the
+compares the HIP kernels with them), the fused attention family (tests/test_attention_kernels_{cpu,gpu}.py), the GEMM /
+convolution kernels (tests/test_gemm_kernels_{cpu,gpu}.py) and the stand-alone GroupNorm kernels
+(tests/test_norm_kernels_{cpu,gpu}.py, the last section).  Everything here is torch on whatever device the operands live on; nothing imports the
 native library.  A plain module, not a conftest: the two test files import it by name."""
 import functools
 import re
@@ -1140,3 +1141,348 @@ def groupnorm32_allowance(x, rows, gamma, beta, eps, silu, dx=0.0):
     y32 = F.group_norm(x.float().reshape(M // rows, rows, N).permute(0, 2, 1), 32, gamma.float(), beta.float(), eps).permute(0, 2, 1)
     y32 = (F.silu(y32) if silu else y32).reshape(M, N)
     return a + fp32_allowance(y64, y32)
+
+
+# ------------------------------------------------------------------------------------------------
+# stand-alone GroupNorm (csrc/norm.hip: pfd_groupnorm_f16, pfd_groupnorm_pstats_f16, pfd_groupnorm_table_f16): reference, the
+# host's decisions restated, bound, mutants, cases and operands
+# (tests/test_norm_kernels_cpu.py pins and qualifies them, tests/test_norm_kernels_gpu.py uses them)
+# ------------------------------------------------------------------------------------------------
+GN_ROWS, GN_MAX_CHUNKS, GN_MAX_G, GNS_T, GNS_MAX = 8, 256, 64, 1024, 8       # the constants of csrc/norm.hip
+GN_FORMS = ("small", "two", "pstats_par", "pstats_plain")
+# the kernels a form launches, in the spelling of `emu_norm --dispatch`
+GN_FORM_KERNELS = {"small": ("gn_small_kernel",), "two": ("gn_stats_kernel", "gn_apply_kernel"),
+                   "pstats_par": ("gn_apply_pstats_kernel<true>",), "pstats_plain": ("gn_apply_pstats_kernel<false>",),
+                   "table": ("gn_stats_kernel", "gn_table_kernel")}
+GN_MUTANTS = ("last_row_dropped", "last_row_twice", "chunk_last_row_dropped", "second_slot_skipped", "count_from_c1",
+              "group_by_source", "eps_1e-5", "eps_omitted", "var_not_clamped", "silu_before_affine", "slab_without_sample_offset",
+              "second_producer_group_dropped")
+
+
+def gn_chunks(B, C, HW):
+    """gn_chunks() of csrc/norm.hip restated: (nchunks, rows_per_chunk) of the two-launch and producer-statistics forms"""
+    nvec = C // 8
+    RT = 256 // nvec if nvec < 256 else 1
+    nchunks = min(-(-512 // B), -(-HW // (RT * 4)), GN_MAX_CHUNKS)
+    nchunks = max(nchunks, 1)
+    rpc = -(-HW // nchunks)
+    return -(-HW // rpc), rpc
+
+
+def gn_is_small(B, C, HW, G):
+    cpg = C // G
+    return cpg % 4 == 0 and cpg >= 32 and HW * (cpg // 4) <= GNS_T * GNS_MAX and B * G >= 128
+
+
+def gn_takes_pstats(B, C1, C2, HW, G):
+    """pfd_groupnorm_takes_pstats restated"""
+    if B <= 0 or C1 <= 0 or C2 < 0 or HW <= 0 or G <= 0 or G > GN_MAX_G:
+        return False
+    C = C1 + C2
+    if C % G or C > 4096 or HW % 64 or C1 % 160 or C2 % 160 or C1 % 32 or C2 % 32:
+        return False
+    if gn_is_small(B, C, HW, G):
+        return False
+    cpg, cpp1 = C // G, C1 // 32
+    cpp2 = C2 // 32 if C2 else cpp1
+    if cpp1 < 8 or 160 % cpp1 or cpg % cpp1 or C1 % cpg:
+        return False
+    if C2 and (cpp2 < 8 or 160 % cpp2 or cpg % cpp2):
+        return False
+    return True
+
+
+def gn_producer_groups(C1, C2, G):
+    """(npg1, npg2): producer groups (C_src / 32 channels each) per group of this norm, per source"""
+    cpg, cpp1 = (C1 + C2) // G, C1 // 32
+    cpp2 = C2 // 32 if C2 else cpp1
+    return cpg // cpp1, cpg // cpp2
+
+
+def gn_form(B, HW, C1, C2, G, pstats):
+    """the form a request takes (pstats: the caller hands over producer statistics), None: PFD_ESHAPE"""
+    if pstats:
+        if not gn_takes_pstats(B, C1, C2, HW, G):
+            return None
+        n1, n2 = gn_producer_groups(C1, C2, G)
+        return "pstats_par" if n1 <= 2 and n2 <= 2 else "pstats_plain"
+    return "small" if gn_is_small(B, C1 + C2, HW, G) else "two"
+
+
+# D, the largest number of fp32 additions between one input value and the sum of its group, from the loops of csrc/norm.hip
+# (an addition of a masked 0.f counts: it is on the chain even where it cannot round); the squares of fp16 values are exact in
+# fp32, so the sum of squares has the same chain.  Behind the two sums come three more roundings that the variance sees in full
+# (sum / count, sum of squares / count, mean * mean): + 3 in every form.
+#   two-launch   gn_stats_kernel: a thread adds GN_ROWS values per sweep of its chunk, sweeps = ceil(rows_per_chunk / (GN_ROWS RT)),
+#                RT = 256 / min(C / 8, 256) row threads per channel vector; thread rt = 0 adds the RT partials of a channel; thread g
+#                adds the C / G channels of its group.  gn_apply_kernel / gn_table_kernel: thread (part, g) adds chunks part,
+#                part + P, ... (ceil(nchunks / P), P = 256 / G), thread g the P partials.
+#                D = GN_ROWS sweeps + RT + C / G + ceil(nchunks / P) + P + 3
+#   small        gn_small_kernel: a thread adds 4 values of each of its GNS_MAX register slots, wave_sum is 6 xor exchanges, every
+#                thread adds the GNS_T / 64 wave sums.  D = 4 GNS_MAX + 6 + GNS_T / 64 + 3
+#   pstats       the tests form the producers' sums in fp64 and round them to fp32 once (1); thread (part, g) folds slabs part,
+#                part + P, ...: the plain loop ceil(nslab / P) slabs of npg producer groups each, the grouped form whole trips of 8
+#                slabs, two additions per slab (the second with weight 0 where npg = 1); thread g adds the P partials.
+#                D = 1 + npg ceil(nslab / P)  |  1 + 2 * 8 ceil(ceil(nslab / P) / 8)   + P + 3
+def gn_depth(form, B, HW, C1, C2, G):
+    C = C1 + C2
+    P = 256 // G
+    if form == "small":
+        return 4 * GNS_MAX + 6 + GNS_T // 64 + 3
+    nchunks, rpc = gn_chunks(B, C, HW)
+    if form in ("two", "table"):
+        RT = 256 // min(C // 8, 256)
+        return GN_ROWS * -(-rpc // (GN_ROWS * RT)) + RT + C // G + -(-nchunks // P) + P + 3
+    per = -(-(HW // 64) // P)
+    if form == "pstats_par":
+        return 1 + 2 * 8 * -(-per // 8) + P + 3
+    assert form == "pstats_plain", form
+    return 1 + max(gn_producer_groups(C1, C2, G)) * per + P + 3
+
+
+def _gn_cat(x1, x2, B, HW, dtype):
+    v = x1.to(dtype).reshape(B, HW, -1)
+    return v if x2 is None else torch.cat([v, x2.to(dtype).reshape(B, HW, -1)], -1)
+
+
+def _gn_stats(x1, x2, B, HW, G, eps, mutant=None, dtype=torch.float64, rpc=None, depth=None):
+    """(v [B, HW, C], mean [B, G], var [B, G], eps): the statistics of the virtual concat as sums over count, the way every
+    kernel form defines them; the wrong variants of GN_MUTANTS that concern the statistics"""
+    assert mutant is None or mutant in GN_MUTANTS, mutant
+    v = _gn_cat(x1, x2, B, HW, dtype)
+    C, C1 = v.shape[-1], x1.shape[-1]
+    cpg = C // G
+    wr, wc = torch.ones(HW, dtype=dtype, device=v.device), torch.ones(C, dtype=dtype, device=v.device)
+    count = float(HW * cpg)
+    if mutant == "last_row_dropped":
+        wr[-1] = 0
+    if mutant == "last_row_twice":
+        wr[-1] = 2
+    if mutant == "chunk_last_row_dropped":
+        wr[rpc - 1::rpc] = 0
+        wr[-1] = 0
+    if mutant == "second_slot_skipped":
+        wc[2048:] = 0
+    if mutant == "count_from_c1":
+        count = float(HW * C1) / G
+    if mutant == "second_producer_group_dropped":
+        n1, n2 = gn_producer_groups(C1, C - C1, G)
+        c = torch.arange(C)
+        cpp = torch.where(c < C1, C1 // 32, (C - C1) // 32 if C > C1 else C1 // 32)
+        npg = torch.where(c < C1, n1, n2)
+        wc[((c % cpg) // cpp == 1) & (npg >= 2)] = 0
+    S = (torch.einsum("r,brc->bc", wr, v) * wc).reshape(B, G, cpg).sum(-1)
+    Q = (torch.einsum("r,brc->bc", wr, v * v) * wc).reshape(B, G, cpg).sum(-1)
+    if mutant == "slab_without_sample_offset":
+        S, Q = S[:1].expand(B, G), Q[:1].expand(B, G)
+    mean = S / count
+    var = Q / count - mean * mean
+    if mutant == "var_not_clamped":
+        # the clamp matters once fp32 rounding has taken the difference below zero: the mutant's variance sits at the low end of
+        # what the allowance admits, D u E[x^2] below the exact one
+        var = var - depth * _U * Q / count
+    else:
+        var = var.clamp_min(0)
+    if mutant == "eps_1e-5":
+        eps = 1e-5
+    if mutant == "eps_omitted":
+        eps = 0.0
+    return v, mean, var, eps
+
+
+def groupnorm_ref(x1, x2, B, HW, G, gamma, beta, eps, silu, mutant=None, dtype=torch.float64, rpc=None, depth=None):
+    """GroupNorm(G) (+ SiLU) over the virtual channel concat [x1 | x2] of token-major [B HW, C1] / [B HW, C2] tensors (x2 may be
+    None) -> [B HW, C1 + C2] in `dtype`: per (sample, group of C / G consecutive channels of the concat) mean = sum / n,
+    var = max(sum of squares / n - mean^2, 0), y = (x - mean) / sqrt(var + eps) * gamma + beta.  mutant: one of GN_MUTANTS (rpc:
+    the rows per chunk for chunk_last_row_dropped, depth: D for var_not_clamped)."""
+    v, mean, var, eps = _gn_stats(x1, x2, B, HW, G, eps, mutant, dtype, rpc, depth)
+    C, C1 = v.shape[-1], x1.shape[-1]
+    cpg = C // G
+    gi = torch.arange(C, device=v.device) // cpg
+    if mutant == "group_by_source":
+        gi[C1:] = torch.arange(C - C1, device=v.device) // cpg
+    rstd = 1.0 / torch.sqrt(var + eps)
+    xhat = (v - mean[:, gi][:, None]) * rstd[:, gi][:, None]
+    if mutant == "silu_before_affine":
+        return (F.silu(xhat) * gamma.to(dtype) + beta.to(dtype)).reshape(B * HW, C)
+    y = xhat * gamma.to(dtype) + beta.to(dtype)
+    return (F.silu(y) if silu else y).reshape(B * HW, C)
+
+
+def groupnorm_table_ref(x1, x2, B, HW, G, gamma, beta, eps):
+    """pfd_groupnorm_table_f16: float64 [B, 2, C], scale = rstd gamma, shift = beta - mean scale"""
+    v, mean, var, eps = _gn_stats(x1, x2, B, HW, G, eps)
+    gi = torch.arange(v.shape[-1]) // (v.shape[-1] // G)
+    scale = (1.0 / torch.sqrt(var + eps))[:, gi] * gamma.double()
+    return torch.stack([scale, beta.double() - mean[:, gi] * scale], 1)
+
+
+def groupnorm_allowance(x1, x2, B, HW, G, gamma, beta, eps, silu, D, parts=False):
+    """groupnorm32_allowance with the number of values per group replaced by D (gn_depth): a sum whose every input passes
+    through at most D fp32 additions is off by at most D u sum |v| (first order; Higham, Accuracy and Stability, 4.2), so mean
+    moves by d_mean = D u mean|x| and the variance E[x^2] - mean^2 by d_var = D u (E[x^2] + 2 |mean| mean|x|); y = gamma xhat +
+    beta moves by |gamma| (rstd d_mean + |xhat| d_var / (2 (var + eps))); plus the fp32 evaluation (fp32_allowance of torch's
+    F.group_norm (+ F.silu) in fp32 on the CPU against the fp64 reference).  Returns a [B HW, C]; parts=True: (a, a_scale,
+    a_shift), the last two [B, C]: the statistics part for the table -- scale = rstd gamma moves by |scale| d_var / (2 (var + eps)),
+    shift = beta - mean scale by |scale| d_mean + |mean| d_scale, each plus 8 u of its terms (rsqrtf, the quotients and products)."""
+    v, mean, var, _ = _gn_stats(x1, x2, B, HW, G, eps)
+    C = v.shape[-1]
+    cpg = C // G
+    vg = v.reshape(B, HW, G, cpg)
+    mabs, msq = vg.abs().mean((1, 3)), (vg * vg).mean((1, 3))
+    rstd = 1.0 / torch.sqrt(var + eps)
+    d_mean = D * _U * mabs
+    d_rstd_rel = 0.5 * D * _U * (msq + 2 * mean.abs() * mabs) / (var + eps)
+    gi = torch.arange(C) // cpg
+    xhat = ((v - mean[:, gi][:, None]) * rstd[:, gi][:, None]).abs()
+    a = (rstd * d_mean)[:, gi][:, None] + xhat * d_rstd_rel[:, gi][:, None]
+    a = (a * gamma.double().abs() * (1.10 if silu else 1.0)).reshape(B * HW, C)
+    y64 = groupnorm_ref(x1, x2, B, HW, G, gamma, beta, eps, silu)
+    y32 = F.group_norm(v.float().permute(0, 2, 1), G, gamma.float(), beta.float(), eps).permute(0, 2, 1)
+    y32 = (F.silu(y32) if silu else y32).reshape(B * HW, C)
+    a = a + fp32_allowance(y64, y32)
+    if not parts:
+        return a
+    scale = rstd[:, gi] * gamma.double()
+    a_scale = scale.abs() * d_rstd_rel[:, gi] + 8 * _U * scale.abs()
+    ms = (mean[:, gi] * scale).abs()
+    a_shift = scale.abs() * d_mean[:, gi] + mean[:, gi].abs() * a_scale + 8 * _U * (beta.double().abs() + ms)
+    return a, a_scale, a_shift
+
+
+def _gnc(cid, form, B, HW, C1, C2=0, G=32, eps=1e-5, silu=True, strides=None, kind="unit", shares=None, table=False):
+    return dict(id=cid, form=form, B=B, HW=HW, C1=C1, C2=C2, G=G, eps=eps, silu=silu, strides=strides, kind=kind, shares=shares,
+                table=table or form == "two")
+
+
+# (id, expected form, B, HW, C1, C2, G, eps, silu, strides = the pad columns of x / x2 / y, input kind); `shares`: the case takes
+# the leading samples of that case's operands; `table`: pfd_groupnorm_table_f16 runs on the case's operands too (every
+# two-launch case and two small-form shapes)
+GN_CASES = [
+    _gnc("small-B4-HW64-C1280", "small", 4, 64, 1280, table=True),                     # B G exactly 128
+    _gnc("small-B4-HW64-C1280+640", "small", 4, 64, 1280, 640, kind="offset6"),          # cpg 60: a group straddles the sources
+    _gnc("small-B4-HW819-C1280", "small", 4, 819, 1280, silu=False),                    # 8190 of 8192 chunks, all eight slots
+    _gnc("small-B4-HW100-C1408", "small", 4, 100, 1408, kind="tiny", table=True),       # cpr 11
+    _gnc("small-B2-HW16-C2048-G64", "small", 2, 16, 2048, G=64, kind="const"),
+    _gnc("small-B4-HW9-C1024+256-strided", "small", 4, 9, 1024, 256, strides=(8, 16, 24)),
+    _gnc("two-B4-HW820-C1280", "two", 4, 820, 1280),                                    # one row past the small form
+    _gnc("two-B3-HW64-C1280", "two", 3, 64, 1280, shares="small-B4-HW64-C1280"),        # B G = 96
+    _gnc("two-B2-HW30-C320+640", "two", 2, 30, 320, 640, kind="offset6"),               # cpg 30, 16 idle threads
+    _gnc("two-B1-HW64-C1280+1280", "two", 1, 64, 1280, 1280, silu=False),               # second vector slot
+    _gnc("two-B1-HW5-C4096", "two", 1, 5, 4096),                                        # both slots full, chunks of 3 and 2 rows
+    _gnc("two-B1-HW1089-C128-eps1e-6", "two", 1, 1089, 128, eps=1e-6, kind="tiny"),     # the VAE's cpg 4 at 33 x 33, ragged last chunk
+    _gnc("two-B1-HW4096-C320", "two", 1, 4096, 320, kind="offset6", silu=False),
+    _gnc("two-B3-HW37-C256", "two", 3, 37, 256, kind="const"),
+    _gnc("two-B2-HW1-C64-G8", "two", 2, 1, 64, G=8),
+    _gnc("two-B2-HW50-C192-G24", "two", 2, 50, 192, G=24),                              # P = 10
+    _gnc("two-B2-HW33-C64-G1", "two", 2, 33, 64, G=1, kind="offset6"),
+    _gnc("two-B1-HW1100-C2048", "two", 1, 1100, 2048, silu=False),                      # the GN_MAX_CHUNKS cap
+    _gnc("two-B2-HW45-C320+192-strided", "two", 2, 45, 320, 192, strides=(8, 16, 24)),
+    _gnc("pstats-B1-HW4096-C320", "pstats_par", 1, 4096, 320),
+    _gnc("pstats-B2-HW1024-C320+320", "pstats_par", 2, 1024, 320, 320, kind="offset6"),
+    _gnc("pstats-B2-HW256-C640", "pstats_par", 2, 256, 640, silu=False),                # clamped slab slots
+    _gnc("pstats-B1-HW4608-C320", "pstats_par", 1, 4608, 320, kind="tiny"),             # second trip of the fold
+    _gnc("pstats-B2-HW128-C1280+1280", "pstats_par", 2, 128, 1280, 1280),
+    _gnc("pstats-B2-HW256-C320-G8", "pstats_plain", 2, 256, 320, G=8),
+    _gnc("pstats-B2-HW256-C640+640-G16", "pstats_plain", 2, 256, 640, 640, G=16, kind="offset6", silu=False),
+    _gnc("pstats-B2-HW128-C1280+640-G24", "pstats_plain", 2, 128, 1280, 640, G=24),     # producer groups of 40 | 20 channels
+]
+GN_CASE = {c["id"]: c for c in GN_CASES}
+assert len(GN_CASE) == len(GN_CASES)
+GN_EDGE_GAIN = 4.0
+
+
+def gn_edge_rows(c):
+    """the rows a wrong row count would lose or count twice: the first and last of a sample, both sides of every chunk
+    boundary (gn_chunks) and, where producer statistics are folded, of every 64-row slab"""
+    nchunks, rpc = gn_chunks(c["B"], c["C1"] + c["C2"], c["HW"])
+    rows = {0, c["HW"] - 1}
+    step = [rpc] + ([64] if c["form"].startswith("pstats") else [])
+    for s in step:
+        for k in range(s, c["HW"], s):
+            rows.update((k - 1, k))
+    return sorted(rows)
+
+
+def gn_depth_of(c, table=False):
+    return gn_depth("table" if table else c["form"], c["B"], c["HW"], c["C1"], c["C2"], c["G"])
+
+
+@functools.lru_cache(maxsize=None)
+def gn_problem(cid):
+    """the seeded fp16 operands of one case (CPU): x1 [B HW, C1], x2 [B HW, C2] | None, gamma = 1 + 0.2 randn, beta = 0.1 randn.
+    kinds: unit (randn + 0.5) | offset6 (6 + 0.5 randn) | tiny (zero mean, std 1e-3 .. 3e-3 per channel) | const (unit, with group
+    0 constant at 3.0 -- every sum exact -- and group 1 at fp16(2.7), whose sums round).  The deviation from the offset is
+    GN_EDGE_GAIN times larger on gn_edge_rows.  Do not modify the result."""
+    c = GN_CASE[cid]
+    if c["shares"]:
+        q = gn_problem(c["shares"])
+        n = c["B"] * c["HW"]
+        assert q["case"]["HW"] == c["HW"] and q["case"]["C1"] == c["C1"] and q["x2"] is None and c["C2"] == 0
+        assert gn_edge_rows(c) == gn_edge_rows(q["case"])
+        return dict(q, case=c, x1=q["x1"][:n])
+    B, HW, C1, C2, G = c["B"], c["HW"], c["C1"], c["C2"], c["G"]
+    C = C1 + C2
+    g = torch.Generator().manual_seed(zlib.crc32(cid.encode()))
+    dev = torch.randn((B, HW, C), generator=g)
+    dev[:, gn_edge_rows(c)] *= GN_EDGE_GAIN
+    if c["kind"] == "offset6":
+        x = 6.0 + 0.5 * dev
+    elif c["kind"] == "tiny":
+        x = dev * (1e-3 + 2e-3 * torch.rand(C, generator=g))
+    else:
+        x = dev + 0.5
+    if c["kind"] == "const":
+        cpg = C // G
+        x[..., :cpg] = 3.0
+        x[..., cpg:2 * cpg] = 2.7
+    x = x.half().reshape(B * HW, C)
+    gamma, beta = (1 + 0.2 * torch.randn(C, generator=g)).half(), (0.1 * torch.randn(C, generator=g)).half()
+    return dict(case=c, x1=x[:, :C1].contiguous(), x2=x[:, C1:].contiguous() if C2 else None, gamma=gamma, beta=beta)
+
+
+def gn_args(p):
+    """the positional arguments of groupnorm_ref / groupnorm_allowance up to silu"""
+    c = p["case"]
+    return (p["x1"], p["x2"], c["B"], c["HW"], c["G"], p["gamma"], p["beta"], c["eps"], c["silu"])
+
+
+def gn_operands(p, poison=True):
+    """what a launch is handed (CPU): x1 / x2 as [B, HW, C] views; with strides, column slices (offset 8) of wider buffers that
+    hold fp16 NaNs (zeros with poison=False) in the pad columns and in two rows in front and three behind"""
+    c = p["case"]
+    out = {}
+    for k, pad in (("x1", 0), ("x2", 1)):
+        t = p[k]
+        if t is None:
+            out[k] = None
+        elif c["strides"] is None:
+            out[k] = t.view(c["B"], c["HW"], -1)
+        else:
+            buf = _embed(t, 2, 3, 8, t.shape[1] + 8 + c["strides"][pad], poison)
+            out[k] = (buf, (2, t.shape[0], 8, t.shape[1], (c["B"], c["HW"], t.shape[1])))
+    return out
+
+
+def gn_pstats(x):
+    """the producer statistics of one source, float32 [B HW / 64, C / 160, 16, 2]: gn_out_ref of the f16 values (fp64 sums)
+    rounded to fp32 once; the slots no producer writes stay NaN"""
+    return gn_out_ref(x).float().contiguous()
+
+
+def gn_mutant_applies(mutant, c):
+    """does the wrong variant differ from the right one on this case, by more than an fp32 rounding?"""
+    C = c["C1"] + c["C2"]
+    ps = c["form"].startswith("pstats")
+    return {
+        "last_row_dropped": not ps, "last_row_twice": not ps,
+        "chunk_last_row_dropped": c["form"] == "two" and gn_chunks(c["B"], C, c["HW"])[0] > 1,
+        "second_slot_skipped": c["form"] == "two" and C > 2048,
+        "count_from_c1": c["C2"] > 0, "group_by_source": c["C2"] > 0,
+        "eps_1e-5": c["eps"] != 1e-5,
+        "eps_omitted": c["kind"] in ("tiny", "const"),
+        "var_not_clamped": c["kind"] == "const",
+        "silu_before_affine": c["silu"],
+        "slab_without_sample_offset": ps and c["B"] > 1,
+        "second_producer_group_dropped": ps and max(gn_producer_groups(c["C1"], c["C2"], c["G"])) >= 2,
+    }[mutant]

@@ -63,11 +63,12 @@ inline const void* kernarg = nullptr;
 inline bool dry_run = false;                // record the launches, do not execute them
 inline std::vector<std::string> launched;   // the kernel expression of every launch, in order (hipLaunchKernelGGL's first argument)
 // the same launches in full: the instantiated kernel ("gemm160_kernel<4, 4, false, 2, 5>": the expression above reads
-// <WAVES_M, WMB, ...> inside a launcher template), grid x / z, block x and a byte copy of every kernel argument
+// <WAVES_M, WMB, ...> inside a launcher template), grid x / z (and y), block x and a byte copy of every kernel argument
 struct LaunchRecord {
   std::string kernel;
   unsigned grid_x, grid_z, block_x;
   std::vector<std::string> args;
+  unsigned grid_y = 0;
 };
 inline std::vector<LaunchRecord> launch_log;
 template <auto K> struct KernelTag {};
@@ -94,7 +95,7 @@ inline std::string kernel_name() {   // the tag's type name carries the kernel's
 template <class... T>
 inline void record(const char* expr, const std::string& name, dim3 grid, dim3 block, const T&... a) {
   launched.push_back(expr);
-  LaunchRecord r{name, grid.x, grid.z, block.x, {}};
+  LaunchRecord r{name, grid.x, grid.z, block.x, {}, grid.y};
   (r.args.emplace_back(reinterpret_cast<const char*>(&a), sizeof(a)), ...);
   launch_log.push_back(r);
 }
