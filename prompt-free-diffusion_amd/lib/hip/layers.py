@@ -49,10 +49,15 @@ def _sig(*ps):
                                      for p in ps)
 
 
-def _dev16(t):
+def _require_gpu(t, message):
+    """the one device guard of the host layer (parameters, contexts): tests of the host composition replace it"""
     if not t.is_cuda:
-        raise RuntimeError("parameters must be on the GPU before the HIP path runs (call net.to('cuda')); "
-                           "there is no CPU fallback")
+        raise RuntimeError(message)
+
+
+def _dev16(t):
+    _require_gpu(t, "parameters must be on the GPU before the HIP path runs (call net.to('cuda')); "
+                    "there is no CPU fallback")
     return t.detach().to(torch.float16)
 
 

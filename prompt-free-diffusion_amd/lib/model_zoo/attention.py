@@ -43,8 +43,7 @@ class ContextKV:
     aligned (pfd_attention_f16 contract)."""
 
     def __init__(self, context):
-        if not context.is_cuda:
-            raise RuntimeError("HIP path: context must be on the GPU (no CPU fallback)")
+        L._require_gpu(context, "HIP path: context must be on the GPU (no CPU fallback)")
         B, Nk, Cd = context.shape
         self.B, self.Nk, self.Cd = B, Nk, Cd
         self.Nkp = (Nk + 7) // 8 * 8
@@ -243,14 +242,15 @@ class CrossAttention(nn.Module, L._Packed):
             o = ops.attention(qk, qk[:, Cd:], vt, B, H, N, N, D, self.scale, ldq=2 * Cd, ldk=2 * Cd,
                               ldvt=B * Np, q_bs=N * 2 * Cd, k_bs=N * 2 * Cd, vt_bs=Np)
         else:
-            k, vt = context.get(self)
+            # (argument errors first: context.get launches the K / V^T projections on its first call)
             if context.B != B:
                 raise ValueError(f"context batch {context.B} != activation batch {B}")
             z = context.zero_lead
+            if single and not (res is not None and 2 * z == B and stats_out and ops.wide_tile_ok(self.to_out[0].out_features, Cd)):
+                raise ValueError("CrossAttention.hip(single=True) needs the zero-context shortcut on half the batch, a residual, "
+                                 "statistics and the wide-tile out-projection (SpatialTransformer.hip checks before it asks)")
+            k, vt = context.get(self)
             if single:
-                if not (res is not None and 2 * z == B and stats_out and ops.wide_tile_ok(self.to_out[0].out_features, Cd)):
-                    raise ValueError("CrossAttention.hip(single=True) needs the zero-context shortcut on half the batch, a residual, "
-                                     "statistics and the wide-tile out-projection (SpatialTransformer.hip checks before it asks)")
                 w_o, b_o = self.to_out[0]._pk()
                 out = torch.empty((B * N, res.shape[1]), dtype=torch.float16, device=res.device)
                 st_o = torch.empty((B * N, out.shape[1] // 160, 2), dtype=torch.float32, device=out.device)
@@ -405,6 +405,8 @@ class SpatialTransformer(nn.Module):
         B, H, W_, Cc = x.shape
         N = H * W_
         blocks = list(self.transformer_blocks)
+        if cfg_pair and blocks[0].disable_self_attn:
+            raise ValueError("cfg_pair needs a context-free self-attention in the first block")
         hs = None
         inner = self.proj_in.out_features if self.use_linear else self.proj_in.out_channels
         if ops.ln_fold_ok(inner) and inner % 160 == 0 and Cc % 64 == 0:   # (a 1x1 conv on Cc % 64 != 0 goes through im2col: no statistics)
@@ -414,8 +416,6 @@ class SpatialTransformer(nn.Module):
         else:
             h = self.proj_in.hip(self.norm.hip(x)).view(B * N, -1)
         if cfg_pair:
-            if blocks[0].disable_self_attn:
-                raise ValueError("cfg_pair needs a context-free self-attention in the first block")
             h = blocks[0].hip_self(h, B, N, context, hs)
             hs = None
             if isinstance(h, tuple):

@@ -209,6 +209,10 @@ class ResBlock(TimestepBlock):
             if x2 is not None and ops.wide_tile_ok(w.shape[0], C1 + C2) and C1 % 64 == 0:
                 # `skip_connection(torch.cat([h, skip], 1))` (:274 after pfd.py:356) as ONE contraction over two sources
                 sk = ops.gemm(x.view(-1, C1), w, bias=b, a2=x2.view(-1, C2), k=C1 + C2)
+            elif x2 is not None and (C1 % 64 or C2 % 64):
+                # a source the GEMM cannot contract on its own (K % 64 != 0, include/pfd_hip.h): the concat is materialised.
+                # No shipped UNet comes here (its skip sources are multiples of 320)
+                sk = skip.hip(torch.cat([x, x2], -1))
             else:
                 sk = ops.gemm(x.view(-1, C1), w[:, :C1], bias=b, k=C1)
                 if x2 is not None:
