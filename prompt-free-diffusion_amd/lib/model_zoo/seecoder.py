@@ -350,6 +350,8 @@ class SemanticContextEncoder(nn.Module):
         self.qtransformer = get_model()(qtransformer_cfg)
 
     def hip(self, x_nhwc):
+        if x_nhwc.shape[0] != 1:               # (the decoder would refuse it, after the whole backbone has run)
+            raise NotImplementedError("one image at a time (see module docstring)")
         fea = self.imencoder.hip(x_nhwc, want=('res3', 'res4', 'res5'))
         hs = self.imdecoder.hip({k: fea[k] for k in ('res3', 'res4', 'res5')})
         return self.qtransformer.hip([hs['res3'], hs['res4'], hs['res5']])

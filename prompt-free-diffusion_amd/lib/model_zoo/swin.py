@@ -64,10 +64,14 @@ class WindowAttention(nn.Module, L._Packed):
         return self._packed("rpb", lambda: L._dev16(self.relative_position_bias_table).contiguous(),
                             self.relative_position_bias_table)
 
-    def hip(self, xn, B, H, W_, shift, res):
-        """xn: LayerNorm'ed tokens [B*H*W, C]; returns proj(window_attention) + res"""
+    def check(self):
+        """what the kernel is built for; callers that launch something in front of this attention ask first"""
         if self.window_size != (12, 12) or self.dim // self.num_heads != 32 or self.qkv.bias is None:
             raise NotImplementedError("pfd_swin_window_attention_f16 is built for window 12, head_dim 32")
+
+    def hip(self, xn, B, H, W_, shift, res):
+        """xn: LayerNorm'ed tokens [B*H*W, C]; returns proj(window_attention) + res"""
+        self.check()
         qkv = self.qkv.hip(xn)
         qkv_bias = self.qkv._pk()[1]
         a = ops.swin_window_attention(qkv, qkv_bias, self._pk_rpb(), B, H, W_, self.dim, self.num_heads, 12, shift,
@@ -95,6 +99,7 @@ class SwinTransformerBlock(nn.Module):
         self.W = None
 
     def hip(self, x, B, H, W_):
+        self.attn.check()                      # (before norm1 is launched)
         x = self.attn.hip(self.norm1.hip(x), B, H, W_, self.shift_size, res=x)
         return self.mlp.hip(self.norm2.hip(x), res=x)
 

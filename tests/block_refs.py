@@ -313,16 +313,21 @@ def nhwc(x):
 # ------------------------------------------------------------------------------------------------
 SWITCHES = {"LN_FOLD": ("ops", "LN_FOLD"), "GN_PSTATS": ("ops", "GN_PSTATS"), "GEMM_FUSE": ("ops", "GEMM_FUSE"),
             "UPS_FOLD": ("ops", "UPS_FOLD"), "fuse_groupnorm": ("ResBlock", "fuse_groupnorm"),
-            "fuse_reduce_groupnorm": ("ResBlock", "fuse_reduce_groupnorm"), "pair_without_copies": ("ST", "pair_without_copies")}
+            "fuse_reduce_groupnorm": ("ResBlock", "fuse_reduce_groupnorm"), "pair_without_copies": ("ST", "pair_without_copies"),
+            "PFD_VAE_ATTN": ("env", "PFD_VAE_ATTN"), "AttnBlock.ROWS": ("AttnBlock", "ROWS")}
 
 
 def apply_switches(monkeypatch, sw):
     from lib.hip import ops
-    from lib.model_zoo import attention as AT, openaimodel as OM
-    owner = {"ops": ops, "ResBlock": OM.ResBlock, "ST": AT.SpatialTransformer}
+    from lib.model_zoo import attention as AT, autokl_modules as AK, openaimodel as OM
+    owner = {"ops": ops, "ResBlock": OM.ResBlock, "ST": AT.SpatialTransformer, "AttnBlock": AK.AttnBlock}
+    monkeypatch.delenv("PFD_VAE_ATTN", raising=False)          # (a case runs the form it names, whatever the caller's environment)
     for k, v in (sw or {}).items():
         o, a = SWITCHES[k]
-        monkeypatch.setattr(owner[o], a, v)
+        if o == "env":
+            monkeypatch.setenv(a, v)
+        else:
+            monkeypatch.setattr(owner[o], a, v)
 
 
 class Built:
@@ -663,6 +668,12 @@ CLASSES = ("resblock", "resample", "attention", "btb", "st", "unet")
 _BUILT = {}
 
 
+def register(cases):
+    """further case tables (tests/encoder_vae_refs.py) share built() / run_gpu() / the stand-in runner; CASES stays the UNet's"""
+    for c in cases:
+        assert CASE.setdefault(c["id"], c) is c, f"case id {c['id']} is taken"
+
+
 def built(cid):
     """cases are built once per session and shared (the reference too: .ref64); nothing in them is modified afterwards"""
     b = _BUILT.get(cid)
@@ -681,7 +692,8 @@ class Census:
     that tell the forms apart.  Calls made inside another `ops` call are not logged."""
 
     FUNCS = ("gemm", "conv", "conv_narrow", "groupnorm", "groupnorm_table", "layernorm", "ln_rowstats", "attention", "add", "axpby",
-             "add_rowvec", "activation", "cat_pair", "timestep_embedding", "to_nhwc", "to_nchw")
+             "add_rowvec", "activation", "cat_pair", "timestep_embedding", "to_nhwc", "to_nchw", "swin_window_attention",
+             "layernorm_patch_merge", "softmax_rows")
 
     def __init__(self):
         self.log, self.depth = [], 0
@@ -732,7 +744,7 @@ class Census:
         elif name == "groupnorm_table":
             if k.get("x2") is not None:
                 f.append("x2")
-        elif name in ("layernorm", "add", "add_rowvec", "axpby"):
+        elif name in ("layernorm", "add", "add_rowvec", "axpby", "softmax_rows"):
             if k.get("out") is not None:
                 f.append("out")
             if k.get("ln_out") is not None:
@@ -839,11 +851,12 @@ def ref_of(b, fwd=False):
     return b.ref64
 
 
-def run_gpu(case, census=False, fwd=False):
+def run_gpu(case, census=False, fwd=False, params=False):
     """the case through the real .hip methods on the device, in a patch context of its own (switches, an empty decline memory) ->
     (output of the first run on the CPU, Census | None of a second run, whether the second run gave the same bits, whether the
     inputs are unchanged).  With census=True a THIRD run keeps the decline memory of the second: its calls are Census.again.  The
-    GroupNorm statistics riding on the first run's output (or None) are Built.gn_carried."""
+    GroupNorm statistics riding on the first run's output (or None) are Built.gn_carried; with params=True the names of the
+    parameters and buffers that differ from the case's after the runs are Built.params_changed."""
     import pytest
     from lib.hip import ops
     b = built(case["id"])
@@ -865,4 +878,7 @@ def run_gpu(case, census=False, fwd=False):
             cen.rerun(lambda: run(mods, inputs))
         torch.cuda.synchronize()
         kept = all(torch.equal(v.cpu(), b.inputs[k]) for k, v in inputs.items() if torch.is_tensor(v))
+        if params:      # the fp16 views of the host layer ARE the parameters of an fp16 module: none of them may be written
+            b.params_changed = [f"{k}.{n}" for k, m in mods.items() for n, t in m.state_dict().items()
+                                if not torch.equal(t.cpu(), b.mods[k].state_dict()[n].to(t.dtype))]
     return y.cpu(), cen, same, kept

@@ -292,14 +292,33 @@ def conv_narrow(x, w, ksize, *, stride=1, pad=None, bias=None, rowvec=None, res=
 # attention, normalisation
 # ----------------------------------------------------------------------------------------------
 def attention(q, k, vt, B, H, Nq, Nk, D, scale, *, ldq, ldk, ldvt, q_bs, k_bs, vt_bs, out=None):
-    if D not in (40, 80, 96, 160) or ldq % 8 or ldk % 8 or ldvt % 8 or vt_bs % 8:
+    if D not in (40, 80, 96, 160, 512) or ldq % 8 or ldk % 8 or ldvt % 8 or vt_bs % 8:
         raise ValueError(f"attention: D {D} / leading dimensions outside the contract of pfd_attention_f16")
+    if D == 512 and (H != 1 or Nk % 32):
+        raise ValueError(f"attention: D 512 needs H == 1 and Nk % 32 == 0 (H {H}, Nk {Nk}; PFD_ESHAPE: include/pfd_hip.h)")
     y = KR.attention_ref(q, k, vt, B, H, Nq, Nk, D, scale, ldq=ldq, ldk=ldk, ldvt=ldvt, q_bs=q_bs, k_bs=k_bs, vt_bs=vt_bs)
     y = _h(y).reshape(B * Nq, H * D)
     if out is None:
         return y.contiguous()
     out[:B * Nq, :H * D].copy_(y)
     return out
+
+
+def swin_window_attention(qkv, qkv_bias, rpb, B, H, W_, Cdim, nH, ws, shift, scale, out=None):
+    """pfd_swin_window_attention_f16: window 12, head width 32, with the refusals of the library.  The result is rounded once;
+    the kernel's fp16 store of the normalised probabilities (profiles/encoder_kernel_tests.md: at most 2^-11 vmax) is not
+    restated here -- profiles/encoder_vae_block_tests.md says what that costs against T"""
+    assert qkv.dtype == torch.float16
+    if ws != KR.WS or Cdim != KR.HD * nH:
+        raise ValueError(f"swin_window_attention: window {ws} / C {Cdim} with {nH} heads (built for window 12, C == 32 nH: PFD_ESHAPE)")
+    if not 0 <= shift < KR.WS:
+        raise ValueError(f"swin_window_attention: shift {shift} outside [0, 12) (PFD_EINVAL)")
+    if tuple(qkv.shape) != (B * H * W_, 3 * Cdim) or not qkv.is_contiguous():
+        raise ValueError(f"swin_window_attention: qkv {tuple(qkv.shape)} is not a dense [{B * H * W_}, {3 * Cdim}]")
+    if out is not None and (tuple(out.shape) != (B * H * W_, Cdim) or not out.is_contiguous()):
+        raise ValueError(f"swin_window_attention: out {tuple(out.shape)} is not a dense [{B * H * W_}, {Cdim}]")
+    y = KR.swin_window_attention_ref(qkv, qkv_bias, rpb, B, H, W_, nH, shift, scale)
+    return ops._written(_put(out, y, (B * H * W_, Cdim)))
 
 
 def _from_pstats(x, x2, st1, st2, B, HW, gamma, beta, eps, silu):
@@ -354,6 +373,18 @@ def groupnorm_table(x, gamma, beta, groups, eps, *, x2=None):
 def layernorm(x, gamma, beta, eps=1e-5, out=None):
     assert x.dtype == torch.float16
     return ops._written(_put(out, KR.layernorm_ref(x, gamma, beta, eps), x.shape))
+
+
+def layernorm_patch_merge(x, gamma, beta, eps=1e-5):
+    assert x.dtype == torch.float16
+    return _h(KR.layernorm_patch_merge_ref(x, gamma, beta, eps)).contiguous()
+
+
+def softmax_rows(x, scale, out=None):
+    """pfd_softmax_rows_f16; out may be x itself (the row is read whole before it is written)"""
+    assert x.dtype == torch.float16
+    R, N, _ = ops._rows(x)
+    return _put(out, KR.softmax_rows_ref(x.reshape(R, N), scale), (R, N))
 
 
 def ln_rowstats(x, out=None):
@@ -417,8 +448,9 @@ def _fell_through(*a, **k):
     raise AssertionError("host layer on the stand-in: a call fell through to the real library")
 
 
-STANDIN = ("gemm", "conv", "conv_narrow", "attention", "groupnorm", "groupnorm_table", "layernorm", "ln_rowstats", "to_nhwc",
-           "to_nchw", "timestep_embedding", "add", "axpby", "add_rowvec", "activation")
+STANDIN = ("gemm", "conv", "conv_narrow", "attention", "swin_window_attention", "groupnorm", "groupnorm_table", "layernorm",
+           "layernorm_patch_merge", "softmax_rows", "ln_rowstats", "to_nhwc", "to_nchw", "timestep_embedding", "add", "axpby",
+           "add_rowvec", "activation")
 
 
 def install(monkeypatch, policy=None):
