@@ -415,6 +415,24 @@ int pfd_cfg_ddim_step_ps(const void* eps, int32_t nb, const float* x, const floa
                          int32_t step, float noise_mul, const float* coef, const float* scale, float* x_prev,
                          float* pred_x0, void* xin_next, int32_t rep, int32_t B, int32_t C, int32_t h, int32_t w,
                          pfd_stream_t stream);
+/* Classifier-free-guidance combine + one step of DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2: multistep, data
+ * prediction), fp32, on the DDIM schedule: from a_t to the step's target a_s, with lambda(a) = 0.5 log(a / (1 - a)),
+ * h = lambda(a_s) - lambda(a_t), c_x = sqrt((1 - a_s) / (1 - a_t)), c_d = -sqrt(a_s) expm1(-h):
+ *   e = e_u + s*(e_c - e_u);  pred_x0 = (x - sqrt(1-a_t) e) * (1 / sqrt(a_t))     [pfd_cfg_ddim_step's, bit for bit]
+ *   D = pred_x0                                   x0_prev == NULL: a first-order step (= DDIM at sigma 0)
+ *   D = w_cur pred_x0 + w_prev x0_prev            else, r = h_last / h, w_prev = -1 / (2 r), w_cur = 1 - w_prev
+ *   x_next = c_x x + c_d D
+ * coef: device fp32 [8] = {a_t, sqrt(1-a_t), c_x, c_d, w_cur, w_prev, guidance scale, 0}, one row of
+ * lib/solver.py::dpmpp_2m_table; coef[4] and coef[5] are not read when x0_prev == NULL.
+ * scale: device fp32 [B] or NULL; when given, scale[b] takes the place of coef[6] for sample b (as in
+ * pfd_cfg_ddim_step_ps: nb = 2 combines, nb = 1 gives e = scale[b] * eps).
+ * x0_prev: NCHW fp32, the pred_x0 of the step before; it must not alias x_next or pred_x0.  eps, x, x_next, pred_x0,
+ * xin_next, rep: as eps, x, x_prev, pred_x0, xin_next, rep of pfd_cfg_ddim_step.  Sample b's outputs are a function of
+ * sample b's inputs only.  NULL eps / x / coef / x_next / pred_x0, nb not 1 or 2, rep < 1 with xin_next, a dimension
+ * <= 0 or C*h*w > 2^34 is PFD_EINVAL. */
+int pfd_cfg_dpmpp_step(const void* eps, int32_t nb, const float* x, const float* x0_prev, const float* coef,
+                       const float* scale, float* x_next, float* pred_x0, void* xin_next, int32_t rep,
+                       int32_t B, int32_t C, int32_t h, int32_t w, pfd_stream_t stream);
 /* y = a + b (f16, fp32 add), n elements; b may be NULL (copy). */
 int pfd_add_f16(const void* a, const void* b, void* y, int64_t n, pfd_stream_t stream);
 /* y = alpha*a + beta*b (f16 storage, fp32 math), n elements; b may be NULL (y = alpha*a).  The

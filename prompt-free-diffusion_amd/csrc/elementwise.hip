@@ -133,6 +133,52 @@ __global__ void cfg_ddim_kernel(const half_t* __restrict__ eps, int nb, const fl
   }
 }
 
+// DPM-Solver++(2M) step (pfd_cfg_dpmpp_step): the guided e and pred_x0 are cfg_ddim_kernel's operations in its order, so
+// pred_x0 is bit-identical to that kernel's for the same inputs; then x_next = c_x x + c_d D with D = pred_x0 (x0_prev ==
+// NULL: a first-order step, the weights are not read) or D = w_cur pred_x0 + w_prev x0_prev.  coef: {a_t, sqrt(1-a_t),
+// c_x, c_d, w_cur, w_prev, guidance scale, 0} (lib/solver.py).  PS as in cfg_ddim_kernel: scale_ps[b] in place of coef[6].
+template <bool PS>
+__global__ void cfg_dpmpp_kernel(const half_t* __restrict__ eps, int nb, const float* __restrict__ x,
+                                 const float* __restrict__ x0_prev, const float* __restrict__ coef,
+                                 float* __restrict__ x_next, float* __restrict__ pred_x0,
+                                 half_t* __restrict__ xin_next, int rep, int B, int C, int h, int w,
+                                 const float* __restrict__ scale_ps) {
+  const long n = (long)B * C * h * w;
+  const float a_t = coef[0], s1mat = coef[1], c_x = coef[2], c_d = coef[3], scale_all = PS ? 0.f : coef[6];
+  const float w_cur = x0_prev ? coef[4] : 1.f, w_prev = x0_prev ? coef[5] : 0.f;
+  const float isq_at = 1.0f / sqrtf(a_t);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    // i indexes NCHW
+    const int xw = (int)(i % w);
+    long t = i / w;
+    const int yh = (int)(t % h);
+    t /= h;
+    const int c = (int)(t % C);
+    const int b = (int)(t / C);
+    const long ei = (((long)b * h + yh) * w + xw) * C + c;  // NHWC
+    const float scale = PS ? scale_ps[b] : scale_all;
+    float e;
+    if (nb == 2) {
+      const float eu = (float)eps[ei];
+      const float ec = (float)eps[n + ei];
+      e = eu + scale * (ec - eu);
+    } else {
+      e = (float)eps[ei] * scale;
+    }
+    const float xv = x[i];
+    const float p0 = (xv - s1mat * e) * isq_at;
+    float d = p0;
+    if (x0_prev) d = w_cur * p0 + w_prev * x0_prev[i];
+    const float xn = c_x * xv + c_d * d;
+    x_next[i] = xn;
+    pred_x0[i] = p0;
+    if (xin_next) {
+      const half_t hv = (half_t)xn;
+      for (int r = 0; r < rep; ++r) xin_next[(long)r * n + ei] = hv;
+    }
+  }
+}
+
 // The generator on its own: one thread per quad (one Philox call), out[b, 4q .. 4q+3].  VEC: n_per_sample % 4 == 0 and
 // `out` 16-byte aligned -> one 16-byte store; otherwise scalar stores, the tail of a sample's last quad dropped.
 template <bool VEC>
@@ -473,6 +519,27 @@ extern "C" int pfd_cfg_ddim_step_ps(const void* eps, int32_t nb, const float* x,
                        (hipStream_t)stream, (const half_t*)eps, nb, x, key, step, noise_mul, coef, x_prev, pred_x0,
                        (half_t*)xin_next, rep, B, C, h, w, scale);
   return pfd_check_launch("pfd_cfg_ddim_step_ps");
+}
+
+extern "C" int pfd_cfg_dpmpp_step(const void* eps, int32_t nb, const float* x, const float* x0_prev, const float* coef,
+                                  const float* scale, float* x_next, float* pred_x0, void* xin_next, int32_t rep,
+                                  int32_t B, int32_t C, int32_t h, int32_t w, pfd_stream_t stream) {
+  if (!eps || !x || !coef || !x_next || !pred_x0) return PFD_EINVAL;
+  if (nb < 1 || nb > 2 || B <= 0 || C <= 0 || h <= 0 || w <= 0 || (xin_next && (rep < 1 || rep > 2))) return PFD_EINVAL;
+  if (x0_prev && (x0_prev == x_next || x0_prev == pred_x0)) return PFD_EINVAL;   // the history is read while both are written
+  const long ns = (long)C * h * w;
+  if (ns > ((long)1 << 34)) return PFD_EINVAL;   // the per-sample bound of the seeded siblings
+  const long n = (long)B * ns;
+  PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
+  if (scale)
+    hipLaunchKernelGGL(cfg_dpmpp_kernel<true>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)eps, nb, x, x0_prev, coef, x_next, pred_x0, (half_t*)xin_next, rep, B, C, h, w,
+                       scale);
+  else
+    hipLaunchKernelGGL(cfg_dpmpp_kernel<false>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)eps, nb, x, x0_prev, coef, x_next, pred_x0, (half_t*)xin_next, rep, B, C, h, w,
+                       (const float*)nullptr);
+  return pfd_check_launch("pfd_cfg_dpmpp_step");
 }
 
 extern "C" int pfd_add_f16(const void* a, const void* b, void* y, int64_t n, pfd_stream_t stream) {

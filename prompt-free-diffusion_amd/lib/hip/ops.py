@@ -857,6 +857,30 @@ def cfg_ddim_step(eps, nb, x, coef, *, noise=None, want_next=True, rep=None, noi
     return x_prev, pred_x0, xin
 
 
+def cfg_dpmpp_step(eps, nb, x, coef, x0_prev=None, want_next=False, rep=None, scale=None):
+    """Fused CFG combine + one DPM-Solver++(2M) step (pfd_cfg_dpmpp_step).  eps NHWC f16 [nb*B,h,w,C]; x NCHW fp32
+    [B,C,h,w]; coef fp32[8] device, one row of lib/solver.py::dpmpp_2m_table.  x0_prev: the pred_x0 of the step before
+    (fp32 NCHW, like x), or None for a first-order step (= DDIM at eta 0; the weights of the row are not read).
+    scale: fp32 [B] tensor, the guidance scale of sample b in place of coef[6]; None: coef[6] for the whole batch.
+    Returns (x_next fp32 NCHW, pred_x0 fp32 NCHW, xin_next f16 NHWC|None) like cfg_ddim_step."""
+    B, Cc, h, w = x.shape
+    rep = nb if rep is None else rep
+    if tuple(coef.shape) != (8,) or coef.dtype != torch.float32:
+        raise ValueError(f"cfg_dpmpp_step: coef must be a float32 row of 8 numbers: got {tuple(coef.shape)} {coef.dtype}")
+    if x0_prev is not None and not (x0_prev.shape == x.shape and x0_prev.dtype == torch.float32 and
+                                    x0_prev.device == x.device and x0_prev.is_contiguous()):
+        raise ValueError("cfg_dpmpp_step: x0_prev must be a contiguous float32 tensor of x's shape, next to x")
+    if scale is not None:
+        scale = guidance_scale_rows(scale, B, x.device)
+    x_next = torch.empty_like(x)
+    pred_x0 = torch.empty_like(x)
+    xin = torch.empty((rep * B, h, w, Cc), dtype=torch.float16, device=x.device) if want_next else None
+    rc = _lib().pfd_cfg_dpmpp_step(eps.data_ptr(), nb, x.data_ptr(), _ptr(x0_prev), coef.data_ptr(), _ptr(scale),
+                                   x_next.data_ptr(), pred_x0.data_ptr(), _ptr(xin), rep, B, Cc, h, w, _stream())
+    _b.check(rc, "pfd_cfg_dpmpp_step")
+    return x_next, pred_x0, xin
+
+
 def add(a, b, out=None):
     _chk16(a, "add a")
     _chk16(b, "add b")

@@ -29,10 +29,18 @@ numbers instead of one number.  Sample b is then combined with its own scale ins
 (pfd_cfg_ddim_step_ps); CFG is always on (nb = 2, also for an entry of 1.0), and the captured graph is keyed on the
 shape only, the vector being one more static input: one graph serves every mixture of scales.  With one number every
 path, graph key and result is what it was.
+
+Second-order solver (opt-in): `sample(..., solver='dpmpp_2m')` runs DPM-Solver++(2M) (lib/solver.py) on the same
+timestep subset, one UNet evaluation per step like DDIM, the update in one kernel (pfd_cfg_dpmpp_step) that takes the
+previous step's pred_x0 as its history; the first and the last step are first-order.  `solver='dpmpp_1'` is that
+kernel at order 1 on every step, which is DDIM at eta 0.  Both are deterministic (eta = 0 only, no noise key, no
+dropout, no multi-context), are captured as a hipGraph like eta = 0 and take a per-sample scale; the graph key carries
+the solver name only for them.  With the default `solver='ddim'` nothing changes.
 """
 import numpy as np
 import torch
 
+from .. import solver as _solver
 from ..hip import ops
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps, noise_like
 
@@ -55,6 +63,16 @@ def per_sample_scale(scale, bs, device):
     if tuple(v.shape) != (bs,):
         raise ValueError(f"a per-sample guidance scale needs {bs} numbers, one per sample: got shape {tuple(v.shape)}")
     return v.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _refuse_noise(solver, eta, noise_dropout, x_info):
+    """the multistep solvers are deterministic: nothing that draws noise goes with them"""
+    if eta != 0.:
+        raise ValueError(f"solver {solver!r} is deterministic: eta must be 0 (got a stochastic schedule)")
+    if noise_dropout > 0.:
+        raise ValueError(f"solver {solver!r} is deterministic: noise_dropout > 0 is not available")
+    if x_info.get('noise_key', None) is not None:
+        raise ValueError(f"solver {solver!r} is deterministic: x_info['noise_key'] is not available")
 
 
 class DDIMSampler(object):
@@ -109,20 +127,30 @@ class DDIMSampler(object):
         tab = np.stack([a, ap, sg, s1, np.full_like(np.asarray(a, dtype=np.float64), float(scale))], axis=1)
         return torch.tensor(tab, dtype=torch.float32, device=self.model.device)
 
+    def _dpmpp_table(self, scale, order):
+        """device fp32 [n_steps, 8]: lib/solver.py::dpmpp_2m_table on this schedule"""
+        tab = _solver.dpmpp_2m_table(self.ddim_alphas, self.ddim_alphas_prev, scale, order)
+        return torch.tensor(tab, dtype=torch.float32, device=self.model.device)
+
     @ops.serialised
     @torch.no_grad()
     def sample(self, steps, shape, x_info, c_info, eta=0., temperature=1., noise_dropout=0., verbose=True,
-               log_every_t=100):
+               log_every_t=100, solver='ddim'):
+        if _solver.solver_order(solver) is not None:
+            _refuse_noise(solver, eta, noise_dropout, x_info)      # before the schedule is made
         self.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=verbose)
         if verbose:
             print(f'Data shape for DDIM sampling is {shape}, eta {eta}')
         return self.ddim_sampling(shape, x_info=x_info, c_info=c_info, noise_dropout=noise_dropout,
-                                  temperature=temperature, log_every_t=log_every_t)
+                                  temperature=temperature, log_every_t=log_every_t, solver=solver)
 
     @ops.serialised
     @torch.no_grad()
     def ddim_sampling(self, shape, x_info, c_info, noise_dropout=0., temperature=1., log_every_t=100,
-                      callback=None):
+                      callback=None, solver='ddim'):
+        order = _solver.solver_order(solver)      # None: the DDIM kernels
+        if order is not None:
+            _refuse_noise(solver, float(np.any(np.asarray(self.ddim_sigmas) != 0.)), noise_dropout, x_info)
         model = self.model
         device = model.device
         dtype = c_info['conditioning'].dtype
@@ -163,7 +191,7 @@ class DDIMSampler(object):
         if control is not None and hasattr(model, 'ctl'):
             hint = model.ctl.prepare_hint(control).feat    # step/sample-invariant: once per request
         nb = 2 if cfg else 1
-        coef = self._coef_table(scale)
+        coef = self._coef_table(scale) if order is None else self._dpmpp_table(scale, order)
         time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
         # all step timestamps at once on the device: [total_steps, 1] int64 (repeated over the nb * n samples of a step)
@@ -199,6 +227,7 @@ class DDIMSampler(object):
                 pair = nb == 2 and self.share_cfg_prefix
                 rep = 1 if pair else nb
                 xin = ops.to_nhwc(x, rep=rep)
+                x0_last = None
                 for i in range(total_steps):
                     index = total_steps - i - 1
                     eps = model.apply_model_nhwc(x_type, xin, t_table[i], c_type, ctx, control=ctl,
@@ -210,7 +239,14 @@ class DDIMSampler(object):
                         if noise_dropout > 0.:
                             noise = torch.nn.functional.dropout(noise, p=noise_dropout)
                         noise = noise.contiguous()
-                    if keyed:     # sigma * temperature * z(key row, index, element), drawn inside the kernel
+                    if order is not None:
+                        # multistep: this step's pred_x0 is the next step's history; none on the first step of a run
+                        # (an img2img start included) nor on the last, nor at order 1
+                        first_order = order == 1 or i == 0 or index == 0
+                        x, pred_x0, xin = ops.cfg_dpmpp_step(eps, nb, x, coef[index], None if first_order else x0_last,
+                                                             want_next=True, rep=rep, **ps)
+                        x0_last = pred_x0
+                    elif keyed:   # sigma * temperature * z(key row, index, element), drawn inside the kernel
                         x, pred_x0, xin = ops.cfg_ddim_step(eps, nb, x, coef[index], want_next=True, rep=rep,
                                                             noise_key=nkey, step=index, noise_mul=temperature, **ps)
                     else:
@@ -234,6 +270,8 @@ class DDIMSampler(object):
                    float(scale) if sps is None else _PER_SAMPLE, nb, x_type, c_type, int(log_every_t), zero_lead,
                    bool(self.share_cfg_prefix), hash(np.asarray(timesteps).tobytes()), self._weights_signature(),
                    None if nkey is None else (float(temperature), hash(np.asarray(self.ddim_sigmas).tobytes())))
+            if order is not None:
+                key = key + (solver,)          # the DDIM key is what it was
             ent = self._graphs.pop(key, None)
             if ent is None:
                 while len(self._graphs) >= self.max_graphs:
@@ -267,7 +305,9 @@ class DDIMSampler(object):
     @ops.serialised
     @torch.no_grad()
     def sample_multicontext(self, steps, shape, x_info, c_info_list, eta=0., temperature=1., noise_dropout=0.,
-                            verbose=True, log_every_t=100):
+                            verbose=True, log_every_t=100, solver='ddim'):
+        if _solver.solver_order(solver) is not None:
+            raise ValueError(f"solver {solver!r} is not available for multi-context sampling: use 'ddim'")
         self.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=verbose)
         if verbose:
             print(f'Data shape for DDIM sampling is {shape}, eta {eta}')

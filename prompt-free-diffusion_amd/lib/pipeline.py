@@ -227,7 +227,7 @@ class PromptFreePipeline:
     @torch.no_grad()
     def generate(self, image, n_global, height, width, steps=50, scale=2.0, eta=0.0, seed=20, control=None,
                  uncond=None, decode=True, gather=False, verbose=False, timings=None, as_uint8=False,
-                 device_noise=False):
+                 device_noise=False, solver='ddim'):
         """returns (images, latents [n_local,4,h,w]); images = [n_local | n_global (gather), 3, H, W] in [0,1]
         in the model dtype, or -- as_uint8 -- packed uint8 [n, H, W, 3] (the bytes ToPILImage would produce,
         app.py:273-275; 4x fewer bytes through the all-gather); decode=False returns the latents twice.
@@ -239,8 +239,14 @@ class PromptFreePipeline:
         size (like x_T) and the loop replays as a hipGraph.  False: the reference's draw from the global generator.
         scale: one number, or a sequence / tensor of n_global numbers: sample j of the GLOBAL batch is guided with
         scale[j] (pfd_cfg_ddim_step_ps; CFG is then on for every sample, also one whose scale is 1).
-        control: [1,3,H,W] is one hint shared by all samples; [n_local,3,H,W] is one hint PER SAMPLE of this rank."""
+        control: [1,3,H,W] is one hint shared by all samples; [n_local,3,H,W] is one hint PER SAMPLE of this rank.
+        solver: 'ddim', or 'dpmpp_2m' -- DPM-Solver++(2M), second order, on the same `steps` timesteps (lib/solver.py;
+        typically 20 to 25 steps in place of 50) -- or 'dpmpp_1', its first-order form (DDIM at eta 0).  The last two are
+        deterministic: eta = 0, no device_noise."""
         from .model_zoo.ddim import is_per_sample
+        from .solver import solver_order
+        if solver_order(solver) is not None and (eta != 0. or device_noise):     # an unknown name raises here too
+            raise ValueError(f"solver {solver!r} is deterministic: eta must be 0 and device_noise off")
         P, r = self.world_size, self.rank
         dev = self.net.device
         if is_per_sample(scale):     # checked before anything touches the device
@@ -282,8 +288,9 @@ class PromptFreePipeline:
                   'unconditional_guidance_scale': scale}
         if control is not None:
             c_info['control'] = self.ingest(control, (height, width), 'control') if u8_control else control.to(dev)
+        how = {} if solver == 'ddim' else {'solver': solver}     # the default call is what it was
         x, _ = self.sampler.sample(steps=steps, shape=list(xT.shape), x_info=x_info, c_info=c_info, eta=eta,
-                                   verbose=verbose)
+                                   verbose=verbose, **how)
         if mk:
             mk.mark()
         if not decode:

@@ -4,7 +4,7 @@ The reference serves requests by letting Gradio's worker threads call `action_in
 model with no lock and one request = one `sampler.sample` of `n_sample_image` samples (app.py:229-277,
 405-410).  Here every request goes through a FIFO; one worker thread owns the device and
 
-  * coalesces compatible queued requests (same output size, step count, guidance scale, eta, noise kind, control /
+  * coalesces compatible queued requests (same output size, step count, solver, guidance scale, eta, noise kind, control /
     unconditional-context kind) into ONE DDIM batch (eta > 0 only with `device_noise=True`, see `shareable`): samples are independent on this path, every sample
     carries its own SeeCoder context in the cross-attention K / V^T cache, so four single-image requests
     cost one batch-4 loop instead of four batch-1 loops (the UNet at batch 2 fills 1/4 of the chip);
@@ -28,11 +28,12 @@ import torch
 
 from . import image_io
 from .pipeline import PromptFreePipeline, shard_noise_keys, shard_xT
+from .solver import solver_order
 
 
 class _Request:
     __slots__ = ("image", "n", "height", "width", "steps", "scale", "eta", "seed", "control", "uncond", "as_uint8",
-                 "device_noise", "future", "mixed")
+                 "device_noise", "future", "mixed", "solver")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -40,11 +41,12 @@ class _Request:
 
     def key(self):
         """requests with equal keys can share one DDIM batch (mixed: any two scales other than 1 can)"""
+        how = () if self.solver in (None, 'ddim') else (self.solver,)     # a batch runs ONE solver; the DDIM keys are unchanged
         if self.mixed:
             return (self.height, self.width, self.steps, float(self.scale) == 1.0, float(self.eta),
-                    self.control is None, self.uncond is None, bool(self.as_uint8), bool(self.device_noise))
+                    self.control is None, self.uncond is None, bool(self.as_uint8), bool(self.device_noise)) + how
         return (self.height, self.width, self.steps, float(self.scale), float(self.eta), self.control is None,
-                self.uncond is None, bool(self.as_uint8), bool(self.device_noise))
+                self.uncond is None, bool(self.as_uint8), bool(self.device_noise)) + how
 
     def shareable(self):
         """eta > 0 WITHOUT device_noise draws its noise from the global RNG inside the loop (ddim.py:166): batched with
@@ -72,7 +74,7 @@ class PromptFreeServer:
 
     # ---- client side (any thread) -------------------------------------------------------------------
     def submit(self, image, n_samples=1, height=512, width=512, steps=50, scale=2.0, eta=0.0, seed=20,
-               control=None, uncond=None, as_uint8=True, device_noise=False):
+               control=None, uncond=None, as_uint8=True, device_noise=False, solver='ddim'):
         """image [1,3,h,w] in [0,1] (any size); control [1,3,H,W] or None; uncond [1,148,768] or None (zeros).
         image and control may each be a uint8 HWC picture [h,w,3] (torch or numpy, any size; the reference picture
         at least 32 a side) instead: the request carries the bytes and the worker converts them on the device
@@ -80,6 +82,8 @@ class PromptFreeServer:
         device_noise: with eta > 0, sample j of the request draws the seeded noise keyed (seed, j) inside the step kernel
         (lib/noise.py) instead of the global generator: its images do not depend on what it was batched with, so such
         requests are coalesced like eta = 0 ones.
+        solver: 'ddim', 'dpmpp_2m' (DPM-Solver++(2M), lib/solver.py) or 'dpmpp_1'; the last two need eta = 0 and no
+        device_noise, and share batches only with requests of the same solver.
         -> Future of uint8 [n,H,W,3] (as_uint8) or float [n,3,H,W] images"""
         if self._stop:
             raise RuntimeError("server is closed")
@@ -91,6 +95,8 @@ class PromptFreeServer:
             raise ValueError(f"n_samples must be in [1, {self.max_batch}]")
         if steps < 1:
             raise ValueError("steps must be >= 1")
+        if solver_order(solver) is not None and (float(eta) != 0.0 or device_noise):     # an unknown name raises here too
+            raise ValueError(f"solver {solver!r} is deterministic: eta must be 0 and device_noise off")
         if image_io.wants_ingest(image):            # a uint8 picture (anything that is not a torch tensor is checked as one)
             image_io.check_u8_picture(image, "image", min_side=32)
         elif not (image.dim() == 4 and image.shape[0] == 1 and image.shape[1] == 3 and image.is_floating_point() and
@@ -106,7 +112,7 @@ class PromptFreeServer:
             raise ValueError(f"control must be a float tensor [1, 3, {height}, {width}] or a uint8 picture [h, w, 3]")
         r = _Request(image=image, n=int(n_samples), height=int(height), width=int(width), steps=int(steps),
                      scale=scale, eta=eta, seed=int(seed), control=control, uncond=uncond, as_uint8=as_uint8,
-                     device_noise=bool(device_noise), future=Future(), mixed=self.mixed_batches or None)
+                     device_noise=bool(device_noise), future=Future(), mixed=self.mixed_batches or None, solver=solver)
         self._q.put(r)
         return r.future
 
@@ -228,8 +234,9 @@ class PromptFreeServer:
             x_info = {'type': 'image', 'xt': xT}
             if r0.device_noise:
                 x_info['noise_key'] = torch.cat(keys).to(dev)
+            how = {} if r0.solver in (None, 'ddim') else {'solver': r0.solver}
             x, _ = self.pipe.sampler.sample(steps=r0.steps, shape=list(xT.shape), x_info=x_info, c_info=c_info,
-                                            eta=r0.eta, verbose=False)
+                                            eta=r0.eta, verbose=False, **how)
             img = self.net.vae_decode(x, 'image', out_uint8=True) if r0.as_uint8 else self.net.vae_decode(x, 'image')
             self.batches.append(int(xT.shape[0]))
         outs, off = [], 0
