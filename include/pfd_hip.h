@@ -502,6 +502,34 @@ int pfd_image_resample_v_u8(const void* src, void* dst, int32_t out_kind, int32_
                             int32_t W, int32_t C, const int32_t* kk, const int32_t* ymin, const int32_t* klen,
                             int32_t ktaps, pfd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Canny edge hints (added under ABI 10): packed uint8 pictures [B, H, W, C], C in {1, 3}, to the edge map of the
+ * reference's canny annotator, `cv2.Canny(img, low_threshold, high_threshold)` (controlnet_annotator/canny/__init__.py:5,
+ * called from ControlNet.preprocess, controlnet.py:332-360, which app.py:246 reaches with do_preprocess=True).
+ *
+ * The algorithm is the numpy statement of lib/canny.py, byte for byte, all integer: low > high are swapped; 3x3 Sobel per
+ * channel on a border replicated by one pixel; m = |gx| + |gy|; for C = 3 the channel with the largest m (the lowest
+ * index on a tie) gives the pixel's signed (xs, ys); non-maximum suppression on m with a border of zeros, with
+ * x = |xs|, y = |ys| << 15, t22 = 13573 x, t67 = t22 + (x << 16): y < t22 compares W (>) and E (>=), y > t67 compares N (>)
+ * and S (>=), otherwise the diagonal pair along the gradient (both >); a survivor with m > low is weak (1), with
+ * m > high strong (2); an edge is a strong pixel or a weak one 8-connected to a strong one through survivors.
+ * That statement restates OpenCV's published algorithm; equality with cv2.Canny itself has not been measured.
+ *
+ * Four launches whatever the picture holds (Sobel + NMS; union-find link; resolve; emit), no host synchronisation,
+ * capturable.  The caller owns the work buffers, each of B * H * W elements: states (uint8; the NMS result, left for
+ * the caller to read), parent (int32), strong (uint8).  out_kind: PFD_IMG_U8 -> uint8 [B, H, W], 255 on an edge;
+ * PFD_IMG_NCHW_F16 / PFD_IMG_NCHW_F32 -> the hint [B, 3, H, W] with 1 on an edge, three equal planes (`ToTensor` +
+ * `repeat(1, 3, 1, 1)`, controlnet.py:357-359).
+ *
+ * Bounds: B >= 1; C in {1, 3}; 1 <= H, W <= 4096; B * H * W < 2^31.  Anything else is PFD_ESHAPE with nothing
+ * launched; null pointers and other output kinds are PFD_EINVAL.
+ * ---------------------------------------------------------------------------------- */
+/* PFD_OK iff pfd_canny_u8 takes [B, H, W, C] (the bounds above); launches nothing. */
+int pfd_canny_check(int32_t B, int32_t H, int32_t W, int32_t C);
+
+int pfd_canny_u8(const void* src, int32_t B, int32_t H, int32_t W, int32_t C, int32_t low, int32_t high, void* states,
+                 void* parent, void* strong, void* out, int32_t out_kind, pfd_stream_t stream);
+
 /* y = act(x) elementwise (act in NONE|GELU|RELU|SILU), n f16 elements.  The SiLU in front
  * of every ResBlock emb_layers Linear (openaimodel.py:217-218) applied once to the shared
  * time embedding, and nonlinearity() on its own (autokl_modules.py:33-35). */

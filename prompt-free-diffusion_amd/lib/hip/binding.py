@@ -97,6 +97,8 @@ SIGNATURES = {
     "pfd_image_resample_check": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "pfd_image_resample_h_u8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
     "pfd_image_resample_v_u8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "pfd_canny_check": (_i32, [_i32, _i32, _i32, _i32]),
+    "pfd_canny_u8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "pfd_prof_enable": (_i32, [_i32]),
     "pfd_prof_read": (_i32, [_i32, C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(C.c_double),
                              C.POINTER(C.c_double)]),

@@ -777,6 +777,52 @@ def image_from_u8(img, size=None, dtype=torch.float16, layout='nchw'):
     return out
 
 
+def canny_thresholds(low, high):
+    """(low, high) as the detector takes them (lib/canny.py step 1): two finite numbers, floored, in order; clamped to
+    [-1, 2041], which changes nothing (a magnitude lies in [0, 2040]) and keeps them int32.  ValueError otherwise."""
+    import math
+    try:
+        low, high = float(low), float(high)
+    except (TypeError, ValueError):
+        raise ValueError(f"canny: thresholds must be two finite numbers, got {low!r}, {high!r}") from None
+    if not (math.isfinite(low) and math.isfinite(high)):
+        raise ValueError(f"canny: thresholds must be two finite numbers, got {low!r}, {high!r}")
+    low, high = (max(-1, min(2041, int(math.floor(v)))) for v in (low, high))
+    return (high, low) if low > high else (low, high)
+
+
+@serialised
+def canny_u8(img, low=100, high=200, out='u8', dtype=torch.float16, return_states=False):
+    """uint8 picture(s) [H,W,C] | [B,H,W,C] (C in {1, 3}) on the device -> the Canny edge map of lib/canny.py, byte for
+    byte (the reference's `cv2.Canny(img, low, high)`, controlnet_annotator/canny/__init__.py:5; equality with OpenCV
+    itself is unverified).  out='u8': uint8 [B,H,W], 255 on an edge; out='hint': [B,3,H,W] in `dtype` (fp16 | fp32) with
+    1 on an edge, three equal planes (`ToTensor` + `repeat(1, 3, 1, 1)`, controlnet.py:357-359).  Four launches on the
+    current stream whatever the picture holds, no host synchronisation: capturable.  return_states: (result, the uint8
+    [B,H,W] states after non-maximum suppression: 0 | 1 weak | 2 strong)."""
+    if not (torch.is_tensor(img) and img.dtype == torch.uint8 and img.dim() in (3, 4)):
+        raise ValueError("canny_u8: a uint8 tensor [H, W, C] or [B, H, W, C] expected")
+    if out not in ('u8', 'hint'):
+        raise ValueError(f"canny_u8: out must be 'u8' or 'hint', got {out!r}")
+    kind = _b.IMG_U8 if out == 'u8' else _IMG_KIND.get(('nchw', dtype))
+    if kind is None:
+        raise ValueError(f"canny_u8: the hint is fp16 or fp32, not {dtype}")
+    low, high = canny_thresholds(low, high)
+    if not img.is_cuda:
+        raise RuntimeError("canny_u8: input must live on the GPU; the HIP path has no CPU fallback")
+    x = (img[None] if img.dim() == 3 else img).contiguous()
+    B, H, W_, Cc = x.shape
+    lib = _lib()
+    _b.check(lib.pfd_canny_check(B, H, W_, Cc), "pfd_canny_check")
+    states = torch.empty((B, H, W_), dtype=torch.uint8, device=x.device)
+    parent = torch.empty((B, H, W_), dtype=torch.int32, device=x.device)
+    strong = torch.empty((B, H, W_), dtype=torch.uint8, device=x.device)
+    res = torch.empty((B, H, W_) if out == 'u8' else (B, 3, H, W_), dtype=torch.uint8 if out == 'u8' else dtype,
+                      device=x.device)
+    _b.check(lib.pfd_canny_u8(x.data_ptr(), B, H, W_, Cc, low, high, states.data_ptr(), parent.data_ptr(),
+                              strong.data_ptr(), res.data_ptr(), kind, _stream()), "pfd_canny_u8")
+    return (res, states) if return_states else res
+
+
 def timestep_embedding(t, dim, max_period=10000.0):
     t = t.to(torch.int64).contiguous()
     out = torch.empty((t.shape[0], dim), dtype=torch.float16, device=t.device)

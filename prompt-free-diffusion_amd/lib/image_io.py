@@ -8,7 +8,9 @@ holds what those kernels need from the host and nothing else:
   * `pillow_bicubic_taps`: the fixed-point tap tables of Pillow's ImagingResample for one axis.  Pure Python floats
     (doubles, as Pillow's C code), no torch, no numpy, no Pillow.
   * `to_device_u8` / `check_u8_picture`: argument checks of a uint8 picture and its move to the device.
+  * `check_control_preprocess`: argument checks of the optional edge detector in front of the hint encoder (csrc/canny.hip).
 """
+import math
 
 PRECISION_BITS = 32 - 8 - 2          # Pillow's 8-bit fixed point: coefficients are scaled by 2^22
 MAX_SIDE = 8192                      # bounds of the kernels (include/pfd_hip.h)
@@ -92,6 +94,28 @@ def check_resize(in_hw, out_hw, what):
         if o < 1 or o > MAX_SIDE or i > MAX_RATIO * o:
             raise ValueError(f"{what}: cannot resize {in_hw[0]} x {in_hw[1]} to {out_hw[0]} x {out_hw[1]} "
                              f"(sides up to {MAX_SIDE}, shrink by at most {MAX_RATIO})")
+
+
+CONTROL_PREPROCESS = (None, 'canny')
+
+
+def check_control_preprocess(control, preprocess, thresholds):
+    """the `control_preprocess` / `control_thresholds` pair of generate and submit: None (the control picture is the hint,
+    as with app.py's do_preprocess=False) or 'canny' (ControlNet.preprocess(type='canny'), app.py:246) with two finite
+    numbers (low, high).  -> (low, high) as floats.  Raises ValueError; touches no device."""
+    if preprocess not in CONTROL_PREPROCESS:
+        raise ValueError(f"control_preprocess must be None or 'canny', got {preprocess!r} (the neural annotators of the "
+                         "reference are not provided)")
+    try:
+        low, high = thresholds
+        low, high = float(low), float(high)
+    except (TypeError, ValueError):
+        raise ValueError(f"control_thresholds must be two finite numbers (low, high), got {thresholds!r}") from None
+    if not (math.isfinite(low) and math.isfinite(high)):
+        raise ValueError(f"control_thresholds must be two finite numbers (low, high), got {thresholds!r}")
+    if preprocess is not None and control is None:
+        raise ValueError(f"control_preprocess={preprocess!r} without a control picture")
+    return low, high
 
 
 def wants_ingest(x):

@@ -3,9 +3,11 @@
 
 Module tree / state-dict keys / constructor kwargs follow the network part of the reference's
 lib/model_zoo/controlnet.py (`ControlNet` :65-297, `forward` :302-324, hint block :165-181,
-`make_zero_conv` :299-300).  `preprocess` and the vendored annotators (:332-503,
-controlnet_annotator/**) are CPU-side third-party image preprocessors, off by default in the
-app (`do_preprocess=False`) and out of scope (SURVEY §2 #11b).
+`make_zero_conv` :299-300).  Of `preprocess` (:332-503) the branches without a network are
+provided -- 'none', 'input' and 'canny' (the one annotator that is closed arithmetic, `cv2.Canny`:
+a HIP kernel here, csrc/canny.hip); the vendored neural annotators (controlnet_annotator/**) are
+third-party preprocessors, off by default in the app (`do_preprocess=False`) and out of scope
+(SURVEY §2 #11b).
 
 The hint encoder (8 convs) depends on neither the step nor the sample, so `prepare_hint` runs
 it once per request; the reference recomputes it in every one of the 50 steps (:314).
@@ -194,10 +196,32 @@ class ControlNet(nn.Module):
         outs = self.hip(ops.to_nhwc(x), hint, timesteps, as_context_kv(context))
         return [ops.to_nchw(o, x.dtype) for o in outs]
 
-    def preprocess(self, *args, **kwargs):
+    def preprocess(self, x, type='canny', **kwargs):
+        """The reference's signature (controlnet.py:332, called as `preprocess(ccraw, type=ctl_method, size=[h, w])` by
+        app.py:246).  x: float [B,3,H,W] in [0,1].  'none' | None -> None; 'input' | 'shuffle_v11e' -> x in fp32;
+        'canny' | 'canny_v11p' -> the Canny edge hint, fp32 [B,3,H,W] of 0 and 1 on x.device: the picture becomes bytes as
+        ToPILImage makes them (`x.mul(255).byte()` in x's dtype, controlnet.py:339) and goes through the HIP detector
+        (ops.canny_u8; kwargs low_threshold = 100, high_threshold = 200, controlnet.py:353-359; other kwargs are ignored
+        as the reference's canny branch ignores them).  The neural annotators (depth, hed, mlsd, ...) are vendored
+        third-party networks and stay out of scope: NotImplementedError.  A file path is refused: the library opens no
+        files (the reference decodes it with Pillow, controlnet.py:334-337)."""
+        if isinstance(x, str):
+            raise ValueError("preprocess: a picture tensor [B, 3, H, W] expected; the library opens no files -- decode "
+                             f"{x!r} in the caller")
+        if not (torch.is_tensor(x) and x.is_floating_point() and x.dim() == 4 and x.shape[1] == 3):
+            raise ValueError("preprocess: a float tensor [B, 3, H, W] in [0, 1] expected")
+        if type == 'none' or type is None:
+            return None
+        if type in ('input', 'shuffle_v11e'):
+            return x.to(torch.float32)
+        if type in ('canny', 'canny_v11p'):
+            low, high = ops.canny_thresholds(kwargs.pop('low_threshold', 100), kwargs.pop('high_threshold', 200))
+            u8 = x.mul(255).byte().permute(0, 2, 3, 1).contiguous()
+            return ops.canny_u8(u8, low, high, out='hint', dtype=torch.float32)
         raise NotImplementedError(
-            "control-hint preprocessors (canny/HED/MiDaS/...) are vendored CPU annotators outside the "
-            "denoising hot path; pass an already prepared control image (app default do_preprocess=False)")
+            f"control-hint annotator {type!r} is a vendored third-party network (HED/MiDaS/MLSD/...) outside this port: "
+            "only 'canny' / 'canny_v11p', 'input' / 'shuffle_v11e' and 'none' are provided; pass an already prepared "
+            "control image (app default do_preprocess=False)")
 
     def get_device(self):
         return self.time_embed[0].weight.device

@@ -225,9 +225,32 @@ class PromptFreePipeline:
 
     @serialised
     @torch.no_grad()
+    def control_hint(self, control, height, width, preprocess=None, thresholds=(100, 200)):
+        """the hint the ControlNet is given for `control`, [1|n,3,height,width] in the model dtype on the device -- what
+        app.py:244-249 calls `cc` and shows next to the results (app.py:272).  preprocess None: the picture itself (a
+        uint8 picture resized to (height, width), `ingest`; a float tensor as it is).  'canny': its Canny edges
+        (ControlNet.preprocess(type='canny'), app.py:246) at `thresholds` = (low, high): a uint8 picture is resized on
+        the device AS uint8 and handed to the detector, which writes the hint in the model dtype (ops.canny_u8) -- no
+        float picture, no byte round trip; a float tensor goes through net.ctl.preprocess, which makes the bytes."""
+        low, high = image_io.check_control_preprocess(control, preprocess, thresholds)
+        dev = self.net.device
+        if preprocess is None:
+            return self.ingest(control, (height, width), 'control') if image_io.wants_ingest(control) else control.to(dev)
+        dtype = self.net.get_dtype() if hasattr(self.net, 'get_dtype') else torch.float32
+        if image_io.wants_ingest(control):
+            image_io.check_resize(image_io.check_u8_picture(control, 'control')[:2], (height, width), 'control')
+            kdtype = dtype if dtype in (torch.float16, torch.float32) else torch.float32
+            u8 = ops.image_from_u8(image_io.to_device_u8(control, dev, 'control'), (height, width), layout='u8')
+            hint = ops.canny_u8(u8, low, high, out='hint', dtype=kdtype)
+            return hint if kdtype == dtype else hint.to(dtype)
+        return self.net.ctl.preprocess(control.to(dev), type=preprocess, low_threshold=low, high_threshold=high,
+                                       size=[height, width]).to(dtype)
+
+    @serialised
+    @torch.no_grad()
     def generate(self, image, n_global, height, width, steps=50, scale=2.0, eta=0.0, seed=20, control=None,
                  uncond=None, decode=True, gather=False, verbose=False, timings=None, as_uint8=False,
-                 device_noise=False, solver='ddim'):
+                 device_noise=False, solver='ddim', control_preprocess=None, control_thresholds=(100, 200)):
         """returns (images, latents [n_local,4,h,w]); images = [n_local | n_global (gather), 3, H, W] in [0,1]
         in the model dtype, or -- as_uint8 -- packed uint8 [n, H, W, 3] (the bytes ToPILImage would produce,
         app.py:273-275; 4x fewer bytes through the all-gather); decode=False returns the latents twice.
@@ -242,7 +265,9 @@ class PromptFreePipeline:
         control: [1,3,H,W] is one hint shared by all samples; [n_local,3,H,W] is one hint PER SAMPLE of this rank.
         solver: 'ddim', or 'dpmpp_2m' -- DPM-Solver++(2M), second order, on the same `steps` timesteps (lib/solver.py;
         typically 20 to 25 steps in place of 50) -- or 'dpmpp_1', its first-order form (DDIM at eta 0).  The last two are
-        deterministic: eta = 0, no device_noise."""
+        deterministic: eta = 0, no device_noise.
+        control_preprocess: None -- the control picture is the hint -- or 'canny': the hint is the picture's Canny edges at
+        control_thresholds = (low, high), computed on the device (`control_hint`; app.py:246 with do_preprocess=True)."""
         from .model_zoo.ddim import is_per_sample
         from .solver import solver_order
         if solver_order(solver) is not None and (eta != 0. or device_noise):     # an unknown name raises here too
@@ -261,6 +286,7 @@ class PromptFreePipeline:
             image_io.check_u8_picture(image, 'image', min_side=32)
         if u8_control:
             image_io.check_resize(image_io.check_u8_picture(control, 'control')[:2], (height, width), 'control')
+        image_io.check_control_preprocess(control, control_preprocess, control_thresholds)
         mk = _Marks(torch.device(dev).type == 'cuda') if timings is not None else None
         if mk:
             mk.mark()
@@ -287,7 +313,7 @@ class PromptFreePipeline:
         c_info = {'type': 'image', 'conditioning': cond, 'unconditional_conditioning': uncond,
                   'unconditional_guidance_scale': scale}
         if control is not None:
-            c_info['control'] = self.ingest(control, (height, width), 'control') if u8_control else control.to(dev)
+            c_info['control'] = self.control_hint(control, height, width, control_preprocess, control_thresholds)
         how = {} if solver == 'ddim' else {'solver': solver}     # the default call is what it was
         x, _ = self.sampler.sample(steps=steps, shape=list(xT.shape), x_info=x_info, c_info=c_info, eta=eta,
                                    verbose=verbose, **how)

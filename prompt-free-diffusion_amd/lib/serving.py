@@ -33,7 +33,7 @@ from .solver import solver_order
 
 class _Request:
     __slots__ = ("image", "n", "height", "width", "steps", "scale", "eta", "seed", "control", "uncond", "as_uint8",
-                 "device_noise", "future", "mixed", "solver")
+                 "device_noise", "future", "mixed", "solver", "control_preprocess", "control_thresholds")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -74,7 +74,8 @@ class PromptFreeServer:
 
     # ---- client side (any thread) -------------------------------------------------------------------
     def submit(self, image, n_samples=1, height=512, width=512, steps=50, scale=2.0, eta=0.0, seed=20,
-               control=None, uncond=None, as_uint8=True, device_noise=False, solver='ddim'):
+               control=None, uncond=None, as_uint8=True, device_noise=False, solver='ddim', control_preprocess=None,
+               control_thresholds=(100, 200)):
         """image [1,3,h,w] in [0,1] (any size); control [1,3,H,W] or None; uncond [1,148,768] or None (zeros).
         image and control may each be a uint8 HWC picture [h,w,3] (torch or numpy, any size; the reference picture
         at least 32 a side) instead: the request carries the bytes and the worker converts them on the device
@@ -84,6 +85,9 @@ class PromptFreeServer:
         requests are coalesced like eta = 0 ones.
         solver: 'ddim', 'dpmpp_2m' (DPM-Solver++(2M), lib/solver.py) or 'dpmpp_1'; the last two need eta = 0 and no
         device_noise, and share batches only with requests of the same solver.
+        control_preprocess: None, or 'canny': the worker turns the control picture into its Canny edge hint at
+        control_thresholds = (low, high) on the device (PromptFreePipeline.control_hint).  A preprocessed control is a
+        control: the batch key does not change.
         -> Future of uint8 [n,H,W,3] (as_uint8) or float [n,3,H,W] images"""
         if self._stop:
             raise RuntimeError("server is closed")
@@ -110,9 +114,11 @@ class PromptFreeServer:
         elif control is not None and not (control.is_floating_point() and
                                           tuple(control.shape) == (1, 3, int(height), int(width))):
             raise ValueError(f"control must be a float tensor [1, 3, {height}, {width}] or a uint8 picture [h, w, 3]")
+        thresholds = image_io.check_control_preprocess(control, control_preprocess, control_thresholds)
         r = _Request(image=image, n=int(n_samples), height=int(height), width=int(width), steps=int(steps),
                      scale=scale, eta=eta, seed=int(seed), control=control, uncond=uncond, as_uint8=as_uint8,
-                     device_noise=bool(device_noise), future=Future(), mixed=self.mixed_batches or None, solver=solver)
+                     device_noise=bool(device_noise), future=Future(), mixed=self.mixed_batches or None, solver=solver,
+                     control_preprocess=control_preprocess, control_thresholds=thresholds)
         self._q.put(r)
         return r.future
 
@@ -198,6 +204,10 @@ class PromptFreeServer:
         except BaseException as e:   # noqa: BLE001
             f.set_exception(e)
 
+    def _hint(self, r):
+        """the hint of one request: its control picture as given, or (control_preprocess) its Canny edges"""
+        return self.pipe.control_hint(r.control, r.height, r.width, r.control_preprocess, r.control_thresholds or (100, 200))
+
     @torch.no_grad()
     def _generate(self, batch):
         """one DDIM batch for a list of compatible requests; returns one image tensor per request"""
@@ -225,12 +235,10 @@ class PromptFreeServer:
             if r0.control is not None and r0.mixed:
                 # one hint per sample [N,3,H,W]: every request's picture is ingested on its own (uint8 pictures may
                 # differ in source size) and repeated over the request's samples
-                hints = [(self.pipe.ingest(r.control, (r.height, r.width), 'control') if image_io.wants_ingest(r.control)
-                          else r.control.to(dev)).expand(r.n, -1, -1, -1) for r in batch]
+                hints = [self._hint(r).expand(r.n, -1, -1, -1) for r in batch]
                 c_info['control'] = torch.cat(hints)
             elif r0.control is not None:
-                c_info['control'] = (self.pipe.ingest(r0.control, (r0.height, r0.width), 'control')
-                                     if image_io.wants_ingest(r0.control) else r0.control.to(dev))
+                c_info['control'] = self._hint(r0)
             x_info = {'type': 'image', 'xt': xT}
             if r0.device_noise:
                 x_info['noise_key'] = torch.cat(keys).to(dev)

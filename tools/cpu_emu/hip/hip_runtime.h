@@ -188,6 +188,13 @@ template <class T> static inline T __shfl_xor(T v, int mask, int = 64) { return 
 // wave-uniform by construction at every use in csrc/ (tid >> 6, a block-uniform flag): lane 0's value
 #define __builtin_amdgcn_readfirstlane(x) emu::exchange((x), 0)
 
+// scoped atomics (csrc/canny.hip): the threads of a block are OS threads, so these are the compiler's own atomics; the
+// scope has no meaning on the host
+#define __HIP_MEMORY_SCOPE_AGENT 4
+#define __hip_atomic_load(p, order, scope) __atomic_load_n((p), (order))
+#define __hip_atomic_store(p, v, order, scope) __atomic_store_n((p), (v), (order))
+#define __hip_atomic_fetch_min(p, v, order, scope) __atomic_fetch_min((p), (v), (order))
+
 static inline uint64_t emu_ballot(bool p) {
   emu::Wave& w = emu::wave();
   w.slot[emu::lane()] = p ? 1 : 0;
