@@ -89,6 +89,53 @@ __global__ void timestep_embedding_kernel(const int64_t* __restrict__ t, half_t*
   out[i] = (half_t)v;
 }
 
+// ---- the fused CFG + sampler step -------------------------------------------------------------------------------------
+// One copy of what the three step kernels (cfg_ddim_kernel, cfg_dpmpp_kernel, cfg_ddim_rng_kernel) compute per element:
+// the guided eps, pred_x0 and the emit of the next UNet input.  That the kernels agree bit for bit on these is a property
+// of the functions below.  Each kernel keeps its own decode of the thread index.
+
+// NHWC index of element (b, c, yh, xw) of an NCHW [B, C, h, w] tensor
+__device__ __forceinline__ long nhwc_index(int b, int c, int yh, int xw, int C, int h, int w) {
+  return (((long)b * h + yh) * w + xw) * C + c;
+}
+
+// the guided eps of the element at NHWC index ei: eps holds nb batches of n elements, unconditional first
+__device__ __forceinline__ float guided_eps(const half_t* __restrict__ eps, int nb, long n, long ei, float scale) {
+  if (nb == 2) {
+    const float eu = (float)eps[ei];
+    const float ec = (float)eps[n + ei];
+    return eu + scale * (ec - eu);
+  }
+  return (float)eps[ei] * scale;
+}
+
+__device__ __forceinline__ float pred_x0_of(float xv, float e, float s1mat, float isq_at) {
+  return (xv - s1mat * e) * isq_at;
+}
+
+// `rep` fp16 copies of the next UNet input at NHWC index ei (nothing without xin_next)
+__device__ __forceinline__ void emit_next(half_t* __restrict__ xin_next, int rep, long n, long ei, float v) {
+  if (xin_next) {
+    const half_t hv = (half_t)v;
+    for (int r = 0; r < rep; ++r) xin_next[(long)r * n + ei] = hv;
+  }
+}
+
+// the per-step numbers of a DDIM row {a_t, a_prev, sigma_t, sqrt(1-a_t), guidance scale}
+struct DdimStep {
+  float sigma, s1mat, isq_at, sq_aprev, dir;
+  __device__ __forceinline__ explicit DdimStep(const float* __restrict__ coef) {
+    const float a_t = coef[0], a_prev = coef[1];
+    sigma = coef[2];
+    s1mat = coef[3];
+    isq_at = 1.0f / sqrtf(a_t);
+    sq_aprev = sqrtf(a_prev);
+    dir = sqrtf(fmaxf(1.0f - a_prev - sigma * sigma, 0.f));
+  }
+  // x_prev without the noise term
+  __device__ __forceinline__ float update(float p0, float e) const { return sq_aprev * p0 + dir * e; }
+};
+
 // PS (per-sample guidance scale, pfd_cfg_ddim_step_ps): scale_ps[b] in place of coef[4]; nothing else differs, and the
 // PS = false instantiation never reads scale_ps.
 template <bool PS>
@@ -98,10 +145,8 @@ __global__ void cfg_ddim_kernel(const half_t* __restrict__ eps, int nb, const fl
                                 half_t* __restrict__ xin_next, int rep, int B, int C, int h, int w,
                                 const float* __restrict__ scale_ps) {
   const long n = (long)B * C * h * w;
-  const float a_t = coef[0], a_prev = coef[1], sigma = coef[2], s1mat = coef[3], scale_all = PS ? 0.f : coef[4];
-  const float isq_at = 1.0f / sqrtf(a_t);
-  const float sq_aprev = sqrtf(a_prev);
-  const float dir = sqrtf(fmaxf(1.0f - a_prev - sigma * sigma, 0.f));
+  const DdimStep k(coef);
+  const float scale_all = PS ? 0.f : coef[4];
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     // i indexes NCHW
     const int xw = (int)(i % w);
@@ -110,33 +155,21 @@ __global__ void cfg_ddim_kernel(const half_t* __restrict__ eps, int nb, const fl
     t /= h;
     const int c = (int)(t % C);
     const int b = (int)(t / C);
-    const long ei = (((long)b * h + yh) * w + xw) * C + c;  // NHWC
-    const float scale = PS ? scale_ps[b] : scale_all;
-    float e;
-    if (nb == 2) {
-      const float eu = (float)eps[ei];
-      const float ec = (float)eps[n + ei];
-      e = eu + scale * (ec - eu);
-    } else {
-      e = (float)eps[ei] * scale;
-    }
-    const float xv = x[i];
-    const float p0 = (xv - s1mat * e) * isq_at;
-    float xp = sq_aprev * p0 + dir * e;
-    if (noise) xp += sigma * noise[i];
+    const long ei = nhwc_index(b, c, yh, xw, C, h, w);
+    const float e = guided_eps(eps, nb, n, ei, PS ? scale_ps[b] : scale_all);
+    const float p0 = pred_x0_of(x[i], e, k.s1mat, k.isq_at);
+    float xp = k.update(p0, e);
+    if (noise) xp += k.sigma * noise[i];
     x_prev[i] = xp;
     pred_x0[i] = p0;
-    if (xin_next) {
-      const half_t hv = (half_t)xp;
-      for (int r = 0; r < rep; ++r) xin_next[(long)r * n + ei] = hv;
-    }
+    emit_next(xin_next, rep, n, ei, xp);
   }
 }
 
-// DPM-Solver++(2M) step (pfd_cfg_dpmpp_step): the guided e and pred_x0 are cfg_ddim_kernel's operations in its order, so
-// pred_x0 is bit-identical to that kernel's for the same inputs; then x_next = c_x x + c_d D with D = pred_x0 (x0_prev ==
-// NULL: a first-order step, the weights are not read) or D = w_cur pred_x0 + w_prev x0_prev.  coef: {a_t, sqrt(1-a_t),
-// c_x, c_d, w_cur, w_prev, guidance scale, 0} (lib/solver.py).  PS as in cfg_ddim_kernel: scale_ps[b] in place of coef[6].
+// DPM-Solver++(2M) step (pfd_cfg_dpmpp_step): the guided e and pred_x0 are the shared functions above; then
+// x_next = c_x x + c_d D with D = pred_x0 (x0_prev == NULL: a first-order step, the weights are not read) or
+// D = w_cur pred_x0 + w_prev x0_prev.  coef: {a_t, sqrt(1-a_t), c_x, c_d, w_cur, w_prev, guidance scale, 0}
+// (lib/solver.py).  PS as in cfg_ddim_kernel: scale_ps[b] in place of coef[6].
 template <bool PS>
 __global__ void cfg_dpmpp_kernel(const half_t* __restrict__ eps, int nb, const float* __restrict__ x,
                                  const float* __restrict__ x0_prev, const float* __restrict__ coef,
@@ -155,27 +188,16 @@ __global__ void cfg_dpmpp_kernel(const half_t* __restrict__ eps, int nb, const f
     t /= h;
     const int c = (int)(t % C);
     const int b = (int)(t / C);
-    const long ei = (((long)b * h + yh) * w + xw) * C + c;  // NHWC
-    const float scale = PS ? scale_ps[b] : scale_all;
-    float e;
-    if (nb == 2) {
-      const float eu = (float)eps[ei];
-      const float ec = (float)eps[n + ei];
-      e = eu + scale * (ec - eu);
-    } else {
-      e = (float)eps[ei] * scale;
-    }
+    const long ei = nhwc_index(b, c, yh, xw, C, h, w);
+    const float e = guided_eps(eps, nb, n, ei, PS ? scale_ps[b] : scale_all);
     const float xv = x[i];
-    const float p0 = (xv - s1mat * e) * isq_at;
+    const float p0 = pred_x0_of(xv, e, s1mat, isq_at);
     float d = p0;
     if (x0_prev) d = w_cur * p0 + w_prev * x0_prev[i];
     const float xn = c_x * xv + c_d * d;
     x_next[i] = xn;
     pred_x0[i] = p0;
-    if (xin_next) {
-      const half_t hv = (half_t)xn;
-      for (int r = 0; r < rep; ++r) xin_next[(long)r * n + ei] = hv;
-    }
+    emit_next(xin_next, rep, n, ei, xn);
   }
 }
 
@@ -204,7 +226,7 @@ __global__ void philox_normal_kernel(const int64_t* __restrict__ key, int step, 
 
 // cfg_ddim_kernel with the noise evaluated in place: thread = four consecutive NCHW elements of ONE sample = one Philox
 // call.  VEC (w % 4 == 0, 16-byte aligned x / x_prev / pred_x0): the four share a row, 16-byte accesses; otherwise the
-// scalar path computes the same values.  After `nz` the arithmetic is cfg_ddim_kernel's, in its order.  PS as there: the
+// scalar path computes the same values.  The arithmetic is the shared functions of cfg_ddim_kernel.  PS as there: the
 // four elements of a thread belong to one sample, so scale_ps[b] is read once per quad.
 template <bool VEC, bool PS>
 __global__ void cfg_ddim_rng_kernel(const half_t* __restrict__ eps, int nb, const float* __restrict__ x,
@@ -216,10 +238,8 @@ __global__ void cfg_ddim_rng_kernel(const half_t* __restrict__ eps, int nb, cons
   const long n = (long)B * ns;
   const long nq = (ns + 3) >> 2;
   const long total = (long)B * nq;
-  const float a_t = coef[0], a_prev = coef[1], sigma = coef[2], s1mat = coef[3], scale_all = PS ? 0.f : coef[4];
-  const float isq_at = 1.0f / sqrtf(a_t);
-  const float sq_aprev = sqrtf(a_prev);
-  const float dir = sqrtf(fmaxf(1.0f - a_prev - sigma * sigma, 0.f));
+  const DdimStep k(coef);
+  const float scale_all = PS ? 0.f : coef[4];
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int b = (int)(i / nq);
     const long q = i - (long)b * nq;
@@ -244,25 +264,15 @@ __global__ void cfg_ddim_rng_kernel(const half_t* __restrict__ eps, int nb, cons
       const long t = el / w;
       const int yh = (int)(t % h);
       const int c = (int)(t / h);
-      const long ei = (((long)b * h + yh) * w + xw) * C + c;  // NHWC
-      float e;
-      if (nb == 2) {
-        const float eu = (float)eps[ei];
-        const float ec = (float)eps[n + ei];
-        e = eu + scale * (ec - eu);
-      } else {
-        e = (float)eps[ei] * scale;
-      }
+      const long ei = nhwc_index(b, c, yh, xw, C, h, w);
+      const float e = guided_eps(eps, nb, n, ei, scale);
       const float nz = noise_mul * z[j];
-      const float p0 = (xv[j] - s1mat * e) * isq_at;
-      float xp = sq_aprev * p0 + dir * e;
-      xp += sigma * nz;
+      const float p0 = pred_x0_of(xv[j], e, k.s1mat, k.isq_at);
+      float xp = k.update(p0, e);
+      xp += k.sigma * nz;
       xp4[j] = xp;
       p04[j] = p0;
-      if (xin_next) {
-        const half_t hv = (half_t)xp;
-        for (int r = 0; r < rep; ++r) xin_next[(long)r * n + ei] = hv;
-      }
+      emit_next(xin_next, rep, n, ei, xp);
     }
     if (VEC) {
       *reinterpret_cast<float4*>(x_prev + base) = make_float4(xp4[0], xp4[1], xp4[2], xp4[3]);
@@ -395,6 +405,42 @@ inline int grid_for(long n, int block) {
   return (int)g;
 }
 
+// ---- the step entry points' shared host side ---------------------------------------------------------------------------
+// what all four step entry points check alike
+inline bool step_args_ok(int nb, int B, int C, int h, int w, const void* xin_next, int rep) {
+  return nb >= 1 && nb <= 2 && B > 0 && C > 0 && h > 0 && w > 0 && !(xin_next && (rep < 1 || rep > 2));
+}
+
+// a thread's quad is one 16-byte access of x / x_prev / pred_x0 (cfg_ddim_rng_kernel<VEC = true>)
+inline bool quad_vec_ok(int w, const float* x, const float* x_prev, const float* pred_x0) {
+  return !(w & 3) && !((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_prev) |
+                        reinterpret_cast<uintptr_t>(pred_x0)) & 15);
+}
+
+// The two launches of the DDIM step on checked arguments: the plain kernel, and the seeded one in the VEC form that the
+// alignment allows.  The entry point hands in its instantiations (PS or not) and its name for the launch check.
+template <class Kernel>
+int launch_ddim(Kernel kernel, const void* eps, int nb, const float* x, const float* noise, const float* coef,
+                const float* scale, float* x_prev, float* pred_x0, void* xin_next, int rep, int B, int C, int h, int w,
+                pfd_stream_t stream, const char* name) {
+  PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(kernel, dim3(grid_for((long)B * C * h * w, 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const half_t*)eps, nb, x, noise, coef, x_prev, pred_x0, (half_t*)xin_next, rep, B, C, h, w, scale);
+  return pfd_check_launch(name);
+}
+
+template <class Kernel>
+int launch_ddim_rng(Kernel vec_kernel, Kernel scalar_kernel, const void* eps, int nb, const float* x, const int64_t* key,
+                    int step, float noise_mul, const float* coef, const float* scale, float* x_prev, float* pred_x0,
+                    void* xin_next, int rep, int B, int C, int h, int w, pfd_stream_t stream, const char* name) {
+  const long nq = ((long)C * h * w + 3) >> 2;
+  PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(quad_vec_ok(w, x, x_prev, pred_x0) ? vec_kernel : scalar_kernel, dim3(grid_for((long)B * nq, 256)),
+                     dim3(256), 0, (hipStream_t)stream, (const half_t*)eps, nb, x, key, step, noise_mul, coef, x_prev,
+                     pred_x0, (half_t*)xin_next, rep, B, C, h, w, scale);
+  return pfd_check_launch(name);
+}
+
 }  // namespace
 
 extern "C" int pfd_nchw_to_nhwc_f16(const void* x, int32_t src_f32, void* y, int32_t B, int32_t C, int32_t H,
@@ -445,13 +491,9 @@ extern "C" int pfd_cfg_ddim_step(const void* eps, int32_t nb, const float* x, co
                                  float* x_prev, float* pred_x0, void* xin_next, int32_t rep, int32_t B, int32_t C,
                                  int32_t h, int32_t w, pfd_stream_t stream) {
   if (!eps || !x || !coef || !x_prev || !pred_x0) return PFD_EINVAL;
-  if (nb < 1 || nb > 2 || B <= 0 || C <= 0 || h <= 0 || w <= 0 || (xin_next && (rep < 1 || rep > 2))) return PFD_EINVAL;
-  const long n = (long)B * C * h * w;
-  PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
-  hipLaunchKernelGGL(cfg_ddim_kernel<false>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const half_t*)eps, nb, x, noise, coef, x_prev, pred_x0, (half_t*)xin_next, rep, B, C, h, w,
-                     (const float*)nullptr);
-  return pfd_check_launch("pfd_cfg_ddim_step");
+  if (!step_args_ok(nb, B, C, h, w, xin_next, rep)) return PFD_EINVAL;
+  return launch_ddim(cfg_ddim_kernel<false>, eps, nb, x, noise, coef, nullptr, x_prev, pred_x0, xin_next, rep, B, C, h, w,
+                     stream, "pfd_cfg_ddim_step");
 }
 
 extern "C" int pfd_philox_normal_f32(const int64_t* key, int32_t step, float* out, int32_t B, int64_t n_per_sample,
@@ -474,22 +516,11 @@ extern "C" int pfd_cfg_ddim_step_rng(const void* eps, int32_t nb, const float* x
                                      float noise_mul, const float* coef, float* x_prev, float* pred_x0, void* xin_next,
                                      int32_t rep, int32_t B, int32_t C, int32_t h, int32_t w, pfd_stream_t stream) {
   if (!eps || !x || !key || !coef || !x_prev || !pred_x0 || step < 0) return PFD_EINVAL;
-  if (nb < 1 || nb > 2 || B <= 0 || C <= 0 || h <= 0 || w <= 0 || (xin_next && (rep < 1 || rep > 2))) return PFD_EINVAL;
-  const long ns = (long)C * h * w;
-  if (ns > ((long)1 << 34)) return PFD_ESHAPE;
-  const long nq = (ns + 3) >> 2;
-  const bool vec = !(w & 3) && !((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_prev) |
-                                  reinterpret_cast<uintptr_t>(pred_x0)) & 15);
-  PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
-  if (vec)
-    hipLaunchKernelGGL((cfg_ddim_rng_kernel<true, false>), dim3(grid_for((long)B * nq, 256)), dim3(256), 0,
-                       (hipStream_t)stream, (const half_t*)eps, nb, x, key, step, noise_mul, coef, x_prev, pred_x0,
-                       (half_t*)xin_next, rep, B, C, h, w, (const float*)nullptr);
-  else
-    hipLaunchKernelGGL((cfg_ddim_rng_kernel<false, false>), dim3(grid_for((long)B * nq, 256)), dim3(256), 0,
-                       (hipStream_t)stream, (const half_t*)eps, nb, x, key, step, noise_mul, coef, x_prev, pred_x0,
-                       (half_t*)xin_next, rep, B, C, h, w, (const float*)nullptr);
-  return pfd_check_launch("pfd_cfg_ddim_step_rng");
+  if (!step_args_ok(nb, B, C, h, w, xin_next, rep)) return PFD_EINVAL;
+  if ((long)C * h * w > ((long)1 << 34)) return PFD_ESHAPE;   // the quad index is one 32-bit counter word
+  return launch_ddim_rng(cfg_ddim_rng_kernel<true, false>, cfg_ddim_rng_kernel<false, false>, eps, nb, x, key, step,
+                         noise_mul, coef, nullptr, x_prev, pred_x0, xin_next, rep, B, C, h, w, stream,
+                         "pfd_cfg_ddim_step_rng");
 }
 
 extern "C" int pfd_cfg_ddim_step_ps(const void* eps, int32_t nb, const float* x, const float* noise, const int64_t* key,
@@ -497,48 +528,28 @@ extern "C" int pfd_cfg_ddim_step_ps(const void* eps, int32_t nb, const float* x,
                                     float* x_prev, float* pred_x0, void* xin_next, int32_t rep, int32_t B, int32_t C,
                                     int32_t h, int32_t w, pfd_stream_t stream) {
   if (!eps || !x || !coef || !scale || !x_prev || !pred_x0 || (noise && key) || (key && step < 0)) return PFD_EINVAL;
-  if (nb < 1 || nb > 2 || B <= 0 || C <= 0 || h <= 0 || w <= 0 || (xin_next && (rep < 1 || rep > 2))) return PFD_EINVAL;
-  const long ns = (long)C * h * w;
-  if (key && ns > ((long)1 << 34)) return PFD_ESHAPE;
-  PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
-  if (!key) {
-    hipLaunchKernelGGL(cfg_ddim_kernel<true>, dim3(grid_for((long)B * ns, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)eps, nb, x, noise, coef, x_prev, pred_x0, (half_t*)xin_next, rep, B, C, h, w,
-                       scale);
-    return pfd_check_launch("pfd_cfg_ddim_step_ps");
-  }
-  const long nq = (ns + 3) >> 2;
-  const bool vec = !(w & 3) && !((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_prev) |
-                                  reinterpret_cast<uintptr_t>(pred_x0)) & 15);
-  if (vec)
-    hipLaunchKernelGGL((cfg_ddim_rng_kernel<true, true>), dim3(grid_for((long)B * nq, 256)), dim3(256), 0,
-                       (hipStream_t)stream, (const half_t*)eps, nb, x, key, step, noise_mul, coef, x_prev, pred_x0,
-                       (half_t*)xin_next, rep, B, C, h, w, scale);
-  else
-    hipLaunchKernelGGL((cfg_ddim_rng_kernel<false, true>), dim3(grid_for((long)B * nq, 256)), dim3(256), 0,
-                       (hipStream_t)stream, (const half_t*)eps, nb, x, key, step, noise_mul, coef, x_prev, pred_x0,
-                       (half_t*)xin_next, rep, B, C, h, w, scale);
-  return pfd_check_launch("pfd_cfg_ddim_step_ps");
+  if (!step_args_ok(nb, B, C, h, w, xin_next, rep)) return PFD_EINVAL;
+  if (key && (long)C * h * w > ((long)1 << 34)) return PFD_ESHAPE;
+  if (!key)
+    return launch_ddim(cfg_ddim_kernel<true>, eps, nb, x, noise, coef, scale, x_prev, pred_x0, xin_next, rep, B, C, h, w,
+                       stream, "pfd_cfg_ddim_step_ps");
+  return launch_ddim_rng(cfg_ddim_rng_kernel<true, true>, cfg_ddim_rng_kernel<false, true>, eps, nb, x, key, step,
+                         noise_mul, coef, scale, x_prev, pred_x0, xin_next, rep, B, C, h, w, stream,
+                         "pfd_cfg_ddim_step_ps");
 }
 
 extern "C" int pfd_cfg_dpmpp_step(const void* eps, int32_t nb, const float* x, const float* x0_prev, const float* coef,
                                   const float* scale, float* x_next, float* pred_x0, void* xin_next, int32_t rep,
                                   int32_t B, int32_t C, int32_t h, int32_t w, pfd_stream_t stream) {
   if (!eps || !x || !coef || !x_next || !pred_x0) return PFD_EINVAL;
-  if (nb < 1 || nb > 2 || B <= 0 || C <= 0 || h <= 0 || w <= 0 || (xin_next && (rep < 1 || rep > 2))) return PFD_EINVAL;
+  if (!step_args_ok(nb, B, C, h, w, xin_next, rep)) return PFD_EINVAL;
   if (x0_prev && (x0_prev == x_next || x0_prev == pred_x0)) return PFD_EINVAL;   // the history is read while both are written
   const long ns = (long)C * h * w;
   if (ns > ((long)1 << 34)) return PFD_EINVAL;   // the per-sample bound of the seeded siblings
-  const long n = (long)B * ns;
   PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
-  if (scale)
-    hipLaunchKernelGGL(cfg_dpmpp_kernel<true>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)eps, nb, x, x0_prev, coef, x_next, pred_x0, (half_t*)xin_next, rep, B, C, h, w,
-                       scale);
-  else
-    hipLaunchKernelGGL(cfg_dpmpp_kernel<false>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)eps, nb, x, x0_prev, coef, x_next, pred_x0, (half_t*)xin_next, rep, B, C, h, w,
-                       (const float*)nullptr);
+  const auto kernel = scale ? cfg_dpmpp_kernel<true> : cfg_dpmpp_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(grid_for((long)B * ns, 256)), dim3(256), 0, (hipStream_t)stream, (const half_t*)eps,
+                     nb, x, x0_prev, coef, x_next, pred_x0, (half_t*)xin_next, rep, B, C, h, w, scale);
   return pfd_check_launch("pfd_cfg_dpmpp_step");
 }
 

@@ -862,6 +862,13 @@ def guidance_scale_rows(scale, B, device):
     return scale
 
 
+def _step_outputs(x, rep, want_next):
+    """(x_prev | x_next, pred_x0) fp32 like x, and the next UNet input f16 NHWC [rep*B, h, w, C] or None"""
+    B, Cc, h, w = x.shape
+    xin = torch.empty((rep * B, h, w, Cc), dtype=torch.float16, device=x.device) if want_next else None
+    return torch.empty_like(x), torch.empty_like(x), xin
+
+
 def cfg_ddim_step(eps, nb, x, coef, *, noise=None, want_next=True, rep=None, noise_key=None, step=None, noise_mul=1.0,
                   scale=None):
     """Fused CFG combine + DDIM update.  eps NHWC f16 [nb*B,h,w,C]; x NCHW fp32 [B,C,h,w];
@@ -881,25 +888,17 @@ def cfg_ddim_step(eps, nb, x, coef, *, noise=None, want_next=True, rep=None, noi
         noise_key = noise_key_rows(noise_key, B, x.device)
     if scale is not None:
         scale = guidance_scale_rows(scale, B, x.device)
-    x_prev = torch.empty_like(x)
-    pred_x0 = torch.empty_like(x)
-    xin = torch.empty((rep * B, h, w, Cc), dtype=torch.float16, device=x.device) if want_next else None
+    x_prev, pred_x0, xin = _step_outputs(x, rep, want_next)
+    outs = (x_prev.data_ptr(), pred_x0.data_ptr(), _ptr(xin), rep, B, Cc, h, w, _stream())
     if scale is not None:
-        rc = _lib().pfd_cfg_ddim_step_ps(eps.data_ptr(), nb, x.data_ptr(), _ptr(noise), _ptr(noise_key),
-                                         0 if step is None else int(step), float(noise_mul), coef.data_ptr(),
-                                         scale.data_ptr(), x_prev.data_ptr(), pred_x0.data_ptr(), _ptr(xin), rep, B, Cc,
-                                         h, w, _stream())
-        _b.check(rc, "pfd_cfg_ddim_step_ps")
-        return x_prev, pred_x0, xin
-    if noise_key is not None:
-        rc = _lib().pfd_cfg_ddim_step_rng(eps.data_ptr(), nb, x.data_ptr(), noise_key.data_ptr(), int(step),
-                                          float(noise_mul), coef.data_ptr(), x_prev.data_ptr(), pred_x0.data_ptr(),
-                                          _ptr(xin), rep, B, Cc, h, w, _stream())
-        _b.check(rc, "pfd_cfg_ddim_step_rng")
-        return x_prev, pred_x0, xin
-    rc = _lib().pfd_cfg_ddim_step(eps.data_ptr(), nb, x.data_ptr(), _ptr(noise), coef.data_ptr(), x_prev.data_ptr(),
-                                  pred_x0.data_ptr(), _ptr(xin), rep, B, Cc, h, w, _stream())
-    _b.check(rc, "pfd_cfg_ddim_step")
+        name = "pfd_cfg_ddim_step_ps"
+        args = (_ptr(noise), _ptr(noise_key), 0 if step is None else int(step), float(noise_mul), coef.data_ptr(),
+                scale.data_ptr())
+    elif noise_key is not None:
+        name, args = "pfd_cfg_ddim_step_rng", (noise_key.data_ptr(), int(step), float(noise_mul), coef.data_ptr())
+    else:
+        name, args = "pfd_cfg_ddim_step", (_ptr(noise), coef.data_ptr())
+    _b.check(getattr(_lib(), name)(eps.data_ptr(), nb, x.data_ptr(), *args, *outs), name)
     return x_prev, pred_x0, xin
 
 
@@ -918,9 +917,7 @@ def cfg_dpmpp_step(eps, nb, x, coef, x0_prev=None, want_next=False, rep=None, sc
         raise ValueError("cfg_dpmpp_step: x0_prev must be a contiguous float32 tensor of x's shape, next to x")
     if scale is not None:
         scale = guidance_scale_rows(scale, B, x.device)
-    x_next = torch.empty_like(x)
-    pred_x0 = torch.empty_like(x)
-    xin = torch.empty((rep * B, h, w, Cc), dtype=torch.float16, device=x.device) if want_next else None
+    x_next, pred_x0, xin = _step_outputs(x, rep, want_next)
     rc = _lib().pfd_cfg_dpmpp_step(eps.data_ptr(), nb, x.data_ptr(), _ptr(x0_prev), coef.data_ptr(), _ptr(scale),
                                    x_next.data_ptr(), pred_x0.data_ptr(), _ptr(xin), rep, B, Cc, h, w, _stream())
     _b.check(rc, "pfd_cfg_dpmpp_step")

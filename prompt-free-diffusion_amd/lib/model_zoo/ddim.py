@@ -75,6 +75,55 @@ def _refuse_noise(solver, eta, noise_dropout, x_info):
         raise ValueError(f"solver {solver!r} is deterministic: x_info['noise_key'] is not available")
 
 
+def _guidance(c_info, bs, device):
+    """-> (sps, scale, uc, cfg, nb): the per-sample scale vector or None, the number for the coefficient table (not read
+    with a vector), the unconditional context, whether CFG is on and the number of UNet batches per step"""
+    scale = c_info['unconditional_guidance_scale']
+    uc = c_info.get('unconditional_conditioning', None)
+    sps = per_sample_scale(scale, bs, device)     # moved to the device once per request
+    if sps is not None:
+        if uc is None:
+            raise ValueError("a per-sample guidance scale needs c_info['unconditional_conditioning']")
+        scale = 1.0
+    cfg = sps is not None or not ((scale == 1.) or (uc is None))
+    return sps, scale, uc, cfg, (2 if cfg else 1)
+
+
+def _draw_noise(x, temperature, noise_dropout, repeat_noise=False):
+    """one step's noise from the global generator, as the reference draws it (:166): noise_like, temperature, dropout"""
+    noise = noise_like(x, repeat_noise) * temperature
+    if noise_dropout > 0.:
+        noise = torch.nn.functional.dropout(noise, p=noise_dropout)
+    return noise.contiguous()
+
+
+def _step_noise(x, sigma, index, nkey, temperature, noise_dropout, repeat_noise=False):
+    """the noise arguments of ops.cfg_ddim_step for a step of noise level sigma: none at sigma 0, else the key rows (the
+    noise is evaluated inside the kernel) or, without a key, a draw from the global generator"""
+    if float(sigma) == 0.:
+        return {}
+    if nkey is not None:
+        return dict(noise_key=nkey, step=index, noise_mul=temperature)
+    return dict(noise=_draw_noise(x, temperature, noise_dropout, repeat_noise))
+
+
+class _CapturedLoop:
+    """one captured trajectory: the hipGraph, its static inputs in the order (x, c_in, hint, nkey, sps) -- None where the
+    request has none --, its static outputs and what must live as long as the graph"""
+
+    def __init__(self, graph, inputs, outs, keep):
+        self.graph, self.inputs, self.outs, self.keep = graph, inputs, outs, keep
+
+    def replay(self, inputs):
+        """the request's tensors into the static inputs, one replay, copies of the static outputs"""
+        for static, t in zip(self.inputs, inputs):
+            if static is not None:
+                static.copy_(t)
+        self.graph.replay()
+        x, inter_xt, inter_x0 = self.outs
+        return x.clone(), [t.clone() for t in inter_xt], [t.clone() for t in inter_x0]
+
+
 class DDIMSampler(object):
     def __init__(self, model, schedule="linear", **kwargs):
         super().__init__()
@@ -155,28 +204,9 @@ class DDIMSampler(object):
         device = model.device
         dtype = c_info['conditioning'].dtype
         bs = shape[0]
-        timesteps = self.ddim_timesteps
-        if x_info.get('xt', None) is not None:
-            x = x_info['xt'].to(device=device, dtype=torch.float32)
-        elif x_info.get('x0', None) is not None:  # img2img: start from a noised encoding
-            x0 = x_info['x0'].to(device=device, dtype=torch.float32)
-            k = x_info['x0_forward_timesteps']
-            ts = torch.as_tensor(np.repeat(timesteps[k], bs)).long().to(device)
-            timesteps = timesteps[:k]
-            x = model.q_sample(x0, ts)
-        else:
-            x = torch.randn(shape, device=device, dtype=dtype).to(torch.float32)
-        x = x.contiguous()
-
-        scale = c_info['unconditional_guidance_scale']
-        uc = c_info.get('unconditional_conditioning', None)
+        x, timesteps = self._start_latent(x_info, shape, dtype, self.ddim_timesteps)
         cond = c_info['conditioning']
-        sps = per_sample_scale(scale, bs, device)     # moved to the device once per request
-        if sps is not None:
-            if uc is None:
-                raise ValueError("a per-sample guidance scale needs c_info['unconditional_conditioning']")
-            scale = 1.0                               # column 4 of the coefficient table: not read on this path
-        cfg = sps is not None or not ((scale == 1.) or (uc is None))
+        sps, scale, uc, cfg, nb = _guidance(c_info, bs, device)
         if cfg and uc.shape[0] == 1 and cond.shape[0] > 1:
             # app.py:239-241 loads ONE fixed unconditional context (SeeCoder-Anime) whatever n_samples is; the
             # reference's torch.cat below then fails for n_samples > 1 -- broadcast it instead
@@ -190,7 +220,6 @@ class DDIMSampler(object):
         hint = None
         if control is not None and hasattr(model, 'ctl'):
             hint = model.ctl.prepare_hint(control).feat    # step/sample-invariant: once per request
-        nb = 2 if cfg else 1
         coef = self._coef_table(scale) if order is None else self._dpmpp_table(scale, order)
         time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
@@ -206,16 +235,15 @@ class DDIMSampler(object):
                                  "global generator: leave the key out)")
             nkey = ops.noise_key_rows(nkey, bs, device)
 
-        def make_loop(n):
-            """the whole trajectory of n samples as a pure function of device tensors (capturable as one hipGraph)"""
-            t_table = t_col.repeat(1, nb * n)
-            zl = n if zero_lead else 0
+        def make_loop():
+            """the whole trajectory as a pure function of device tensors (capturable as one hipGraph), and its timestep table"""
+            t_table = t_col.repeat(1, nb * bs)
 
-            def run_loop(x, c_in, hint, nkey=None, sps=None):
-                ps = {} if sps is None else {'scale': sps}
+            def run_loop(x, c_in, hint, nkey, sps):
                 from .controlnet import PreparedHint
+                ps = {} if sps is None else {'scale': sps}
                 ctx = model.prepare_context(c_in)
-                ctx.zero_lead = zl
+                ctx.zero_lead = zero_lead
                 ctl = PreparedHint(hint) if hint is not None else None
                 # every ResBlock's time-embedding projection for ALL steps in one GEMM (t is the same for
                 # every sample of a step): [total_steps, sum Cout]
@@ -232,13 +260,6 @@ class DDIMSampler(object):
                     index = total_steps - i - 1
                     eps = model.apply_model_nhwc(x_type, xin, t_table[i], c_type, ctx, control=ctl,
                                                  emb_table=emb_all[i:i + 1], cfg_pair=pair)
-                    noise = None
-                    keyed = nkey is not None and self.ddim_sigmas[index] != 0.
-                    if self.ddim_sigmas[index] != 0. and not keyed:
-                        noise = noise_like(x) * temperature
-                        if noise_dropout > 0.:
-                            noise = torch.nn.functional.dropout(noise, p=noise_dropout)
-                        noise = noise.contiguous()
                     if order is not None:
                         # multistep: this step's pred_x0 is the next step's history; none on the first step of a run
                         # (an img2img start included) nor on the last, nor at order 1
@@ -246,12 +267,9 @@ class DDIMSampler(object):
                         x, pred_x0, xin = ops.cfg_dpmpp_step(eps, nb, x, coef[index], None if first_order else x0_last,
                                                              want_next=True, rep=rep, **ps)
                         x0_last = pred_x0
-                    elif keyed:   # sigma * temperature * z(key row, index, element), drawn inside the kernel
-                        x, pred_x0, xin = ops.cfg_ddim_step(eps, nb, x, coef[index], want_next=True, rep=rep,
-                                                            noise_key=nkey, step=index, noise_mul=temperature, **ps)
                     else:
-                        x, pred_x0, xin = ops.cfg_ddim_step(eps, nb, x, coef[index], noise=noise, want_next=True,
-                                                            rep=rep, **ps)
+                        noise = _step_noise(x, self.ddim_sigmas[index], index, nkey, temperature, noise_dropout)
+                        x, pred_x0, xin = ops.cfg_ddim_step(eps, nb, x, coef[index], want_next=True, rep=rep, **ps, **noise)
                     if index % log_every_t == 0 or index == total_steps - 1:
                         inter_xt.append(x)
                         inter_x0.append(pred_x0)
@@ -260,9 +278,9 @@ class DDIMSampler(object):
                 return x, inter_xt, inter_x0
             return run_loop, t_table
 
+        inputs = (x, c_in, hint, nkey, sps)
         # a keyed schedule draws nothing from a generator: capturable whatever eta is
-        use_graph = self.use_graph and (not stochastic or nkey is not None) and callback is None and x.is_cuda
-        if use_graph:
+        if self.use_graph and (not stochastic or nkey is not None) and callback is None and x.is_cuda:
             # one hipGraph per (shape, schedule, weights version, flags); static input buffers, replayed per request.
             # (Round 4 also cut the batch into concurrent sub-batch graphs on their own streams: 520 -> 646 ms per batch at
             #  C2, profiles/r04_lanes_ab.log -- removed in round 5.)
@@ -272,34 +290,42 @@ class DDIMSampler(object):
                    None if nkey is None else (float(temperature), hash(np.asarray(self.ddim_sigmas).tobytes())))
             if order is not None:
                 key = key + (solver,)          # the DDIM key is what it was
-            ent = self._graphs.pop(key, None)
-            if ent is None:
-                while len(self._graphs) >= self.max_graphs:
-                    torch.cuda.synchronize()   # never drop a graph whose replay may still be in flight
-                    self._graphs.pop(next(iter(self._graphs)))   # least recently used (a server varies batch size and
-                run_loop, t_table = make_loop(bs)                 # scale per request: keep the others)
-                ent = self._capture(run_loop, x, c_in, hint, (coef, t_table), nkey, sps)
-            self._graphs[key] = ent            # (re-)inserted last = most recently used
-            g, sx, sc, sh, outs, _keep, sk, ss = ent
-            sx.copy_(x)
-            sc.copy_(c_in)
-            if sh is not None:
-                sh.copy_(hint)
-            if sk is not None:
-                sk.copy_(nkey)
-            if ss is not None:
-                ss.copy_(sps)
-            g.replay()
-            xf = outs[0].clone()               # static output buffers of the graph
-            ixt = [t.clone() for t in outs[1]]
-            ix0 = [t.clone() for t in outs[2]]
+            xf, ixt, ix0 = self._graph_for(key, lambda: self._capture(*make_loop(), inputs, coef)).replay(inputs)
         else:
-            run_loop, _ = make_loop(bs)
-            xf, ixt, ix0 = run_loop(x, c_in, hint, nkey, sps)
+            xf, ixt, ix0 = make_loop()[0](*inputs)
         intermediates = {'pred_xt': [t.to(dtype) for t in ixt], 'pred_x0': [t.to(dtype) for t in ix0]}
         out = xf.to(dtype)
         x_info['x'] = out
         return out, intermediates
+
+    def _start_latent(self, x_info, shape, dtype, timesteps):
+        """-> (x fp32 contiguous, timesteps): x_info['xt'] as given; an img2img start, x_info['x0'] noised to step
+        x_info['x0_forward_timesteps'] with the run shortened to the steps below it; else a draw like the reference's (:105)"""
+        device = self.model.device
+        if x_info.get('xt', None) is not None:
+            x = x_info['xt'].to(device=device, dtype=torch.float32)
+        elif x_info.get('x0', None) is not None:
+            x0 = x_info['x0'].to(device=device, dtype=torch.float32)
+            k = x_info['x0_forward_timesteps']
+            ts = torch.as_tensor(np.repeat(timesteps[k], shape[0])).long().to(device)
+            timesteps = timesteps[:k]
+            x = self.model.q_sample(x0, ts)
+        else:
+            x = torch.randn(shape, device=device, dtype=dtype).to(torch.float32)
+        return x.contiguous(), timesteps
+
+    def _single_step(self, x_info, eps, nb, xf, dtype, scale, sps, index, repeat_noise, use_original_steps,
+                     noise_dropout, temperature):
+        """the tail of p_sample_ddim and p_sample_ddim_multicontext: coefficient row, noise, the step -> (x_prev, pred_x0)"""
+        coef = self._coef_table(scale, use_original_steps)[index]
+        sig = (self.ddim_sigmas_for_original_num_steps if use_original_steps else self.ddim_sigmas)[index]
+        nkey = x_info.get('noise_key', None)
+        if nkey is not None and noise_dropout > 0.:
+            raise ValueError("noise_dropout > 0 is not available with x_info['noise_key']")
+        ps = {} if sps is None else {'scale': sps}
+        noise = _step_noise(xf, sig, index, nkey, temperature, noise_dropout, repeat_noise)
+        x_prev, pred_x0, _ = ops.cfg_ddim_step(eps, nb, xf, coef, want_next=False, **ps, **noise)
+        return x_prev.to(dtype), pred_x0.to(dtype)
 
     # ---- multi-context sampling (ddim.py:174-299) ------------------------------------------------
     @ops.serialised
@@ -345,18 +371,7 @@ class DDIMSampler(object):
         device = model.device
         dtype = c_info_list[0]['conditioning'].dtype
         bs = shape[0]
-        timesteps = self.ddim_timesteps
-        if x_info.get('xt', None) is not None:
-            x = x_info['xt'].to(device=device, dtype=torch.float32)
-        elif x_info.get('x0', None) is not None:
-            x0 = x_info['x0'].to(device=device, dtype=torch.float32)
-            k = x_info['x0_forward_timesteps']
-            ts = torch.as_tensor(np.repeat(timesteps[k], bs)).long().to(device)
-            timesteps = timesteps[:k]
-            x = model.q_sample(x0, ts)
-        else:
-            x = torch.randn(shape, device=device, dtype=dtype).to(torch.float32)
-        x = x.contiguous()
+        x, timesteps = self._start_latent(x_info, shape, dtype, self.ddim_timesteps)
         mix, scale, nb = self._mix_for(c_info_list, bs)   # context K / V^T: once per request
         coef = self._coef_table(scale)
         time_range = np.flip(timesteps)
@@ -369,13 +384,8 @@ class DDIMSampler(object):
         for i in range(total_steps):
             index = total_steps - i - 1
             eps = model.apply_model_nhwc(x_type, xin, t_table[i], None, mix, emb_table=emb_all[i:i + 1])
-            noise = None
-            if self.ddim_sigmas[index] != 0.:
-                noise = noise_like(x) * temperature
-                if noise_dropout > 0.:
-                    noise = torch.nn.functional.dropout(noise, p=noise_dropout)
-                noise = noise.contiguous()
-            x, pred_x0, xin = ops.cfg_ddim_step(eps, nb, x, coef[index], noise=noise, want_next=True)
+            noise = _step_noise(x, self.ddim_sigmas[index], index, None, temperature, noise_dropout)
+            x, pred_x0, xin = ops.cfg_ddim_step(eps, nb, x, coef[index], want_next=True, **noise)
             if index % log_every_t == 0 or index == total_steps - 1:
                 inter['pred_xt'].append(x.to(dtype))
                 inter['pred_x0'].append(pred_x0.to(dtype))
@@ -394,22 +404,8 @@ class DDIMSampler(object):
             x_info['x'] = torch.cat([x] * 2)      # the reference leaves the doubled batch behind (:271)
         xf = x.to(torch.float32).contiguous()
         eps = self.model.apply_model_nhwc(x_info['type'], ops.to_nhwc(xf, rep=nb), t_in, None, mix)
-        coef = self._coef_table(scale, use_original_steps)[index]
-        noise = None
-        sig = (self.ddim_sigmas_for_original_num_steps if use_original_steps else self.ddim_sigmas)[index]
-        nkey = x_info.get('noise_key', None)
-        if nkey is not None and noise_dropout > 0.:
-            raise ValueError("noise_dropout > 0 is not available with x_info['noise_key']")
-        if nkey is not None and float(sig) != 0.:
-            x_prev, pred_x0, _ = ops.cfg_ddim_step(eps, nb, xf, coef, want_next=False, noise_key=nkey, step=index,
-                                                   noise_mul=temperature)
-            return x_prev.to(x.dtype), pred_x0.to(x.dtype)
-        if float(sig) != 0.:
-            noise = (noise_like(xf, repeat_noise) * temperature).contiguous()
-            if noise_dropout > 0.:
-                noise = torch.nn.functional.dropout(noise, p=noise_dropout).contiguous()
-        x_prev, pred_x0, _ = ops.cfg_ddim_step(eps, nb, xf, coef, noise=noise, want_next=False)
-        return x_prev.to(x.dtype), pred_x0.to(x.dtype)
+        return self._single_step(x_info, eps, nb, xf, x.dtype, scale, None, index, repeat_noise, use_original_steps,
+                                 noise_dropout, temperature)
 
     # ---- hipGraph plumbing (launch-bound loop: ~700 kernel launches per step) -------------------
     use_graph = False
@@ -433,23 +429,33 @@ class DDIMSampler(object):
         from ..hip.layers import generation
         return hash((generation(),) + tuple((p.data_ptr(), p._version) for p in self.model.parameters()))
 
-    def _capture(self, run_loop, x, c_in, hint, keep, nkey=None, sps=None):
+    def _capture(self, run_loop, t_table, inputs, coef):
+        """run_loop captured on clones of `inputs`; the two tables its kernels read live as long as the graph"""
         from ..hip import binding
         binding.prof_enable(False)  # event timing cannot be captured
-        sx, sc = x.clone(), c_in.clone()
-        sh = hint.clone() if hint is not None else None
-        sk = nkey.clone() if nkey is not None else None
-        ss = sps.clone() if sps is not None else None
+        static = [None if t is None else t.clone() for t in inputs]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):     # warm-up outside capture: packs weights, sizes the allocator
-            run_loop(sx, sc, sh, sk, ss)
+            run_loop(*static)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            outs = run_loop(sx, sc, sh, sk, ss)
-        return g, sx, sc, sh, outs, keep, sk, ss
+            outs = run_loop(*static)
+        return _CapturedLoop(g, static, outs, (coef, t_table))
+
+    def _graph_for(self, key, capture):
+        """the captured loop of `key`, captured now if it is new; kept in order of use, the least recently used dropped at
+        max_graphs (a server varies batch size and scale per request: keep the others)"""
+        ent = self._graphs.pop(key, None)
+        if ent is None:
+            while len(self._graphs) >= self.max_graphs:
+                torch.cuda.synchronize()   # never drop a graph whose replay may still be in flight
+                self._graphs.pop(next(iter(self._graphs)))
+            ent = capture()
+        self._graphs[key] = ent            # (re-)inserted last = most recently used
+        return ent
 
     @ops.serialised
     @torch.no_grad()
@@ -459,17 +465,7 @@ class DDIMSampler(object):
         (x_prev, pred_x0) in x.dtype); the loop above uses the same kernels without the
         per-step layout conversions."""
         x = x_info['x']
-        b = x.shape[0]
-        scale = c_info['unconditional_guidance_scale']
-        uc = c_info.get('unconditional_conditioning', None)
-        sps = per_sample_scale(scale, b, x.device)
-        if sps is not None:
-            if uc is None:
-                raise ValueError("a per-sample guidance scale needs c_info['unconditional_conditioning']")
-            scale = 1.0
-        ps = {} if sps is None else {'scale': sps}
-        cfg = sps is not None or not ((scale == 1.) or (uc is None))
-        nb = 2 if cfg else 1
+        sps, scale, uc, cfg, nb = _guidance(c_info, x.shape[0], x.device)
         if cfg:
             c_in = torch.cat([uc, c_info['conditioning']])
             t_in = torch.cat([t] * 2)
@@ -482,19 +478,5 @@ class DDIMSampler(object):
         xf = x.to(torch.float32).contiguous()
         eps = self.model.apply_model_nhwc(x_info['type'], ops.to_nhwc(xf, rep=nb), t_in, c_info['type'], ctx,
                                           control=c_info.get('control', None))
-        coef = self._coef_table(scale, use_original_steps)[index]
-        noise = None
-        sig = (self.ddim_sigmas_for_original_num_steps if use_original_steps else self.ddim_sigmas)[index]
-        nkey = x_info.get('noise_key', None)
-        if nkey is not None and noise_dropout > 0.:
-            raise ValueError("noise_dropout > 0 is not available with x_info['noise_key']")
-        if nkey is not None and float(sig) != 0.:
-            x_prev, pred_x0, _ = ops.cfg_ddim_step(eps, nb, xf, coef, want_next=False, noise_key=nkey, step=index,
-                                                   noise_mul=temperature, **ps)
-            return x_prev.to(x.dtype), pred_x0.to(x.dtype)
-        if float(sig) != 0.:
-            noise = (noise_like(xf, repeat_noise) * temperature).contiguous()
-            if noise_dropout > 0.:
-                noise = torch.nn.functional.dropout(noise, p=noise_dropout).contiguous()
-        x_prev, pred_x0, _ = ops.cfg_ddim_step(eps, nb, xf, coef, noise=noise, want_next=False, **ps)
-        return x_prev.to(x.dtype), pred_x0.to(x.dtype)
+        return self._single_step(x_info, eps, nb, xf, x.dtype, scale, sps, index, repeat_noise, use_original_steps,
+                                 noise_dropout, temperature)
