@@ -433,6 +433,22 @@ int pfd_cfg_ddim_step_ps(const void* eps, int32_t nb, const float* x, const floa
 int pfd_cfg_dpmpp_step(const void* eps, int32_t nb, const float* x, const float* x0_prev, const float* coef,
                        const float* scale, float* x_next, float* pred_x0, void* xin_next, int32_t rep,
                        int32_t B, int32_t C, int32_t h, int32_t w, pfd_stream_t stream);
+/* The seeded latent start of an image-to-image request, one launch: the VAE posterior's sample (distributions.py:24-62),
+ * the latent scale (pfd.py vae_encode) and the forward noising q(x_t | x_0) (pfd.py:204-207; the x0 branch of
+ * ddim.py:213-219 composes the same three from two draws of the global generator):
+ *   std = expf(0.5 * clamp(logvar, -30, 20));  x0 = scale_factor * (mean + posterior_mul * std * z_p)
+ *   x_t = sq_at * x0 + sq_1mat * z_q
+ * moments: f16 NHWC [Bm, h, w, 2C], what the VAE's quant_conv GEMM writes: per pixel the C means, then the C logvars.
+ * Bm is 1 (one picture shared by the B samples) or B.  key: device int64 [B, 2] = {seed, sample_id} per sample.
+ * z_q / z_p of element e (NCHW order inside the sample, e = (c*h + y)*w + x) are the normals of pfd_philox_normal_f32 at
+ * step 0 with the counter's fourth word -- 0 for the step noise -- set to 1 (z_q) and 2 (z_p): a sample's start depends on
+ * its key row and its picture only.  sq_at = sqrt(a_t), sq_1mat = sqrt(1 - a_t) of the level the run starts at;
+ * posterior_mul: 1 samples the posterior, 0 takes its mode.  x0 (may be NULL), xt: fp32 NCHW [B, C, h, w].
+ * lib/img2img.py is the same specification on the host.  NULL moments / key / xt, Bm not in {1, B} or a dimension <= 0
+ * is PFD_EINVAL; C*h*w > 2^34 is PFD_ESHAPE; nothing is launched then. */
+int pfd_latent_start(const void* moments, int32_t Bm, const int64_t* key, float scale_factor, float sq_at,
+                     float sq_1mat, float posterior_mul, float* x0, float* xt, int32_t B, int32_t C, int32_t h,
+                     int32_t w, pfd_stream_t stream);
 /* y = a + b (f16, fp32 add), n elements; b may be NULL (copy). */
 int pfd_add_f16(const void* a, const void* b, void* y, int64_t n, pfd_stream_t stream);
 /* y = alpha*a + beta*b (f16 storage, fp32 math), n elements; b may be NULL (y = alpha*a).  The

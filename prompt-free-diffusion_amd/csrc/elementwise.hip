@@ -212,7 +212,7 @@ __global__ void philox_normal_kernel(const int64_t* __restrict__ key, int step, 
     const int b = (int)(i / nq);
     const long q = i - (long)b * nq;
     float z[4];
-    pfd_philox_normal4(key[2 * b], key[2 * b + 1], step, (uint32_t)q, z);
+    pfd_philox_normal4(key[2 * b], key[2 * b + 1], step, (uint32_t)q, PFD_STREAM_STEP, z);
     float* o = out + (long)b * ns + q * 4;
     if (VEC) {
       *reinterpret_cast<float4*>(o) = make_float4(z[0], z[1], z[2], z[3]);
@@ -247,7 +247,7 @@ __global__ void cfg_ddim_rng_kernel(const half_t* __restrict__ eps, int nb, cons
     const long base = (long)b * ns + e0;
     const float scale = PS ? scale_ps[b] : scale_all;
     float z[4], xv[4], xp4[4], p04[4];
-    pfd_philox_normal4(key[2 * b], key[2 * b + 1], step, (uint32_t)q, z);
+    pfd_philox_normal4(key[2 * b], key[2 * b + 1], step, (uint32_t)q, PFD_STREAM_STEP, z);
     if (VEC) {
       const float4 v = *reinterpret_cast<const float4*>(x + base);
       xv[0] = v.x; xv[1] = v.y; xv[2] = v.z; xv[3] = v.w;

@@ -42,9 +42,16 @@ PFD_HD void pfd_box_muller(uint32_t ra, uint32_t rb, float* z0, float* z1) {
   *z1 = rad * sinpif(2.0f * v);
 }
 
-// the normals of elements 4q .. 4q+3 of sample (seed, sample_id) at DDIM step `step`
-PFD_HD void pfd_philox_normal4(int64_t seed, int64_t sample_id, int32_t step, uint32_t q, float z[4]) {
-  uint32_t c[4] = {q, (uint32_t)step, (uint32_t)((uint64_t)sample_id & 0xffffffffu), 0u};
+// the fourth counter word names the stream a draw belongs to: the same (seed, sample_id, step, element) gives unrelated
+// normals in different streams.  0: the step noise (what the word always was); 1 / 2: the forward-noising noise and the
+// posterior noise of an img2img start (latent.hip), both at step 0
+#define PFD_STREAM_STEP 0u
+#define PFD_STREAM_Q 1u
+#define PFD_STREAM_POSTERIOR 2u
+
+// the normals of elements 4q .. 4q+3 of sample (seed, sample_id) at DDIM step `step` in stream `stream`
+PFD_HD void pfd_philox_normal4(int64_t seed, int64_t sample_id, int32_t step, uint32_t q, uint32_t stream, float z[4]) {
+  uint32_t c[4] = {q, (uint32_t)step, (uint32_t)((uint64_t)sample_id & 0xffffffffu), stream};
   pfd_philox4x32_10(c, (uint32_t)((uint64_t)seed & 0xffffffffu), (uint32_t)(((uint64_t)seed >> 32) & 0xffffffffu));
   pfd_box_muller(c[0], c[1], &z[0], &z[1]);
   pfd_box_muller(c[2], c[3], &z[2], &z[3]);

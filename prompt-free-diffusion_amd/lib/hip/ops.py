@@ -851,6 +851,36 @@ def philox_normal(key, step, n_per_sample):
     return out
 
 
+def latent_start(moments_nhwc, key, scale_factor, a_t, B=None, posterior='sample', want_x0=False):
+    """The seeded start of an img2img request in one launch (pfd_latent_start; lib/img2img.py is the same function on the
+    host).  moments_nhwc: f16 NHWC [Bm, h, w, 2C], what `quant_conv.hip(...)` returns, Bm = 1 (one picture for all
+    samples) or B; key: int64 [B, 2] rows (seed, sample_id), B = key.shape[0] unless given; a_t: the cumulative alpha of
+    the first timestep the run evaluates.  -> x_t fp32 NCHW [B, C, h, w], or (x0, x_t) with want_x0."""
+    from ..img2img import check_posterior, kernel_scalars
+    check_posterior(posterior)
+    if not (torch.is_tensor(moments_nhwc) and moments_nhwc.dtype == torch.float16 and moments_nhwc.dim() == 4 and
+            moments_nhwc.shape[3] % 2 == 0):
+        raise ValueError("latent_start: moments must be an f16 NHWC tensor [Bm, h, w, 2C]")
+    if not torch.is_tensor(key) or key.dim() != 2:
+        raise ValueError("latent_start: key must be an int64 tensor [B, 2] of (seed, sample_id) rows")
+    B = int(key.shape[0]) if B is None else int(B)
+    Bm, h, w, C2 = moments_nhwc.shape
+    if Bm not in (1, B):
+        raise ValueError(f"latent_start: {Bm} pictures for {B} samples (one shared picture, or one per sample)")
+    sf, sq_at, sq_1mat = (float(v) for v in kernel_scalars(scale_factor, a_t))
+    if not moments_nhwc.is_cuda:
+        raise RuntimeError("latent_start: moments must live on the GPU; the HIP path has no CPU fallback")
+    if not moments_nhwc.is_contiguous():
+        raise ValueError("latent_start: dense NHWC moments expected")
+    key = noise_key_rows(key, B, moments_nhwc.device)
+    xt = torch.empty((B, C2 // 2, h, w), dtype=torch.float32, device=moments_nhwc.device)
+    x0 = torch.empty_like(xt) if want_x0 else None
+    rc = _lib().pfd_latent_start(moments_nhwc.data_ptr(), Bm, key.data_ptr(), sf, sq_at, sq_1mat,
+                                 1.0 if posterior == 'sample' else 0.0, _ptr(x0), xt.data_ptr(), B, C2 // 2, h, w, _stream())
+    _b.check(rc, "pfd_latent_start")
+    return (x0, xt) if want_x0 else xt
+
+
 def guidance_scale_rows(scale, B, device):
     """the per-sample guidance scales of cfg_ddim_step, checked: a contiguous float32 tensor [B] on the GPU (the step
     runs inside a captured loop, so nothing is converted or copied here: DDIMSampler moves the vector once per request)"""

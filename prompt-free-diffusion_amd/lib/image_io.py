@@ -9,6 +9,8 @@ holds what those kernels need from the host and nothing else:
     (doubles, as Pillow's C code), no torch, no numpy, no Pillow.
   * `to_device_u8` / `check_u8_picture`: argument checks of a uint8 picture and its move to the device.
   * `check_control_preprocess`: argument checks of the optional edge detector in front of the hint encoder (csrc/canny.hip).
+  * `check_init_picture` / `check_img2img`: argument checks of an img2img request's init picture, strength and posterior
+    (lib/img2img.py, csrc/latent.hip).
 """
 import math
 
@@ -116,6 +118,32 @@ def check_control_preprocess(control, preprocess, thresholds):
     if preprocess is not None and control is None:
         raise ValueError(f"control_preprocess={preprocess!r} without a control picture")
     return low, high
+
+
+def check_init_picture(init, height, width, what="init"):
+    """the `init` picture of an img2img request: a uint8 picture [h, w, 3] of any size the kernels can resize to
+    (height, width), or a float tensor [1, 3, height, width] in [0, 1].  -> True for the uint8 form.  Raises ValueError;
+    touches no device."""
+    height, width = int(height), int(width)
+    if height < 8 or width < 8 or height % 8 or width % 8:
+        raise ValueError(f"{what}: the output size must be a positive multiple of 8 (the VAE's stride), got {height} x {width}")
+    if wants_ingest(init):
+        check_resize(check_u8_picture(init, what)[:2], (height, width), what)
+        return True
+    if not (init.is_floating_point() and tuple(init.shape) == (1, 3, height, width)):
+        raise ValueError(f"{what} must be a float tensor [1, 3, {height}, {width}] in [0, 1] or a uint8 picture [h, w, 3], "
+                         f"got {tuple(init.shape)} {init.dtype}")
+    return False
+
+
+def check_img2img(init, height, width, steps, strength, posterior='sample', what="init"):
+    """everything an img2img request can get wrong before a device is touched -> k, the number of steps it runs
+    (lib/img2img.py::start_steps)"""
+    from .img2img import check_posterior, start_steps
+    k = start_steps(steps, strength)
+    check_posterior(posterior)
+    check_init_picture(init, height, width, what)
+    return k
 
 
 def wants_ingest(x):

@@ -59,10 +59,28 @@ class AutoencoderKL(nn.Module):
         return self.encode_trainable(x, out_posterior)
 
     def encode_trainable(self, x, out_posterior=False):
-        h = self.encoder.hip(ops.to_nhwc(x, mul=2.0, add=-1.0))
-        moments = ops.to_nchw(self.quant_conv.hip(h), x.dtype)
+        moments = ops.to_nchw(self.encode_moments_nhwc(x, layout='nchw'), x.dtype)
         posterior = DiagonalGaussianDistribution(moments)
         return posterior if out_posterior else posterior.sample()
+
+    def encode_moments_nhwc(self, x, layout=None):
+        """picture in [0, 1] -> the posterior's moments as the quant_conv GEMM leaves them: f16 NHWC [B, H/8, W/8, 2*zc],
+        per pixel the zc means, then the zc logvars (what ops.latent_start reads; `encode` is this + ops.to_nchw).
+        x: NCHW float [B, 3, H, W], or -- layout 'nhwc' -- the f16 NHWC [B, H, W, 3] of ops.image_from_u8(...,
+        layout='nhwc').  layout None: 'nhwc' for an f16 tensor with 3 channels last and not 3 second.  A deterministic
+        function of x and the weights: capturable."""
+        if layout is None:
+            layout = 'nhwc' if (x.dtype == torch.float16 and x.dim() == 4 and x.shape[3] == 3 and x.shape[1] != 3) else 'nchw'
+        if layout == 'nhwc':
+            if not (x.dtype == torch.float16 and x.dim() == 4 and x.shape[3] == 3 and x.is_contiguous()):
+                raise ValueError("encode_moments_nhwc: an NHWC picture must be a dense f16 tensor [B, H, W, 3]")
+            # x*2-1 without a change of layout: the boundary kernel on the picture seen as one row of one channel
+            xin = ops.to_nhwc(x.reshape(1, 1, 1, -1), mul=2.0, add=-1.0).reshape(x.shape)
+        elif layout == 'nchw':
+            xin = ops.to_nhwc(x, mul=2.0, add=-1.0)
+        else:
+            raise ValueError(f"encode_moments_nhwc: layout must be 'nchw' or 'nhwc', got {layout!r}")
+        return self.quant_conv.hip(self.encoder.hip(xin))
 
     @torch.no_grad()
     def decode(self, z, in_scale=1.0, out_uint8=False):

@@ -36,6 +36,12 @@ previous step's pred_x0 as its history; the first and the last step are first-or
 kernel at order 1 on every step, which is DDIM at eta 0.  Both are deterministic (eta = 0 only, no noise key, no
 dropout, no multi-context), are captured as a hipGraph like eta = 0 and take a per-sample scale; the graph key carries
 the solver name only for them.  With the default `solver='ddim'` nothing changes.
+
+Shortened run from a given latent (opt-in): x_info['xt'] together with x_info['xt_steps'] = k runs the k steps
+ddim_timesteps[:k] from that latent, which the caller noised to the level of ddim_timesteps[k - 1] (the seeded img2img
+start of ops.latent_start, lib/img2img.py); every solver, the multi-context loop included.  The graph key already
+carries the step count and the timesteps.  Without 'xt_steps' nothing changes; the x_info['x0'] branch keeps the
+reference's convention (noised to ddim_timesteps[k]).
 """
 import numpy as np
 import torch
@@ -299,11 +305,18 @@ class DDIMSampler(object):
         return out, intermediates
 
     def _start_latent(self, x_info, shape, dtype, timesteps):
-        """-> (x fp32 contiguous, timesteps): x_info['xt'] as given; an img2img start, x_info['x0'] noised to step
-        x_info['x0_forward_timesteps'] with the run shortened to the steps below it; else a draw like the reference's (:105)"""
+        """-> (x fp32 contiguous, timesteps): x_info['xt'] as given -- with x_info['xt_steps'] = k it is a latent at the
+        level of timesteps[k - 1] (ops.latent_start) and the run is the k steps timesteps[:k] --; an img2img start,
+        x_info['x0'] noised to step x_info['x0_forward_timesteps'] with the run shortened to the steps below it; else a
+        draw like the reference's (:105)"""
         device = self.model.device
         if x_info.get('xt', None) is not None:
             x = x_info['xt'].to(device=device, dtype=torch.float32)
+            k = x_info.get('xt_steps', None)
+            if k is not None:
+                if int(k) != k or not 1 <= int(k) <= len(timesteps):
+                    raise ValueError(f"x_info['xt_steps'] must be an integer in [1, {len(timesteps)}], got {k!r}")
+                timesteps = timesteps[:int(k)]
         elif x_info.get('x0', None) is not None:
             x0 = x_info['x0'].to(device=device, dtype=torch.float32)
             k = x_info['x0_forward_timesteps']

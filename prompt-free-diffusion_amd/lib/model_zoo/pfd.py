@@ -135,6 +135,14 @@ class PromptFreeDiffusion(nn.Module):
 
     @ops.serialised
     @torch.no_grad()
+    def vae_encode_moments(self, x, which, **kwargs):
+        """picture in [0, 1] (NCHW float, or the f16 NHWC of ops.image_from_u8) -> the posterior's moments, f16 NHWC
+        [B, H/8, W/8, 2*zc], unscaled: the input of ops.latent_start, which samples, scales and noises them in one launch
+        (`vae_encode` is the reference's surface: a sample drawn from the global generator)"""
+        return self.vae[which].encode_moments_nhwc(x, **kwargs)
+
+    @ops.serialised
+    @torch.no_grad()
     def vae_decode(self, z, which, **kwargs):
         scale = (self.latent_scale_factor or {}).get(which, None)
         return self.vae[which].decode(z, in_scale=1.0 if scale is None else 1. / scale, **kwargs)

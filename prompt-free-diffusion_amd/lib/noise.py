@@ -6,8 +6,11 @@ is the specification restated, the oracle of the tests, and the way to reproduce
 The noise of element e (NCHW order inside the sample, e = (c*h + y)*w + x) of sample (seed, sample_id) at DDIM
 step index `step` is output word e & 3 -> normal of
 
-    Philox4x32-10(counter = (e >> 2, step, sample_id & 0xffffffff, 0),
+    Philox4x32-10(counter = (e >> 2, step, sample_id & 0xffffffff, stream),
                   key     = (seed & 0xffffffff, (seed >> 32) & 0xffffffff))
+
+`stream` is 0 for the step noise (the word was always 0: those draws are what they were), 1 for the forward-noising
+noise and 2 for the posterior noise of an img2img start (lib/img2img.py, csrc/latent.hip), both at step 0;
 
 with words (r0, r1) -> (z0, z1) and (r2, r3) -> (z2, z3) by Box-Muller:
 
@@ -47,14 +50,23 @@ def key_words(seed):
     return seed & _MASK, (seed >> 32) & _MASK
 
 
-def normal(seed, sample_id, step, n):
-    """float32 [n]: the noise of the first n elements of sample (seed, sample_id) at DDIM step `step`"""
+STREAM_STEP, STREAM_Q, STREAM_POSTERIOR = 0, 1, 2
+
+
+def normal(seed, sample_id, step, n, stream=0):
+    """float32 [n]: the noise of the first n elements of sample (seed, sample_id) at DDIM step `step` in `stream`"""
+    return normal64(seed, sample_id, step, n, stream).astype(np.float32)
+
+
+def normal64(seed, sample_id, step, n, stream=0):
+    """`normal` before its one rounding: float64 [n]"""
     n = int(n)
     nq = (n + 3) // 4
     ctr = np.zeros((nq, 4), dtype=np.uint64)
     ctr[:, 0] = np.arange(nq, dtype=np.uint64)
     ctr[:, 1] = int(step) & _MASK
     ctr[:, 2] = int(sample_id) & _MASK
+    ctr[:, 3] = int(stream) & _MASK
     r = philox4x32_10(ctr, np.array(key_words(seed), dtype=np.uint64)).astype(np.uint64)
     ra, rb = r[:, 0::2], r[:, 1::2]                                   # [nq, 2] each: (r0, r2), (r1, r3)
     u = ((ra >> np.uint64(8)) + np.uint64(1)).astype(np.float64) * 2.0 ** -24
@@ -62,7 +74,7 @@ def normal(seed, sample_id, step, n):
     rad = np.sqrt(-2.0 * np.log(u))
     ang = 2.0 * np.pi * v
     z = np.stack([rad * np.cos(ang), rad * np.sin(ang)], axis=-1)     # [nq, 2, 2] -> z0 z1 z2 z3
-    return z.reshape(-1)[:n].astype(np.float32)
+    return z.reshape(-1)[:n]
 
 
 def sample_keys(seed, first, count):

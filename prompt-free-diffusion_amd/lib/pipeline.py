@@ -192,16 +192,18 @@ class PromptFreePipeline:
             sampler = DDIMSampler(net)
         self.sampler = sampler
         self.rank, self.world_size = rank, world_size
-        self._ctx_stage = self._vae_stage = self._stages = None
+        self._ctx_stage = self._vae_stage = self._enc_stage = self._stages = None
+        self._acp_host = None
 
     def enable_graph(self, on=True):
-        """hipGraph replay for all three stages: the DDIM loop (DDIMSampler.enable_graph) and, here, the
-        context encode and the VAE decode"""
+        """hipGraph replay for every stage: the DDIM loop (DDIMSampler.enable_graph) and, here, the context encode, the
+        VAE decode and the VAE encode of an img2img start"""
         self.sampler.enable_graph(on)
         if on and self._stages is None:
             self._stages = (_GraphedStage(self.net, 'ctx_encode', 'image', self.net.ctx['image']),
-                            _GraphedStage(self.net, 'vae_decode', 'image', self.net.vae['image']))
-        self._ctx_stage, self._vae_stage = self._stages if on else (None, None)
+                            _GraphedStage(self.net, 'vae_decode', 'image', self.net.vae['image']),
+                            _GraphedStage(self.net, 'vae_encode_moments', 'image', self.net.vae['image']))
+        self._ctx_stage, self._vae_stage, self._enc_stage = self._stages if on else (None, None, None)
 
     @serialised
     @torch.no_grad()
@@ -246,11 +248,43 @@ class PromptFreePipeline:
         return self.net.ctl.preprocess(control.to(dev), type=preprocess, low_threshold=low, high_threshold=high,
                                        size=[height, width]).to(dtype)
 
+    def _level(self, steps, k):
+        """a_t of an img2img start that runs k of `steps` steps: alphas_cumprod at ddim_timesteps[k - 1], the first
+        timestep the loop evaluates (lib/img2img.py) -- the number DDIMSampler.make_schedule puts in ddim_alphas[k - 1]"""
+        from .img2img import level
+        from .model_zoo.diffusion_utils import make_ddim_timesteps
+        acp = self.net.alphas_cumprod
+        if self._acp_host is None or self._acp_host[0] is not acp:
+            self._acp_host = (acp, acp.detach().float().cpu().numpy())     # one copy per schedule tensor, not per request
+        ts = make_ddim_timesteps("uniform", steps, self.net.num_timesteps, verbose=False)
+        return level(self._acp_host[1], ts, k)
+
+    @serialised
+    @torch.no_grad()
+    def init_latent(self, init, height, width, steps, strength, keys, posterior='sample'):
+        """the seeded start of an img2img request -> (x_t fp32 [n, 4, height/8, width/8] on the device, k): the latent of
+        `init` -- a uint8 HWC picture of any size, resized to (height, width) on the device straight into the f16 NHWC
+        the encoder reads, or a float tensor [1, 3, height, width] in [0, 1] -- sampled from the VAE posterior (or its
+        mode), scaled and noised to the level of the first of the k = start_steps(steps, strength) steps the request
+        runs, in one launch behind the encoder (ops.latent_start).  keys: int64 [n, 2] rows (seed, sample_id): sample i's
+        start is a function of the picture and keys[i] alone (lib/img2img.py); the picture is encoded once."""
+        k = image_io.check_img2img(init, height, width, steps, strength, posterior)
+        dev = self.net.device
+        if image_io.wants_ingest(init):
+            pic = ops.image_from_u8(image_io.to_device_u8(init, dev, 'init'), (int(height), int(width)), layout='nhwc')
+        else:
+            pic = init.to(dev)
+        moments = self._enc_stage(pic) if self._enc_stage is not None else self.net.vae_encode_moments(pic, 'image')
+        sf = (getattr(self.net, 'latent_scale_factor', None) or {}).get('image', None)
+        x_t = ops.latent_start(moments, keys.to(dev), 1.0 if sf is None else sf, self._level(steps, k), posterior=posterior)
+        return x_t, k
+
     @serialised
     @torch.no_grad()
     def generate(self, image, n_global, height, width, steps=50, scale=2.0, eta=0.0, seed=20, control=None,
                  uncond=None, decode=True, gather=False, verbose=False, timings=None, as_uint8=False,
-                 device_noise=False, solver='ddim', control_preprocess=None, control_thresholds=(100, 200)):
+                 device_noise=False, solver='ddim', control_preprocess=None, control_thresholds=(100, 200), init=None,
+                 strength=0.75, init_posterior='sample'):
         """returns (images, latents [n_local,4,h,w]); images = [n_local | n_global (gather), 3, H, W] in [0,1]
         in the model dtype, or -- as_uint8 -- packed uint8 [n, H, W, 3] (the bytes ToPILImage would produce,
         app.py:273-275; 4x fewer bytes through the all-gather); decode=False returns the latents twice.
@@ -267,7 +301,13 @@ class PromptFreePipeline:
         typically 20 to 25 steps in place of 50) -- or 'dpmpp_1', its first-order form (DDIM at eta 0).  The last two are
         deterministic: eta = 0, no device_noise.
         control_preprocess: None -- the control picture is the hint -- or 'canny': the hint is the picture's Canny edges at
-        control_thresholds = (low, high), computed on the device (`control_hint`; app.py:246 with do_preprocess=True)."""
+        control_thresholds = (low, high), computed on the device (`control_hint`; app.py:246 with do_preprocess=True).
+        init: image-to-image -- a uint8 HWC picture of any size or a float [1,3,height,width] tensor in [0,1] shared by all
+        samples.  The trajectory starts from the picture's latent noised to the level of the first of the
+        k = min(steps, int(steps * strength)) steps it runs (`init_latent`) instead of from x_T: no x_T is drawn, sample j
+        of the GLOBAL batch draws its posterior and forward noise keyed (seed, j), so the result does not depend on the
+        world size.  strength in (0, 1]: 1 runs every step (the picture only shades the start), small values stay close
+        to the picture.  init_posterior: 'sample' or 'mode' (the posterior mean).  timings gains init_encode_ms."""
         from .model_zoo.ddim import is_per_sample
         from .solver import solver_order
         if solver_order(solver) is not None and (eta != 0. or device_noise):     # an unknown name raises here too
@@ -287,11 +327,15 @@ class PromptFreePipeline:
         if u8_control:
             image_io.check_resize(image_io.check_u8_picture(control, 'control')[:2], (height, width), 'control')
         image_io.check_control_preprocess(control, control_preprocess, control_thresholds)
+        if init is not None:         # strength first: checked before anything touches the device
+            image_io.check_img2img(init, height, width, steps, strength, init_posterior)
+            if n_global % P:
+                raise ValueError("global batch must divide over the ranks")
         mk = _Marks(torch.device(dev).type == 'cuda') if timings is not None else None
         if mk:
             mk.mark()
-        xT = shard_xT(n_global, height, width, seed, r, P)
-        n = xT.shape[0]
+        xT = shard_xT(n_global, height, width, seed, r, P) if init is None else None
+        n = xT.shape[0] if init is None else n_global // P
         if u8_image:
             image = self.ingest(image)
         if image.shape[0] > 1:
@@ -307,7 +351,16 @@ class PromptFreePipeline:
             uncond = zeros
         if mk:
             mk.mark()
-        x_info = {'type': 'image', 'xt': xT.to(dev)}
+        if init is None:
+            x_info = {'type': 'image', 'xt': xT.to(dev)}
+            shape = list(xT.shape)
+        else:
+            x_t, k = self.init_latent(init, height, width, steps, strength, shard_noise_keys(n_global, seed, r, P),
+                                      init_posterior)
+            x_info = {'type': 'image', 'xt': x_t, 'xt_steps': k}
+            shape = list(x_t.shape)
+            if mk:
+                mk.mark()
         if device_noise:
             x_info['noise_key'] = shard_noise_keys(n_global, seed, r, P).to(dev)
         c_info = {'type': 'image', 'conditioning': cond, 'unconditional_conditioning': uncond,
@@ -315,7 +368,7 @@ class PromptFreePipeline:
         if control is not None:
             c_info['control'] = self.control_hint(control, height, width, control_preprocess, control_thresholds)
         how = {} if solver == 'ddim' else {'solver': solver}     # the default call is what it was
-        x, _ = self.sampler.sample(steps=steps, shape=list(xT.shape), x_info=x_info, c_info=c_info, eta=eta,
+        x, _ = self.sampler.sample(steps=steps, shape=shape, x_info=x_info, c_info=c_info, eta=eta,
                                    verbose=verbose, **how)
         if mk:
             mk.mark()
@@ -329,7 +382,10 @@ class PromptFreePipeline:
             mk.mark()
             if mk.on_gpu:
                 torch.cuda.synchronize()
-            timings.update(ctx_encode_ms=mk.ms(0, 1), ddim_loop_ms=mk.ms(1, 2), vae_decode_ms=mk.ms(2, 3))
+            o = 0 if init is None else 1      # the mark behind the init encode
+            timings.update(ctx_encode_ms=mk.ms(0, 1), ddim_loop_ms=mk.ms(1 + o, 2 + o), vae_decode_ms=mk.ms(2 + o, 3 + o))
+            if init is not None:
+                timings.update(init_encode_ms=mk.ms(1, 2))
         if gather:
             img = all_gather_batch(img, P)
         return img, x

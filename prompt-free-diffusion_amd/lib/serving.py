@@ -33,7 +33,8 @@ from .solver import solver_order
 
 class _Request:
     __slots__ = ("image", "n", "height", "width", "steps", "scale", "eta", "seed", "control", "uncond", "as_uint8",
-                 "device_noise", "future", "mixed", "solver", "control_preprocess", "control_thresholds")
+                 "device_noise", "future", "mixed", "solver", "control_preprocess", "control_thresholds", "init", "strength",
+                 "init_k")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -42,6 +43,8 @@ class _Request:
     def key(self):
         """requests with equal keys can share one DDIM batch (mixed: any two scales other than 1 can)"""
         how = () if self.solver in (None, 'ddim') else (self.solver,)     # a batch runs ONE solver; the DDIM keys are unchanged
+        if self.init is not None:     # img2img: a batch runs ONE number of steps; every other key is unchanged
+            how = how + (('init', int(self.init_k)),)
         if self.mixed:
             return (self.height, self.width, self.steps, float(self.scale) == 1.0, float(self.eta),
                     self.control is None, self.uncond is None, bool(self.as_uint8), bool(self.device_noise)) + how
@@ -75,7 +78,7 @@ class PromptFreeServer:
     # ---- client side (any thread) -------------------------------------------------------------------
     def submit(self, image, n_samples=1, height=512, width=512, steps=50, scale=2.0, eta=0.0, seed=20,
                control=None, uncond=None, as_uint8=True, device_noise=False, solver='ddim', control_preprocess=None,
-               control_thresholds=(100, 200)):
+               control_thresholds=(100, 200), init=None, strength=0.75):
         """image [1,3,h,w] in [0,1] (any size); control [1,3,H,W] or None; uncond [1,148,768] or None (zeros).
         image and control may each be a uint8 HWC picture [h,w,3] (torch or numpy, any size; the reference picture
         at least 32 a side) instead: the request carries the bytes and the worker converts them on the device
@@ -88,6 +91,10 @@ class PromptFreeServer:
         control_preprocess: None, or 'canny': the worker turns the control picture into its Canny edge hint at
         control_thresholds = (low, high) on the device (PromptFreePipeline.control_hint).  A preprocessed control is a
         control: the batch key does not change.
+        init: image-to-image (PromptFreePipeline.init_latent) -- a uint8 HWC picture of any size or a float
+        [1,3,height,width] tensor: the request starts from that picture's latent, noised for the
+        k = min(steps, int(steps * strength)) steps it runs, sample j keyed (seed, j).  Such requests share a batch with
+        each other when k (and the rest of the key) is equal, each with its own picture and keys.
         -> Future of uint8 [n,H,W,3] (as_uint8) or float [n,3,H,W] images"""
         if self._stop:
             raise RuntimeError("server is closed")
@@ -115,7 +122,9 @@ class PromptFreeServer:
                                           tuple(control.shape) == (1, 3, int(height), int(width))):
             raise ValueError(f"control must be a float tensor [1, 3, {height}, {width}] or a uint8 picture [h, w, 3]")
         thresholds = image_io.check_control_preprocess(control, control_preprocess, control_thresholds)
-        r = _Request(image=image, n=int(n_samples), height=int(height), width=int(width), steps=int(steps),
+        init_k = None if init is None else image_io.check_img2img(init, int(height), int(width), int(steps), strength)
+        r = _Request(image=image, n=int(n_samples), height=int(height), width=int(width), steps=int(steps), init=init,
+                     strength=strength, init_k=init_k,
                      scale=scale, eta=eta, seed=int(seed), control=control, uncond=uncond, as_uint8=as_uint8,
                      device_noise=bool(device_noise), future=Future(), mixed=self.mixed_batches or None, solver=solver,
                      control_preprocess=control_preprocess, control_thresholds=thresholds)
@@ -223,8 +232,11 @@ class PromptFreeServer:
                 c, z = self.pipe.encode_reference(img, r.n)
                 conds.append(c)
                 unconds.append(z if r.uncond is None else r.uncond.to(dev).to(c.dtype).expand(r.n, -1, -1))
-                xts.append(shard_xT(r.n, r.height, r.width, r.seed, 0, 1))      # each request keeps ITS x_T stream
-                keys.append(shard_noise_keys(r.n, r.seed, 0, 1))                # ... and ITS noise keys (seed, j)
+                keys.append(shard_noise_keys(r.n, r.seed, 0, 1))                # each request keeps ITS noise keys (seed, j)
+                if r.init is None:
+                    xts.append(shard_xT(r.n, r.height, r.width, r.seed, 0, 1))  # ... and ITS x_T stream
+                else:                                                           # ... or ITS picture, noised under ITS keys
+                    xts.append(self.pipe.init_latent(r.init, r.height, r.width, r.steps, r.strength, keys[-1])[0])
             cond, uncond, xT = torch.cat(conds), torch.cat(unconds), torch.cat(xts).to(dev)
             c_info = {'type': 'image', 'conditioning': cond, 'unconditional_conditioning': uncond,
                       'unconditional_guidance_scale': r0.scale}
@@ -240,6 +252,8 @@ class PromptFreeServer:
             elif r0.control is not None:
                 c_info['control'] = self._hint(r0)
             x_info = {'type': 'image', 'xt': xT}
+            if r0.init is not None:
+                x_info['xt_steps'] = r0.init_k       # equal over the batch: part of the key
             if r0.device_noise:
                 x_info['noise_key'] = torch.cat(keys).to(dev)
             how = {} if r0.solver in (None, 'ddim') else {'solver': r0.solver}

@@ -43,6 +43,8 @@ struct float2 { float x, y; };
 static inline uint2 make_uint2(unsigned a, unsigned b) { return uint2{a, b}; }
 static inline uint4 make_uint4(unsigned a, unsigned b, unsigned c, unsigned d) { return uint4{a, b, c, d}; }
 static inline float2 make_float2(float a, float b) { return float2{a, b}; }
+struct alignas(16) float4 { float x, y, z, w; };
+static inline float4 make_float4(float a, float b, float c, float d) { return float4{a, b, c, d}; }
 typedef void* hipStream_t;
 typedef int hipError_t;
 
@@ -169,6 +171,11 @@ static inline long min(long a, int b) { return a < b ? a : (long)b; }
 static inline long max(long a, int b) { return a > b ? a : (long)b; }
 static inline float rsqrtf(float x) { return 1.0f / sqrtf(x); }
 #define __expf(x) expf(x)   /* glibc declares (but does not export) __expf */
+// sin(pi x) / cos(pi x) (csrc/philox.h): in libm only since glibc 2.41; through double they are within an fp32 ulp
+static inline float emu_sinpif(float x) { return (float)sin(3.14159265358979323846 * (double)x); }
+static inline float emu_cospif(float x) { return (float)cos(3.14159265358979323846 * (double)x); }
+#define sinpif(x) emu_sinpif(x)
+#define cospif(x) emu_cospif(x)
 
 template <class T> static inline T __shfl(T v, int src, int = 64) { return emu::exchange(v, src); }
 template <class T> static inline T __shfl_xor(T v, int mask, int = 64) { return emu::exchange(v, emu::lane() ^ mask); }
