@@ -1602,48 +1602,126 @@ __global__ __launch_bounds__(768) void conv3x3_patch_ws_kernel(const G160Params 
       rbase[i] = ty * PW + tx + l15;
     }
     const int sw = (l15 >> 1) & 7;
+    // both 32-wide halves (ks) of a 64-channel block sit in one LDS row; the chunk of ks = 1 is the chunk of ks = 0 with
+    // bit 2 flipped under either swizzle -- ((4 + g) ^ sw) == (g ^ sw) ^ 4 and ((4 + g + x) & 7) == ((g + x) & 7) ^ 4 --
+    // so its byte offset is the ks = 0 offset XOR 64
     const int boff0 = wn * 80 * ROWB + l15 * ROWB + (((0 + g) ^ sw) << 4);
-    const int boff1 = wn * 80 * ROWB + l15 * ROWB + (((4 + g) ^ sw) << 4);
     float4_t acc[WMB][5];
 #pragma unroll
     for (int i = 0; i < WMB; ++i)
 #pragma unroll
       for (int j = 0; j < 5; ++j) acc[i][j] = (float4_t){0.f, 0.f, 0.f, 0.f};
-    auto a_off = [&](int i, int toff, int ks) -> int {   // byte offset of A fragment i in the patch (rotation swizzle)
+    auto a_off = [&](int i, int toff) -> int {   // byte offset of A fragment i, ks = 0, in the patch (rotation swizzle)
       const int r = rbase[i] + toff;
-      return r * ROWB + ((((ks * 4 + g) + (r & ~1)) & 7) << 4);
+      return r * ROWB + (((g + (r & ~1)) & 7) << 4);
     };
     {
+      // Fragment pipeline.  A tap is two half steps (ks) of 5 columns x 4 MFMAs.  The reads of a half
+      // step are issued one half step ahead of the MFMAs that use them, into a second set of A registers (a0: ks = 0,
+      // a1: ks = 1) and into the B register of a column whose four MFMAs were just issued; sched_barrier fences pin that
+      // order (the compiler otherwise sinks every read next to its use).  Per tap and wave: 18 ds_read_b128, 40 MFMAs.
+      // Which reads cross which barrier:
+      //  * A, ks = 0, of taps 1..8 of a channel block is read during half step 1 of the tap before, that is BEFORE
+      //    barrier (A) of its own tap.  The patch of a block is complete at barrier (A) of the block's tap 0 -- every
+      //    loader form waits for all of its pieces (or ds_writes) there -- and read-only for the nine taps.
+      //  * No other read crosses a barrier.  The weights of tap t + 1 may be in flight until barrier (A) of t + 1: all
+      //    B reads of a tap follow its barrier.  A of tap 0 follows its barrier too: with the 3-stage ring, pieces of
+      //    that patch issued at tap 6 of the block before may still be outstanding at barrier (A) of its tap 8.
+      // The early read cannot hit a buffer the loaders are writing: during block ci they fill buffer (ci & 1) ^ 1, and
+      // buffer ci & 1 is rewritten only after barrier (A) of block ci + 1's tap 0.  Tap 8 prefetches nothing, and its
+      // last reads of the buffer (A, ks = 1) are consumed by MFMAs of tap 8, so nothing is outstanding at that barrier.
+      // For the same reason a split-K slice with ncbs == 0 (no loop) or ncbs == 1 (no second block) has no early read
+      // that leaves its one patch.  Every accumulator still sums ks, taps and channel blocks in the order of the 8-wave
+      // form (conv3x3_patch_kernel), so the bits are the same.
       int stage = 0;
+      half8_t a0[WMB], a1[WMB], bf[5];
+      int ao[WMB];
+      auto fence = [] { __builtin_amdgcn_sched_barrier(0); };
+      auto tap_step = [&](auto prefetch, const char* patch, const char* wt, int ntoff) {
+        auto lda = [&](int off) { return *reinterpret_cast<const half8_t*>(patch + off); };
+        auto ldb = [&](int j, int ks) { return *reinterpret_cast<const half8_t*>(wt + (boff0 ^ (ks << 6)) + j * 16 * ROWB); };
+        auto col = [&](const half8_t(&af)[WMB], int j) {
+#pragma unroll
+          for (int i = 0; i < WMB; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j], af[i], acc[i][j], 0, 0, 0);
+        };
+        // column 1 first: LDS data returns in order, so the one wait in front of column 0 covers both and every later
+        // wait is for a read issued eight or more MFMAs earlier
+        bf[1] = ldb(1, 0);
+        bf[0] = ldb(0, 0);
+        bf[2] = ldb(2, 0);
+        bf[3] = ldb(3, 0);
+        bf[4] = ldb(4, 0);
+        fence();
+        col(a0, 0);
+        fence();
+        a1[0] = lda(ao[0] ^ 64);
+        a1[1] = lda(ao[1] ^ 64);
+        bf[0] = ldb(0, 1);
+        fence();
+        col(a0, 1);
+        fence();
+        a1[2] = lda(ao[2] ^ 64);
+        a1[3] = lda(ao[3] ^ 64);
+        bf[1] = ldb(1, 1);
+        fence();
+        col(a0, 2);
+        fence();
+        bf[2] = ldb(2, 1);
+        fence();
+        col(a0, 3);
+        fence();
+        bf[3] = ldb(3, 1);
+        fence();
+        col(a0, 4);
+        if constexpr (decltype(prefetch)::value) {   // the offsets of the next tap, under the MFMAs
+#pragma unroll
+          for (int i = 0; i < WMB; ++i) ao[i] = a_off(i, ntoff);
+        }
+        fence();
+        bf[4] = ldb(4, 1);
+        fence();
+        col(a1, 0);
+        fence();
+        if constexpr (decltype(prefetch)::value) {
+          a0[0] = lda(ao[0]);
+          a0[1] = lda(ao[1]);
+          fence();
+        }
+        col(a1, 1);
+        fence();
+        if constexpr (decltype(prefetch)::value) {
+          a0[2] = lda(ao[2]);
+          a0[3] = lda(ao[3]);
+          fence();
+        }
+        col(a1, 2);
+        col(a1, 3);
+        col(a1, 4);
+      };
+      auto next_stage = [&]() {
+        if constexpr (NWS == 2) stage ^= 1;
+        else if (++stage == NWS) stage = 0;
+      };
       for (int ci = 0; ci < ncbs; ++ci) {
         const char* patch = smem + (ci & 1) * PATCH_BYTES;
-        int toff = 0;
-#pragma nounroll
-        for (int ky = 0; ky < 3; ++ky) {
-#pragma nounroll
-          for (int kx = 0; kx < 3; ++kx) {
-            block_barrier();                    // (A)
-            const char* wt = smem + OFF_W + stage * WT_BYTES;
+        int toff = 0, kx = 0;
+        block_barrier();                        // (A) of tap 0: this block's patch is complete
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-              half8_t af[WMB], bf[5];
-#pragma unroll
-              for (int i = 0; i < WMB; ++i) af[i] = *reinterpret_cast<const half8_t*>(patch + a_off(i, toff, ks));
-              const int bo = ks ? boff1 : boff0;
-#pragma unroll
-              for (int j = 0; j < 5; ++j) bf[j] = *reinterpret_cast<const half8_t*>(wt + bo + j * 16 * ROWB);
-#pragma unroll
-              for (int i = 0; i < WMB; ++i)
-#pragma unroll
-                for (int j = 0; j < 5; ++j)
-                  acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j], af[i], acc[i][j], 0, 0, 0);
-            }
-            if constexpr (NWS == 2) stage ^= 1;
-            else if (++stage == NWS) stage = 0;
-            toff += 1;
-          }
-          toff += PW - 3;
+        for (int i = 0; i < WMB; ++i) {
+          ao[i] = a_off(i, 0);
+          a0[i] = *reinterpret_cast<const half8_t*>(patch + ao[i]);
         }
+#pragma nounroll
+        for (int tap = 0; tap < 8; ++tap) {
+          const int ntoff = toff + (kx == 2 ? PW - 2 : 1);   // ky * PW + kx of the next tap
+          kx = kx == 2 ? 0 : kx + 1;
+          tap_step(std::true_type{}, patch, smem + OFF_W + stage * WT_BYTES, ntoff);
+          toff = ntoff;
+          next_stage();
+          block_barrier();                      // (A) of taps 1..8; A, ks = 0, of that tap is already on its way
+        }
+        tap_step(std::false_type{}, patch, smem + OFF_W + stage * WT_BYTES, 0);
+        next_stage();
       }
       block_barrier();                          // (B)
     }

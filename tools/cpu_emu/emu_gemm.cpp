@@ -55,6 +55,7 @@ struct Case {
   int gnf = 0;             // 1 / 2: GroupNorm(+SiLU) fused into the split-K reduction (PfdGemmDesc.gnf_y), raw tensor skipped / kept
   int res_rows = 0;        // > 0: the residual holds that many rows, read with one wrap (PfdGemmDesc.res_rows)
   bool declined = false;   // the library must not serve the request: return value 1, nothing written
+  int gn_pro = 0;          // 1 / 2: GroupNorm affine map (+ SiLU) in the staging path of the patch kernel (PfdGemmDesc.gn_table)
 };
 
 // PfdGemmDesc.ups = 2: the 3x3 weight [N][9 Cin] folded (fp32, rounded once) into four 2x2-tap phase blocks [py][px][N][4 Cin]:
@@ -83,7 +84,7 @@ static std::vector<_Float16> fold_phase_weight(const std::vector<_Float16>& Wt, 
 static int run_variant(const Case& c, int variant, const std::vector<h16>& A, const std::vector<h16>& A2, const std::vector<h16>& Wt,
                        const std::vector<h16>& bias, const std::vector<h16>& rv, const std::vector<h16>& R, int M, int K, int Ho, int Wo,
                        std::vector<h16>& C, std::vector<float>& ws, std::vector<float>* gn = nullptr, std::vector<h16>* gnf_y = nullptr,
-                       const std::vector<h16>* gnf_gb = nullptr, int gnf_skip_raw = 0) {
+                       const std::vector<h16>* gnf_gb = nullptr, int gnf_skip_raw = 0, const std::vector<float>* gn_table = nullptr) {
   const bool conv = c.ksize > 0;
   PfdGemmDesc d;
   memset(&d, 0, sizeof(d));
@@ -119,6 +120,7 @@ static int run_variant(const Case& c, int variant, const std::vector<h16>& A, co
     d.gnf_gamma = gnf_gb->data(); d.gnf_beta = gnf_gb->data() + c.N; d.gnf_y = gnf_y->data(); d.gnf_ldy = c.N; d.gnf_eps = 1e-5f;
     d.gnf_act = PFD_ACT_SILU; d.gnf_rows = conv ? Ho * Wo : M; d.gnf_skip_raw = gnf_skip_raw;
   }
+  if (gn_table) { d.gn_table = gn_table->data(); d.gn_c1 = c.Cin; d.gn_act = c.gn_pro == 2 ? PFD_ACT_SILU : PFD_ACT_NONE; }
   return pfd_gemm160_try(&d, variant, c.splits, nullptr);
 }
 
@@ -152,7 +154,26 @@ static int run_case(const Case& c) {
   std::vector<float> ws((size_t)8 * M * N + 64);
   g_err.clear();
   std::vector<float> gn1((size_t)(M / 64 + 1) * (N / 160) * 32, -1.f), gn2 = gn1;
-  const int rc = run_variant(c, c.variant, A1, A2, Wt, bias, rv, R, M, K, Ho, Wo, C, ws, c.gn_stats ? &gn1 : nullptr);
+  // GroupNorm prologue: a per-sample {scale[Cin], shift[Cin]} table; the operand of the contraction is the f16 rounding of
+  // act(x * scale + shift), and the zero padding pads THAT image
+  std::vector<float> table;
+  std::vector<h16> Apro;
+  if (c.gn_pro) {
+    std::uniform_real_distribution<float> d(-1.f, 1.f);
+    table.resize((size_t)c.B * 2 * c.Cin);
+    for (int b = 0; b < c.B; ++b)
+      for (int ch = 0; ch < c.Cin; ++ch) { table[((size_t)b * 2) * c.Cin + ch] = 1.f + 0.3f * d(rng); table[((size_t)b * 2 + 1) * c.Cin + ch] = 0.4f * d(rng); }
+    Apro.resize(Afull.size());
+    for (size_t i = 0; i < Afull.size(); ++i) {
+      const int ch = (int)(i % c.Cin), b = (int)(i / ((size_t)c.H * c.W * c.Cin));
+      double v = (double)Afull[i] * (double)table[((size_t)b * 2) * c.Cin + ch] + (double)table[((size_t)b * 2 + 1) * c.Cin + ch];
+      if (c.gn_pro == 2) v = v / (1.0 + exp(-v));
+      Apro[i] = (h16)v;
+    }
+  }
+  const std::vector<h16>& Aref = c.gn_pro ? Apro : Afull;
+  const int rc = run_variant(c, c.variant, A1, A2, Wt, bias, rv, R, M, K, Ho, Wo, C, ws, c.gn_stats ? &gn1 : nullptr, nullptr, nullptr, 0,
+                             c.gn_pro ? &table : nullptr);
   if (c.declined) {
     size_t touched = 0;
     for (const auto& v : C) touched += (float)v != -77.f;
@@ -177,7 +198,7 @@ static int run_case(const Case& c) {
             int iy = oy * c.stride + ky - c.pad, ix = ox * c.stride + kx - c.pad;
             if (iy < 0 || iy >= Hin || ix < 0 || ix >= Win) continue;
             if (c.ups) { iy /= 2; ix /= 2; }
-            const h16* ap = &Afull[(((size_t)b * c.H + iy) * c.W + ix) * c.Cin];
+            const h16* ap = &Aref[(((size_t)b * c.H + iy) * c.W + ix) * c.Cin];
             const h16* wp = &Wt[(size_t)n * K + (ky * c.ksize + kx) * c.Cin];
             for (int ci = 0; ci < c.Cin; ++ci) s += (double)ap[ci] * (double)wp[ci];
           }
@@ -196,7 +217,8 @@ static int run_case(const Case& c) {
   std::string extra;
   if (ok && c.base_variant >= 0) {
     std::vector<h16> C2((size_t)M * N, (h16)-55.f);
-    const int rc2 = run_variant(c, c.base_variant, A1, A2, Wt, bias, rv, R, M, K, Ho, Wo, C2, ws);
+    const int rc2 = run_variant(c, c.base_variant, A1, A2, Wt, bias, rv, R, M, K, Ho, Wo, C2, ws, nullptr, nullptr, nullptr, 0,
+                                c.gn_pro ? &table : nullptr);
     size_t nd = 0;
     for (size_t i = 0; i < C.size(); ++i) nd += memcmp(&C[i], &C2[i], sizeof(h16)) != 0;
     if (rc2 != 0 || nd) { fails = 1; extra = " | vs variant " + std::to_string(c.base_variant) + ": rc " + std::to_string(rc2) + ", " + std::to_string(nd) + " elements differ"; }
@@ -521,6 +543,16 @@ int main(int argc, char** argv) {
   conv("phase-fold: upsample conv 16x16x64 -> 128 (128-wide tile)", 128, 0, 0, 3, 1, 1, 2, 1, 16, 16, 64, false, -1);
   { auto c = conv("phase-fold: upsample conv 16x16x128 -> 160, K-tile-contiguous phase blocks", 160, 0, 0, 3, 1, 1, 2, 1, 16, 16, 128, false, -1); c->w_tiled = true; }
   { auto c = conv("phase-fold: upsample conv 8x8x64 -> 160 is declined (a tile would straddle two phases)", 160, 0, 0, 3, 1, 1, 2, 1, 8, 8, 64, false, -1); c->declined = true; }
+  // the fragment pipeline of the loader-wave patch kernel: A fragments read one half step ahead, those of
+  // taps 1..8 before the tap's barrier.  (The emulation checks the index arithmetic and the order of the sums -- same bits as
+  // the 8-wave kernel, whose loop reads every fragment behind the barrier -- not the hazard: a copy lands when it is issued.)
+  // Three channel blocks: both buffer hand-overs and one buffer reuse.
+  conv("fragment pipeline: 3-stage ring form, 16x16x192 -> 160, three channel blocks", 160, 96, 1, 3, 1, 1, 0, 1, 16, 16, 192, true, 99);
+  conv("fragment pipeline: two-stage form, 16x16x192 -> 160, three channel blocks", 160, 98, 1, 3, 1, 1, 0, 1, 16, 16, 192, true, 99);
+  // split-K 3 over five channel blocks: slices [0, 2), [2, 4), [4, 5) -- the last has one block and no early read
+  conv("fragment pipeline: 3-stage ring form, split-K 3 over 16x16x320 -> 160", 160, 96, 3, 3, 1, 1, 0, 1, 16, 16, 320, true, 99);
+  conv("fragment pipeline: two-stage form, split-K 3 over 16x16x320 -> 160", 160, 98, 3, 3, 1, 1, 0, 1, 16, 16, 320, true, 99);
+  { auto c = conv("fragment pipeline: GroupNorm + SiLU prologue form, 16x16x128 -> 160", 160, 98, 1, 3, 1, 1, 0, 1, 16, 16, 128, true, 0); c->gn_pro = 2; }
   int fails = 0, n = 0;
   for (const auto& c : cases) {
     if (argc > 1) {

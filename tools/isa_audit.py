@@ -90,7 +90,113 @@ def findings(files=None):
     return bad, rows
 
 
+# ---- the fragment pipeline of the wave-specialised patch kernel ----
+PATCH_WS = {"<2>": "conv3x3_patch_ws_kernelILi2ELi2EE", "<1>": "conv3x3_patch_ws_kernelILi1ELi2EE",
+            "<0,3>": "conv3x3_patch_ws_kernelILi0ELi3EE", "<0,2>": "conv3x3_patch_ws_kernelILi0ELi2EE"}
+
+
+def kernel_text(asm_path, name_part):
+    """-> (instruction lines of the one kernel whose mangled name contains name_part, its .amdhsa_* directives as a dict)"""
+    body, meta, name, state = [], {}, None, 0
+    for line in open(asm_path):
+        m = re.match(r"^(_Z[A-Za-z0-9_]+):", line)
+        if m and state == 0 and name_part in m.group(1):
+            name, state = m.group(1), 1
+            continue
+        t = line.strip()
+        if state == 1:
+            if t.startswith(".amdhsa_kernel") and name in t:
+                state = 3
+            elif t.startswith(".section") or t.startswith(".Lfunc_end"):
+                state = 2
+            elif t and not t.startswith(";") and not t.startswith(".") or re.match(r"^\.LBB\d+_\d+:", t):
+                body.append(t.split(";")[0].strip())
+        elif state == 2 and t.startswith(".amdhsa_kernel") and name in t:
+            state = 3
+        elif state == 3:
+            m = re.match(r"^\.amdhsa_(\w+)\s+(\S+)", t)
+            if m:
+                meta[m.group(1)] = m.group(2)
+            if t.startswith(".end_amdhsa_kernel"):
+                break
+    if name is None:
+        raise KeyError(name_part)
+    return body, meta
+
+
+def mfma_loops(body):
+    """backward-branch spans [label index, branch index] that hold MFMAs, innermost (shortest) first"""
+    labels = {t[:-1]: i for i, t in enumerate(body) if t.endswith(":")}
+    spans = []
+    for i, t in enumerate(body):
+        m = re.match(r"s_cbranch_\w+\s+(\S+)", t) or re.match(r"s_branch\s+(\S+)", t)
+        if m and labels.get(m.group(1), i) < i and any(x.startswith("v_mfma") for x in body[labels[m.group(1)]:i]):
+            spans.append((labels[m.group(1)], i))
+    return sorted(spans, key=lambda s: s[1] - s[0])
+
+
+def wait_distances(seq):
+    """Walk an instruction sequence: LDS reads return in order, so `s_waitcnt lgkmcnt(n)` retires all but the newest n.
+    -> [(position, n, MFMAs issued since the newest read this wait retires (None: retires nothing), first wait after s_barrier)]"""
+    fifo, mfmas, out, after_barrier = [], 0, [], False
+    for pos, t in enumerate(seq):
+        if t.startswith("ds_read") or t.startswith("ds_load"):
+            fifo.append(mfmas)
+        elif re.match(r"(ds_|s_load|s_buffer_load|flat_)", t):
+            fifo.append(mfmas)                       # any other LGKM operation counts like a read
+        elif t.startswith("v_mfma"):
+            mfmas += 1
+        elif t.startswith("s_barrier"):
+            after_barrier = True
+        elif t.startswith("s_waitcnt"):
+            m = re.search(r"lgkmcnt\((\d+)\)", t)
+            if not m:
+                continue
+            n, newest = int(m.group(1)), None
+            while len(fifo) > n:
+                newest = fifo.pop(0)
+            out.append((pos, n, None if newest is None else mfmas - newest, after_barrier))
+            after_barrier = False
+    return out
+
+
+def patch_pipeline_report(asm_path, name_part):
+    """The consumer tap loop of one patch-kernel instantiation: resources, reads / MFMAs per loop body, and the distance
+    (in MFMAs) between each LDS wait and the newest read it waits for -- in the steady state of the loop (second of two
+    consecutive iterations) and along one pass of the enclosing channel-block loop (tap 0's reads, one loop body, tap 8)."""
+    body, meta = kernel_text(asm_path, name_part)
+    spans = [s for s in mfma_loops(body) if sum(x.startswith("v_mfma") for x in body[s[0]:s[1]]) >= 40]
+    lo, hi = spans[0]
+    outer = next(((a, b) for a, b in spans[1:] if a <= lo and b >= hi), None)
+    loop = body[lo:hi + 1]
+    rep = dict(vgprs=int(meta["next_free_vgpr"]), scratch=int(meta["private_segment_fixed_size"]),
+               lds=int(meta["group_segment_fixed_size"]),
+               reads=sum(t.startswith("ds_read_b128") for t in loop), other_lds=sum(t.startswith("ds_") and not t.startswith("ds_read_b128") for t in loop),
+               mfmas=sum(t.startswith("v_mfma") for t in loop), barriers=sum(t.startswith("s_barrier") for t in loop),
+               valu=sum(bool(re.match(r"v_(?!mfma)", t)) for t in loop))
+    steady = [w for w in wait_distances(loop + loop) if w[0] >= len(loop)]
+    rep["steady"] = [(n, d, first) for _, n, d, first in steady]
+    rep["block"] = [(n, d, first) for _, n, d, first in wait_distances(body[outer[0]:outer[1] + 1])] if outer else []
+    return rep
+
+
+def patch_pipeline_main():
+    asm = compile_asm(os.path.join(CSRC, "gemm_glds.hip"))
+    bad = 0
+    for inst, part in PATCH_WS.items():
+        r = patch_pipeline_report(asm, part)
+        print(f"conv3x3_patch_ws_kernel{inst}: vgprs {r['vgprs']} scratch {r['scratch']} lds {r['lds']} | tap loop: {r['reads']} ds_read_b128, "
+              f"{r['mfmas']} MFMAs, {r['valu']} VALU, {r['barriers']} barrier")
+        for what in ("steady", "block"):
+            txt = " ".join(f"lgkmcnt({n}):{'-' if d is None else d}{'*' if first else ''}" for n, d, first in r[what])
+            print(f"  {what:6s} wait:MFMAs since the read (* first after s_barrier): {txt}")
+            bad += sum(1 for n, d, first in r[what] if d is not None and not first and d < 8)
+    return 1 if bad else 0
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["--patch-pipeline"]:
+        sys.exit(patch_pipeline_main())
     bad, rows = findings([os.path.abspath(a) for a in sys.argv[1:]] or None)
     for f, k, v in rows:
         print(f"{f:14s} {k[:84]:84s} loads={v['loads']:3d} serialised={v['serialised']:2d} "
