@@ -442,7 +442,7 @@ __global__ __launch_bounds__(NWAVES * 64, (D <= 40 ? 4 : 1)) void attention2_ker
             half4_t o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = (half_t)(o16[i][qt][e] * inv);
-            *reinterpret_cast<half4_t*>(op + d0) = o;
+            gst_t<PFD_ST_ATTN>(reinterpret_cast<half4_t*>(op + d0), o);
           }
         }
       }
@@ -467,7 +467,7 @@ __global__ __launch_bounds__(NWAVES * 64, (D <= 40 ? 4 : 1)) void attention2_ker
             half4_t o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = (half_t)(o32[i][rq * 4 + e] * inv);
-            *reinterpret_cast<half4_t*>(op + d0) = o;
+            gst_t<PFD_ST_ATTN>(reinterpret_cast<half4_t*>(op + d0), o);
           }
         }
     }

@@ -297,7 +297,7 @@ __global__ __launch_bounds__(256, 2) void attention3_kernel(const AttnParams p) 
             half4_t ov;
 #pragma unroll
             for (int e = 0; e < 4; ++e) ov[e] = (half_t)(o[i][qt][e] * inv);
-            *reinterpret_cast<half4_t*>(op + d0) = ov;
+            gst_t<PFD_ST_ATTN>(reinterpret_cast<half4_t*>(op + d0), ov);
           }
         }
       }

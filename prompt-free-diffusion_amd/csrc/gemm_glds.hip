@@ -157,28 +157,8 @@ __device__ __forceinline__ G160Params reload_params() {
   return q;
 }
 
-// Global-memory accesses of the epilogues, with the address space spelled out at the access: a pointer that came out of
-// reload_params() is generic to the compiler (flat_load / flat_store, which also tick lgkmcnt and order against the LDS reads of
-// the store pass); through these they are global_load / global_store whatever the pointer's provenance.
-template <int BYTES> struct GRaw;
-template <> struct GRaw<2>  { typedef unsigned short type; };
-template <> struct GRaw<8>  { typedef unsigned int type __attribute__((ext_vector_type(2))); };
-template <> struct GRaw<16> { typedef unsigned int type __attribute__((ext_vector_type(4))); };
-template <class T>
-__device__ __forceinline__ T gld(const void* ptr) {
-  typedef typename GRaw<sizeof(T)>::type V;
-  const V v = *reinterpret_cast<const __attribute__((address_space(1))) V*>((unsigned long)ptr);
-  T out;
-  __builtin_memcpy(&out, &v, sizeof(T));
-  return out;
-}
-template <class T>
-__device__ __forceinline__ void gst(void* ptr, T val) {
-  typedef typename GRaw<sizeof(T)>::type V;
-  V v;
-  __builtin_memcpy(&v, &val, sizeof(T));
-  *reinterpret_cast<__attribute__((address_space(1))) V*>((unsigned long)ptr) = v;
-}
+// Global-memory accesses of the epilogues go through gld / gst (pfd_common.h): a pointer that came out of reload_params() is
+// generic to the compiler, through them the access is global_load / global_store whatever the pointer's provenance.
 
 // output row (index into M) of row `row` of the tile that starts at m0 (see G160Params.pt_w)
 // PT = 0 (every kernel but the 3x3 patch kernels): rows are consecutive, the mapping folds away
@@ -238,6 +218,8 @@ __device__ __forceinline__ void lds_store16_opaque(void* lds_dst, uint4 v) {
 // every row 16-byte aligned for the ds_read_b128 of the store pass (cols = 160: 336 B = 84 dwords, row r
 // starts at bank 20 r mod 64; 128: 272 B -> 4 r; 80: 176 B -> 44 r mod 64; 64: 144 B -> 36 r mod 64).
 constexpr int stage_row_bytes(int cols) { return cols * 2 + 16; }
+// the transposed tail stores single halfs: never write-through (a 2-byte sc1 store is one fabric write each)
+constexpr int ST_OUT_NARROW = PFD_ST_OUT == ST_WT ? ST_PLAIN : PFD_ST_OUT;
 
 // pass 1 (the waves that hold accumulators): returns true when the tile was staged in LDS and needs pass 2
 // lnstat: per-row {rstd, -rstd * mean} of this block's rows in LDS (LayerNorm folded into the GEMM), or nullptr
@@ -303,7 +285,7 @@ __device__ __forceinline__ bool epilogue_stage(float4_t (&acc)[WMB][NT], const G
       for (int j = 0; j < NT; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r)   // 16 lanes = 16 consecutive m: 32-byte segments per output row
-          gst<half_t>(p.Ct + (long)(nw + j * 16 + r - p.n_split) * p.ldct + m, (half_t)(acc[i][j][r] + bv[j][r]));
+          gst<ST_OUT_NARROW>(p.Ct + (long)(nw + j * 16 + r - p.n_split) * p.ldct + m, (half_t)(acc[i][j][r] + bv[j][r]));
     }
     return false;
   }
@@ -429,7 +411,7 @@ constexpr int GN_SLAB = 64;
 
 // cs / cq: this lane's partial column sums of its chunk of ITS slab (wave w works on slab w / WPS, WPS = waves per slab,
 // so a lane carries 16 sums whatever the tile height).  red_base(s): scratch of slab s (>= (WPS + 1) * 1280 bytes).
-template <int NSLAB, int NTHREADS, class RedBase>
+template <int NSLAB, int NTHREADS, int GN_ST = ST_PLAIN, class RedBase>   // GN_ST: store policy of the caller's family
 __device__ __forceinline__ void gn_slab_reduce(float (&cs)[8], float (&cq)[8], int tid, int cpg, int slab0, int nslab_total,
                                                int tiles_n, int tile_n, float2* __restrict__ out, RedBase red_base) {
   constexpr int W = NTHREADS / 64, WPS = W / NSLAB;
@@ -469,7 +451,7 @@ __device__ __forceinline__ void gn_slab_reduce(float (&cs)[8], float (&cq)[8], i
       q += fin[(c >> 3) * 16 + 8 + (c & 7)];
     }
     if (slab0 + s < nslab_total)   // (a tile past M holds slabs that do not exist)
-      gst<float2>(out + ((long)(slab0 + s) * tiles_n + tile_n) * 16 + gl, make_float2(a, q));
+      gst<GN_ST>(out + ((long)(slab0 + s) * tiles_n + tile_n) * 16 + gl, make_float2(a, q));
   }
 }
 
@@ -513,7 +495,7 @@ __device__ __forceinline__ void epilogue_store_gn(const G160Params& p, int m0, i
 #pragma unroll
         for (int e = 0; e < 8; ++e) v.e[e] = (half_t)((float)v.e[e] + (float)r[u].e[e]);
       }
-      if (ok) gst<uint4>(p.C + (long)m * p.ldc + n0 + cc * 8, v.u);
+      if (ok) gst<PFD_ST_OUT>(p.C + (long)m * p.ldc + n0 + cc * 8, v.u);
       const float mk = ok ? 1.f : 0.f;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -523,7 +505,7 @@ __device__ __forceinline__ void epilogue_store_gn(const G160Params& p, int m0, i
       }
     }
   }
-  gn_slab_reduce<NSLAB, NTHREADS>(cs, cq, tid, p.N / 32, slab0, p.M / GN_SLAB, p.N / 160, n0 / 160, p.gn_out,
+  gn_slab_reduce<NSLAB, NTHREADS, PFD_ST_OUT>(cs, cq, tid, p.N / 32, slab0, p.M / GN_SLAB, p.N / 160, n0 / 160, p.gn_out,
                                   [&](int sl) { return reinterpret_cast<float*>(smem + sl * GN_SLAB * RS); });
 }
 
@@ -580,13 +562,13 @@ __device__ __forceinline__ void epilogue_store(const G160Params& p, int m0, int 
             sum += f;
             sq = fmaf(f, f, sq);
           }
-          if (ok) gst<uint4>(p.C + (long)m * p.ldc + n0 + (k + 4 * j) * 8, v.u);
+          if (ok) gst<PFD_ST_OUT>(p.C + (long)m * p.ldc + n0 + (k + 4 * j) * 8, v.u);
         }
         sum += __shfl_xor(sum, 1, 64);
         sq += __shfl_xor(sq, 1, 64);
         sum += __shfl_xor(sum, 2, 64);
         sq += __shfl_xor(sq, 2, 64);
-        if (ok && k == 0) gst<float2>(p.ln_out + (long)m * tiles_n + tile_n, make_float2(sum, sq));
+        if (ok && k == 0) gst<PFD_ST_OUT>(p.ln_out + (long)m * tiles_n + tile_n, make_float2(sum, sq));
       }
       return;
     }
@@ -624,7 +606,9 @@ __device__ __forceinline__ void epilogue_store(const G160Params& p, int m0, int 
 #pragma unroll
           for (int e = 0; e < 8; ++e) v.e[e] = (half_t)((float)v.e[e] + (float)r[u].e[e]);
         }
-        gst<uint4>(Cb + (long)m * ldc + nc0 + cc * 8, v.u);
+        if constexpr (PFD_ST_SLAB == PFD_ST_OUT) gst<PFD_ST_OUT>(Cb + (long)m * ldc + nc0 + cc * 8, v.u);
+        else if (slab) gst<PFD_ST_SLAB>(Cb + (long)m * ldc + nc0 + cc * 8, v.u);   // (block-uniform)
+        else gst<PFD_ST_OUT>(Cb + (long)m * ldc + nc0 + cc * 8, v.u);
       }
     }
   };
@@ -1798,7 +1782,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const G160Params p) 
       else if (p.act == PFD_ACT_SILU) x = pfd_silu(x);
       o.e[e] = (half_t)(x + (float)rr.e[e]);
     }
-    *reinterpret_cast<uint4*>(p.C + (long)m * p.ldc + n) = o.u;
+    gst_t<PFD_ST_REDUCE>(reinterpret_cast<uint4*>(p.C + (long)m * p.ldc + n), o.u);
   }
 }
 
@@ -1876,10 +1860,10 @@ __global__ __launch_bounds__(RGN_T) void splitk_reduce_gn_kernel(const G160Param
         cs[e] += f;
         cq[e] = fmaf(f, f, cq[e]);
       }
-      if (ok[u]) *reinterpret_cast<uint4*>(p.C + (long)m[u] * p.ldc + n) = o.u;
+      if (ok[u]) gst_t<PFD_ST_REDUCE>(reinterpret_cast<uint4*>(p.C + (long)m[u] * p.ldc + n), o.u);
     }
   }
-  gn_slab_reduce<1, RGN_T>(cs, cq, tid, p.N / 32, slab, p.M / GN_SLAB, tiles_n, tile_n, p.gn_out, [&](int) { return red; });
+  gn_slab_reduce<1, RGN_T, PFD_ST_REDUCE>(cs, cq, tid, p.N / 32, slab, p.M / GN_SLAB, tiles_n, tile_n, p.gn_out, [&](int) { return red; });
 }
 
 
@@ -1995,7 +1979,7 @@ __global__ __launch_bounds__(GNF_T) void splitk_reduce_gnorm_kernel(const G160Pa
         else if (p.act == PFD_ACT_SILU) x = pfd_silu(x);
         o.e[e] = (half_t)(x + (float)xq[u].e[e]);
       }
-      if (on[u] && !f.skip_raw) *reinterpret_cast<uint2*>(p.C + (m_b + ru[u]) * p.ldc + n_g + cu[u] * 4) = o.u;
+      if (on[u] && !f.skip_raw) gst_t<PFD_ST_REDUCE>(reinterpret_cast<uint2*>(p.C + (m_b + ru[u]) * p.ldc + n_g + cu[u] * 4), o.u);
       v[k0 + u] = on[u] ? o.u : make_uint2(0, 0);
     }
   }
@@ -2048,7 +2032,7 @@ __global__ __launch_bounds__(GNF_T) void splitk_reduce_gnorm_kernel(const G160Pa
         if (f.act == PFD_ACT_SILU) t = pfd_silu(t);
         o.e[e] = (half_t)t;
       }
-      *reinterpret_cast<uint2*>(yb + (long)r * f.ldy + ch * 4) = o.u;
+      gst_t<PFD_ST_REDUCE>(reinterpret_cast<uint2*>(yb + (long)r * f.ldy + ch * 4), o.u);
     }
     r += dr;
     ch += dc;

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnSrc s, const half_t* __
           if (act == PFD_ACT_SILU) t = pfd_silu(t);
           q.e[e] = (half_t)t;
         }
-        *reinterpret_cast<uint4*>(y + row * ldy + v * 8) = q.u;
+        gst_t<PFD_ST_NORM>(reinterpret_cast<uint4*>(y + row * ldy + v * 8), q.u);
       }
     }
   }
@@ -314,7 +314,7 @@ __global__ __launch_bounds__(256) void gn_apply_pstats_kernel(GnSrc s, GnPStats 
           if (act == PFD_ACT_SILU) t = pfd_silu(t);
           qv.e[e] = (half_t)t;
         }
-        *reinterpret_cast<uint4*>(y + row * ldy + v * 8) = qv.u;
+        gst_t<PFD_ST_NORM>(reinterpret_cast<uint4*>(y + row * ldy + v * 8), qv.u);
       }
     }
   }
@@ -439,7 +439,7 @@ __global__ __launch_bounds__(GNS_T) void gn_small_kernel(GnSrc s, const half_t* 
         if (act == PFD_ACT_SILU) t = pfd_silu(t);
         o.e[e] = (half_t)t;
       }
-      *reinterpret_cast<uint2*>(y + ((long)b * HW + r) * ldy + c) = o.u;
+      gst_t<PFD_ST_NORM>(reinterpret_cast<uint2*>(y + ((long)b * HW + r) * ldy + c), o.u);
     }
   }
 }
@@ -521,7 +521,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const half_t* __restrict
 #pragma unroll
       for (int e = 0; e < 8; ++e)
         o.e[e] = (half_t)((vals[k][e] - mean) * rstd * (float)g[k].e[e] + (float)bt[k].e[e]);
-      *reinterpret_cast<uint4*>(y + (long)row * ldy + v * 8) = o.u;
+      gst_t<PFD_ST_NORM>(reinterpret_cast<uint4*>(y + (long)row * ldy + v * 8), o.u);
     }
   }
 }
@@ -585,7 +585,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const half_t* __res
 #pragma unroll
         for (int e = 0; e < 8; ++e)
           o.e[e] = (half_t)(((float)p[r][k].e[e] - mean) * rstd * (float)g[k].e[e] + (float)bt[k].e[e]);
-        *reinterpret_cast<uint4*>(y + (long)(row0 + r) * ldy + v * 8) = o.u;
+        gst_t<PFD_ST_NORM>(reinterpret_cast<uint4*>(y + (long)(row0 + r) * ldy + v * 8), o.u);
       }
     }
   }

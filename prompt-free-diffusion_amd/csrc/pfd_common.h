@@ -63,6 +63,73 @@ union Pack8 {
   half_t e[4];
 };
 
+// Global-memory accesses with the address space spelled out at the access: a pointer the compiler cannot trace to a kernel
+// argument (gemm_glds.hip, reload_params) is generic to it (flat_load / flat_store, which also tick lgkmcnt and order against
+// LDS reads); through these they are global_load / global_store whatever the pointer's provenance.
+template <int BYTES> struct GRaw;
+template <> struct GRaw<2>  { typedef unsigned short type; };
+template <> struct GRaw<4>  { typedef unsigned int type; };
+template <> struct GRaw<8>  { typedef unsigned int type __attribute__((ext_vector_type(2))); };
+template <> struct GRaw<16> { typedef unsigned int type __attribute__((ext_vector_type(4))); };
+template <class T>
+__device__ __forceinline__ T gld(const void* ptr) {
+  typedef typename GRaw<sizeof(T)>::type V;
+  const V v = *reinterpret_cast<const __attribute__((address_space(1))) V*>((unsigned long)ptr);
+  T out;
+  __builtin_memcpy(&out, &v, sizeof(T));
+  return out;
+}
+
+// Cache policy of an output store.  A policy changes where the line lives after the store, never the value
+// and never the visibility rules: consumers are later launches, ordered by the kernel boundary as before.
+//   ST_PLAIN  the line stays dirty in the XCD's L2 until something writes it back (at the latest the end of the kernel)
+//   ST_WT     write-through (sc1): the bytes leave the L2 as they are stored, the kernel ends with nothing left to write back
+//   ST_NT     non-temporal (nt): kept in L2, marked for early eviction
+enum StorePolicy { ST_PLAIN = 0, ST_WT = 1, ST_NT = 2 };
+// The policy of each family of stores, decided family by family on end-to-end pairs (profiles/store_policy.md): the final
+// store passes of the GEMM / convolution kernels write through (-1.45 % / -0.87 % per batch on two machines, nothing on a third); every
+// other family's write-through and non-temporal arms were inside the run-to-run spread or slower and stay plain.
+constexpr int PFD_ST_SLAB = ST_PLAIN;      // split-K partial sums (epilogue_store, slab branch): sc1 +0.15 %, nt -0.4 % (inside the spread)
+constexpr int PFD_ST_REDUCE = ST_PLAIN;    // outputs of the split-K reduction kernels: sc1 -0.04 %
+constexpr int PFD_ST_OUT = ST_WT;          // final outputs of the GEMM / convolution store passes (with ln_out; not the 2-byte tail)
+constexpr int PFD_ST_ATTN = ST_PLAIN;      // attention outputs: sc1 +0.6 %
+constexpr int PFD_ST_NORM = ST_PLAIN;      // GroupNorm / LayerNorm apply kernels: sc1 -0.06 %
+
+template <int POLICY = ST_PLAIN, class T>
+__device__ __forceinline__ void gst(void* ptr, T val) {
+  typedef typename GRaw<sizeof(T)>::type V;
+  V v;
+  __builtin_memcpy(&v, &val, sizeof(T));
+  typedef __attribute__((address_space(1))) V* GPtr;
+  GPtr g = reinterpret_cast<GPtr>((unsigned long)ptr);
+#if defined(PFD_CPU_EMU)
+  *g = v;
+#else
+  if constexpr (POLICY == ST_NT) {
+    __builtin_nontemporal_store(v, g);
+  } else if constexpr (POLICY == ST_WT && sizeof(T) == 16) {
+    // (the trailing s_nop keeps the data registers from being rewritten in the store's issue shadow; "memory": the compiler
+    //  must not move other accesses of these bytes across a store it cannot see)
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(g), "v"(v) : "memory");
+  } else if constexpr (POLICY == ST_WT && sizeof(T) == 8) {
+    unsigned long bits;   // a relaxed agent-scope atomic store is the compiler-visible spelling of an 8-byte sc1 store
+    __builtin_memcpy(&bits, &val, 8);
+    __hip_atomic_store(reinterpret_cast<__attribute__((address_space(1))) unsigned long*>((unsigned long)ptr), bits,
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    static_assert(POLICY == ST_PLAIN, "write-through stores are 8 or 16 bytes wide");
+    *g = v;
+  }
+#endif
+}
+// The same for a store through a pointer the compiler can trace to a kernel argument: under ST_PLAIN it is the ordinary typed
+// store (type-based alias information and __restrict__ intact, so the schedule around it is what it always was)
+template <int POLICY = ST_PLAIN, class T>
+__device__ __forceinline__ void gst_t(T* ptr, T val) {
+  if constexpr (POLICY == ST_PLAIN) *ptr = val;
+  else gst<POLICY>(ptr, val);
+}
+
 // XCD-aware, bijective remap of a linear block id: the dispatcher places block b on XCD
 // b % 8; give every XCD one contiguous chunk of the tile space so neighbouring tiles
 // (which share an operand panel) meet in the same L2.  Speed only, never correctness.

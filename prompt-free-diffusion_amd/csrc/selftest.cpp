@@ -1436,6 +1436,7 @@ static const Mode kModes[] = {
     {"--bench-patch", nullptr, nullptr, bench_patch, "one 3x3 convolution per image width the patch kernel serves"},
     {"--bench-gn-conv", nullptr, nullptr, bench_gn_conv_list, "GroupNorm + conv as two launches vs table + prologue"},
     {"--launch-floor", nullptr, nullptr, bench_launch_floor, "per-launch cost of the runtime, in-stream and as a hipGraph"},
+    {"--boundary", nullptr, nullptr, bench_boundary, "cost of a dependent kernel boundary behind 0 ... 64 MB of output, per store policy"},
     {"--replay", nullptr, nullptr, [](int n, char** a) { return n > 0 ? replay(a[0], false, 0) : 2; },
      "<file>  relaunch a recorded GEMM / conv launch list (switches: PFD_REPLAY_DET, PFD_REPLAY_LN, PFD_REPLAY_TILED = 1)"},
     {"--replay-time", nullptr, nullptr, [](int n, char** a) { return n > 0 ? replay(a[0], true, n > 1 ? atoi(a[1]) : 0) : 2; },

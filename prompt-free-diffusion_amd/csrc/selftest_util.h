@@ -138,5 +138,7 @@ int bench_gn_conv_list(int, char**);
 int bench_attn_list(int, char**);
 int bench_gn_list(int, char**);
 int bench_launch_floor(int, char**);
+// selftest_boundary.cpp
+int bench_boundary(int, char**);
 // selftest_replay.cpp
 int replay(const char* path, bool timed, int force_tile);

@@ -13,6 +13,7 @@
   3. scratch (register spills) in any kernel.
 
 usage: isa_audit.py [file.hip ...]   (default: gemm_glds.hip gemm_conv.hip norm.hip)   -> prints one line per kernel, exit 1 on a finding
+       isa_audit.py --stores [file.hip ...]   -> per kernel: registers, scratch and how many global stores carry which cache policy
 """
 import os
 import re
@@ -31,11 +32,18 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{REPO}/inclu
 KNOWN = {}
 
 
+# per-file flags of csrc/Makefile (register counts are compared with the library's own build)
+FILE_FLAGS = {"attention3.hip": ["-fno-honor-nans"]}
+
+
 def compile_asm(src):
     out = os.path.join(tempfile.gettempdir(), "pfd_isa_" + os.path.basename(src) + ".s")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src),
-                                                               os.path.getmtime(os.path.join(CSRC, "pfd_common.h"))):
-        subprocess.run([HIPCC] + FLAGS + [src, "-o", out], check=True, stderr=subprocess.DEVNULL)
+    deps = [src, os.path.join(CSRC, "pfd_common.h")]
+    if os.path.basename(src) == "attention3.hip":
+        deps.append(os.path.join(CSRC, "attention3_kernel.h"))
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
+        subprocess.run([HIPCC] + FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + [src, "-o", out], check=True,
+                       stderr=subprocess.DEVNULL)
     return out
 
 
@@ -88,6 +96,43 @@ def findings(files=None):
             if v["ring"] and v["drained_barriers"] > 2:
                 bad.append(f"{k}: {v['drained_barriers']} barriers behind a vmcnt(0) wait in a ring kernel")
     return bad, rows
+
+
+# ---- cache policy of the global stores, with the registers and scratch of each kernel ----
+STORE_FILES = ("gemm_glds.hip", "norm.hip", "attention.hip", "attention3.hip", "elementwise.hip")
+
+
+def store_policies(asm_path):
+    """-> {kernel: dict(plain, wt, nt, vgprs, scratch)}: global stores by cache policy (wt = write-through, the sc1 bit;
+    nt = non-temporal), .amdhsa_next_free_vgpr and .amdhsa_private_segment_fixed_size"""
+    res, name, meta_of = {}, None, None
+    for line in open(asm_path):
+        m = re.match(r"^(_Z[A-Za-z0-9_]+):", line)
+        if m:
+            name = m.group(1)
+            res[name] = dict(plain=0, wt=0, nt=0, vgprs=0, scratch=0)
+            continue
+        t = line.strip()
+        if t.startswith(".amdhsa_kernel "):
+            meta_of = t.split()[1]
+        elif t.startswith(".end_amdhsa_kernel"):
+            meta_of = None
+        elif meta_of in res and t.startswith(".amdhsa_next_free_vgpr"):
+            res[meta_of]["vgprs"] = int(t.split()[-1])
+        elif meta_of in res and t.startswith(".amdhsa_private_segment_fixed_size"):
+            res[meta_of]["scratch"] = int(t.split()[-1])
+        elif name is not None and t.startswith("global_store_"):
+            flags = t.split(";")[0].split()
+            res[name]["wt" if "sc1" in flags else "nt" if "nt" in flags else "plain"] += 1
+    return {k: v for k, v in res.items() if "kernel" in k}
+
+
+def store_policy_rows(files=None):
+    from concurrent.futures import ThreadPoolExecutor
+    files = files or [os.path.join(CSRC, f) for f in STORE_FILES]
+    with ThreadPoolExecutor(len(files)) as ex:      # (the compiles run side by side: gemm_glds.hip alone takes a minute)
+        asm = list(ex.map(compile_asm, files))
+    return [(os.path.basename(f), k, v) for f, a in zip(files, asm) for k, v in sorted(store_policies(a).items())]
 
 
 # ---- the fragment pipeline of the wave-specialised patch kernel (DESIGN.md 3.16) ----
@@ -197,6 +242,10 @@ def patch_pipeline_main():
 if __name__ == "__main__":
     if sys.argv[1:] == ["--patch-pipeline"]:
         sys.exit(patch_pipeline_main())
+    if sys.argv[1:2] == ["--stores"]:
+        for f, k, v in store_policy_rows([os.path.abspath(a) for a in sys.argv[2:]] or None):
+            print(f"{f:16s} {k} vgprs={v['vgprs']} scratch={v['scratch']} stores: plain={v['plain']} wt={v['wt']} nt={v['nt']}")
+        sys.exit(0)
     bad, rows = findings([os.path.abspath(a) for a in sys.argv[1:]] or None)
     for f, k, v in rows:
         print(f"{f:14s} {k[:84]:84s} loads={v['loads']:3d} serialised={v['serialised']:2d} "
