@@ -449,6 +449,40 @@ int pfd_cfg_dpmpp_step(const void* eps, int32_t nb, const float* x, const float*
 int pfd_latent_start(const void* moments, int32_t Bm, const int64_t* key, float scale_factor, float sq_at,
                      float sq_1mat, float posterior_mul, float* x0, float* xt, int32_t B, int32_t C, int32_t h,
                      int32_t w, pfd_stream_t stream);
+/* Masked regeneration (inpainting), the sampler step: pfd_cfg_ddim_step_rng / pfd_cfg_ddim_step_ps (solver 0) or
+ * pfd_cfg_dpmpp_step (solver 1) with the blend that keeps the unmasked region on the init picture's trajectory, one launch
+ * (lib/inpaint.py is the same specification on the host; the reference's ddim.py has no masked path).  For element
+ * e = (c*h + y)*w + x of sample b with key row key[b] = {seed, sample_id}:
+ *   xp    = the unmasked update of that solver.  solver 0: coef is the DDIM row [5]; when its sigma != 0 the step noise
+ *           is sigma * noise_mul * z, z the stream-0 normal of (key[b], step, e) -- there is no form with a noise tensor.
+ *           solver 1: coef is the DPM-Solver++ row [8], x0_prev the history or NULL for a first-order step.
+ *   known = ksq * x0_keep[e] + ks * z_keep,   z_keep the normal of (key[b], step, e) with the counter's fourth word set to 3
+ *   x_out = m * xp + (1 - m) * known,         m = mask[b or 0, y, x], the same for every channel; values in [0, 1]
+ * in exactly this form: m = 1 gives xp's bits (those of the unmasked entry point), m = 0 gives known's.  pred_x0 is the
+ * unmasked one; xin_next holds half(x_out).  ksq = sqrt(a_prev), ks = sqrt(1 - a_prev) of the row being stepped to, and
+ * (1, 0) at the last step, where the kept region ends as x0_keep itself.  sigma == 0 and ks == 0 each skip their
+ * generator call.  x0_keep: fp32 NCHW [B, C, h, w] (pfd_latent_start's x0); mask: fp32 [Bm, h, w], Bm 1 or B; scale: device
+ * fp32 [B] or NULL as in pfd_cfg_ddim_step_ps.  Everything else as in the unmasked entry points.  A NULL eps / x / key /
+ * coef / x0_keep / mask / x_out / pred_x0, solver not 0 or 1, step < 0, Bm not in {1, B}, x0_keep (or x0_prev) aliasing an
+ * output, x0_prev with solver 0, nb not 1 or 2, rep not 1 or 2 with xin_next or a dimension <= 0 is PFD_EINVAL;
+ * C*h*w > 2^34 is PFD_ESHAPE; nothing is launched then. */
+int pfd_cfg_step_masked(const void* eps, int32_t nb, const float* x, int32_t solver, const float* x0_prev,
+                        const int64_t* key, int32_t step, float noise_mul, const float* coef, const float* scale,
+                        const float* x0_keep, const float* mask, int32_t Bm, float ksq, float ks, float* x_out,
+                        float* pred_x0, void* xin_next, int32_t rep, int32_t B, int32_t C, int32_t h, int32_t w,
+                        pfd_stream_t stream);
+/* uint8 mask(s) [Bm, Hm, Wm] -> the binary grid [Bm, gh, gw], fp32 0.0 / 1.0 (out_f32 != 0) or uint8 0 / 1.  Cell y
+ * covers mask rows lo = (y*Hm)/gh up to hi = max(lo + 1, ceil((y+1)*Hm/gh)) in integer arithmetic, columns alike; a cell
+ * is set if any pixel of its footprint is >= 128.  Footprints are never empty and together cover the mask: the rule
+ * dilates and never erodes.  NULL pointers or a dimension <= 0 is PFD_EINVAL, a side above 8192 PFD_ESHAPE. */
+int pfd_mask_grid_u8(const void* mask, int32_t Bm, int32_t Hm, int32_t Wm, void* out, int32_t out_f32, int32_t gh,
+                     int32_t gw, pfd_stream_t stream);
+/* out[i, y, x, :] = sel[i or 0, y, x] ? decoded[i, y, x, :] : init[i or 0, y, x, :] on packed uint8 pictures:
+ * decoded, out [n, H, W, C]; init [Bi, H, W, C]; sel [Bs, H, W] (pfd_mask_grid_u8 at the pixel grid); Bi, Bs 1 or n.
+ * NULL pointers, a dimension <= 0, Bi / Bs not in {1, n} or out aliasing an input is PFD_EINVAL; a side above 8192 or
+ * C > 4 is PFD_ESHAPE. */
+int pfd_composite_u8(const void* decoded, const void* init, int32_t Bi, const void* sel, int32_t Bs, void* out, int32_t n,
+                     int32_t H, int32_t W, int32_t C, pfd_stream_t stream);
 /* y = a + b (f16, fp32 add), n elements; b may be NULL (copy). */
 int pfd_add_f16(const void* a, const void* b, void* y, int64_t n, pfd_stream_t stream);
 /* y = alpha*a + beta*b (f16 storage, fp32 math), n elements; b may be NULL (y = alpha*a).  The

@@ -4,6 +4,7 @@
 // except pfd_nhwc_to_nchw / pfd_add_f16 which see full-size images.
 #include "pfd_common.h"
 #include "philox.h"
+#include "step_common.h"
 
 namespace {
 
@@ -90,51 +91,8 @@ __global__ void timestep_embedding_kernel(const int64_t* __restrict__ t, half_t*
 }
 
 // ---- the fused CFG + sampler step -------------------------------------------------------------------------------------
-// One copy of what the three step kernels (cfg_ddim_kernel, cfg_dpmpp_kernel, cfg_ddim_rng_kernel) compute per element:
-// the guided eps, pred_x0 and the emit of the next UNet input.  That the kernels agree bit for bit on these is a property
-// of the functions below.  Each kernel keeps its own decode of the thread index.
-
-// NHWC index of element (b, c, yh, xw) of an NCHW [B, C, h, w] tensor
-__device__ __forceinline__ long nhwc_index(int b, int c, int yh, int xw, int C, int h, int w) {
-  return (((long)b * h + yh) * w + xw) * C + c;
-}
-
-// the guided eps of the element at NHWC index ei: eps holds nb batches of n elements, unconditional first
-__device__ __forceinline__ float guided_eps(const half_t* __restrict__ eps, int nb, long n, long ei, float scale) {
-  if (nb == 2) {
-    const float eu = (float)eps[ei];
-    const float ec = (float)eps[n + ei];
-    return eu + scale * (ec - eu);
-  }
-  return (float)eps[ei] * scale;
-}
-
-__device__ __forceinline__ float pred_x0_of(float xv, float e, float s1mat, float isq_at) {
-  return (xv - s1mat * e) * isq_at;
-}
-
-// `rep` fp16 copies of the next UNet input at NHWC index ei (nothing without xin_next)
-__device__ __forceinline__ void emit_next(half_t* __restrict__ xin_next, int rep, long n, long ei, float v) {
-  if (xin_next) {
-    const half_t hv = (half_t)v;
-    for (int r = 0; r < rep; ++r) xin_next[(long)r * n + ei] = hv;
-  }
-}
-
-// the per-step numbers of a DDIM row {a_t, a_prev, sigma_t, sqrt(1-a_t), guidance scale}
-struct DdimStep {
-  float sigma, s1mat, isq_at, sq_aprev, dir;
-  __device__ __forceinline__ explicit DdimStep(const float* __restrict__ coef) {
-    const float a_t = coef[0], a_prev = coef[1];
-    sigma = coef[2];
-    s1mat = coef[3];
-    isq_at = 1.0f / sqrtf(a_t);
-    sq_aprev = sqrtf(a_prev);
-    dir = sqrtf(fmaxf(1.0f - a_prev - sigma * sigma, 0.f));
-  }
-  // x_prev without the noise term
-  __device__ __forceinline__ float update(float p0, float e) const { return sq_aprev * p0 + dir * e; }
-};
+// What the three step kernels (cfg_ddim_kernel, cfg_dpmpp_kernel, cfg_ddim_rng_kernel) compute per element -- the guided
+// eps, pred_x0, the emit of the next UNet input -- is step_common.h, shared with the masked step of inpaint.hip.
 
 // PS (per-sample guidance scale, pfd_cfg_ddim_step_ps): scale_ps[b] in place of coef[4]; nothing else differs, and the
 // PS = false instantiation never reads scale_ps.
@@ -398,24 +356,8 @@ __global__ void image_u8_kernel(const half_t* __restrict__ x, uint8_t* __restric
   }
 }
 
-inline int grid_for(long n, int block) {
-  long g = (n + block - 1) / block;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 // ---- the step entry points' shared host side ---------------------------------------------------------------------------
-// what all four step entry points check alike
-inline bool step_args_ok(int nb, int B, int C, int h, int w, const void* xin_next, int rep) {
-  return nb >= 1 && nb <= 2 && B > 0 && C > 0 && h > 0 && w > 0 && !(xin_next && (rep < 1 || rep > 2));
-}
-
-// a thread's quad is one 16-byte access of x / x_prev / pred_x0 (cfg_ddim_rng_kernel<VEC = true>)
-inline bool quad_vec_ok(int w, const float* x, const float* x_prev, const float* pred_x0) {
-  return !(w & 3) && !((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_prev) |
-                        reinterpret_cast<uintptr_t>(pred_x0)) & 15);
-}
+// (grid_for, step_args_ok and quad_vec_ok: step_common.h)
 
 // The two launches of the DDIM step on checked arguments: the plain kernel, and the seeded one in the VEC form that the
 // alignment allows.  The entry point hands in its instantiations (PS or not) and its name for the launch check.

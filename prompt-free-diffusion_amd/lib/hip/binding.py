@@ -89,6 +89,10 @@ SIGNATURES = {
                                     _i32, _vp]),
     "pfd_cfg_dpmpp_step": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "pfd_latent_start": (_i32, [_vp, _i32, _vp, _f32, _f32, _f32, _f32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "pfd_cfg_step_masked": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _vp, _vp,
+                                   _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "pfd_mask_grid_u8": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "pfd_composite_u8": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pfd_add_f16": (_i32, [_vp, _vp, _vp, _i64, _vp]),
     "pfd_axpby_f16": (_i32, [_vp, _f32, _vp, _f32, _vp, _i64, _vp]),
     "pfd_add_rowvec_f16": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp]),

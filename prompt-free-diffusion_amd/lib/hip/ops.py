@@ -954,6 +954,131 @@ def cfg_dpmpp_step(eps, nb, x, coef, x0_prev=None, want_next=False, rep=None, sc
     return x_next, pred_x0, xin
 
 
+MASKED_SOLVERS = {'ddim': 0, 'dpmpp': 1}
+
+
+def mask_rows(mask, B, h, w):
+    """the mask of cfg_step_masked, checked: float32 [1 | B, h, w] or [1 | B, 1, h, w] -> the contiguous [1 | B, h, w] view"""
+    if not (torch.is_tensor(mask) and mask.dtype == torch.float32 and mask.dim() in (3, 4)):
+        raise ValueError(f"mask must be a float32 tensor [1 | {B}, {h}, {w}] or [1 | {B}, 1, {h}, {w}]")
+    if mask.dim() == 4:
+        if mask.shape[1] != 1:
+            raise ValueError(f"mask must have one channel (it is shared by the latent's channels), got {tuple(mask.shape)}")
+        mask = mask[:, 0]
+    if mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (h, w):
+        raise ValueError(f"mask must be [1 | {B}, {h}, {w}], got {tuple(mask.shape)}")
+    return mask
+
+
+def cfg_step_masked(eps, nb, x, coef, *, solver='ddim', x0_prev=None, keep_key=None, step=None, x0_keep=None, mask=None,
+                    ksq=None, ks=None, noise_mul=1.0, scale=None, want_next=True, rep=None):
+    """The masked (inpainting) form of cfg_ddim_step (solver='ddim') / cfg_dpmpp_step (solver='dpmpp') in one launch
+    (pfd_cfg_step_masked; lib/inpaint.py is the same function on the host): x_out = m * xp + (1 - m) * known with xp the
+    unmasked update and known = ksq * x0_keep + ks * z_keep, z_keep the stream-3 normal of (keep_key[b], step, element).
+    keep_key: int64 [B, 2] rows (seed, sample_id), required: a DDIM row with sigma != 0 draws its step noise from the same
+    rows (stream 0, times noise_mul) -- there is no form with a noise tensor.  x0_keep: fp32 NCHW like x, the clean latent
+    of the init picture (latent_start(..., want_x0=True)); mask: fp32 [1 | B, h, w] in [0, 1], 1 = regenerate; ksq, ks:
+    lib/inpaint.py::step_constants of the row stepped to.  coef, x0_prev, scale, want_next, rep: as in the unmasked ops.
+    The mask's values are the caller's (reading them back would synchronise a loop that is captured): outside [0, 1] the
+    blend extrapolates, nothing is read or written out of bounds.
+    Returns (x_out fp32 NCHW, pred_x0 fp32 NCHW -- the unmasked one --, xin_next f16 NHWC | None)."""
+    if solver not in MASKED_SOLVERS:
+        raise ValueError(f"cfg_step_masked: solver must be 'ddim' or 'dpmpp', got {solver!r}")
+    if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() == 4):
+        raise ValueError("cfg_step_masked: x must be a float32 NCHW tensor")
+    B, Cc, h, w = x.shape
+    if nb not in (1, 2):
+        raise ValueError(f"cfg_step_masked: nb must be 1 or 2, got {nb!r}")
+    rep = nb if rep is None else rep
+    if rep not in (1, 2):
+        raise ValueError(f"cfg_step_masked: rep must be 1 or 2, got {rep!r}")
+    if not (torch.is_tensor(eps) and eps.dtype == torch.float16 and tuple(eps.shape) == (nb * B, h, w, Cc) and
+            eps.device == x.device and eps.is_contiguous()):
+        raise ValueError(f"cfg_step_masked: eps must be a contiguous f16 NHWC tensor [{nb * B}, {h}, {w}, {Cc}] next to x")
+    if keep_key is None or step is None or x0_keep is None or mask is None or ksq is None or ks is None:
+        raise ValueError("cfg_step_masked: keep_key, step, x0_keep, mask, ksq and ks are all required")
+    if int(step) != step or int(step) < 0:
+        raise ValueError(f"cfg_step_masked: step must be a non-negative integer, got {step!r}")
+    import math
+    if not all(math.isfinite(float(v)) for v in (ksq, ks, noise_mul)):
+        raise ValueError(f"cfg_step_masked: ksq, ks and noise_mul must be finite, got {ksq!r}, {ks!r}, {noise_mul!r}")
+    ncoef = 5 if solver == 'ddim' else 8
+    if not (torch.is_tensor(coef) and tuple(coef.shape) == (ncoef,) and coef.dtype == torch.float32):
+        raise ValueError(f"cfg_step_masked: coef must be a float32 row of {ncoef} numbers for solver {solver!r}")
+    if x0_prev is not None and solver != 'dpmpp':
+        raise ValueError("cfg_step_masked: x0_prev goes with solver='dpmpp'")
+    for t, what in ((x0_keep, 'x0_keep'), (x0_prev, 'x0_prev')):
+        if t is not None and not (torch.is_tensor(t) and t.shape == x.shape and t.dtype == torch.float32 and
+                                  t.device == x.device and t.is_contiguous()):
+            raise ValueError(f"cfg_step_masked: {what} must be a contiguous float32 tensor of x's shape, next to x")
+    mask = mask_rows(mask, B, h, w)
+    if mask.device != x.device or not mask.is_contiguous():
+        raise ValueError("cfg_step_masked: mask must be contiguous and live next to x")
+    if not (torch.is_tensor(keep_key) and keep_key.dtype == torch.int64 and tuple(keep_key.shape) == (B, 2)):
+        raise ValueError(f"cfg_step_masked: keep_key must be an int64 tensor [{B}, 2] of (seed, sample_id) rows")
+    if not x.is_cuda:
+        raise RuntimeError("cfg_step_masked: x must live on the GPU; the HIP path has no CPU fallback")
+    if keep_key.device != x.device or not keep_key.is_contiguous() or not x.is_contiguous():
+        raise ValueError("cfg_step_masked: keep_key must be contiguous and live next to x, x contiguous")
+    if scale is not None:
+        scale = guidance_scale_rows(scale, B, x.device)
+    x_out, pred_x0, xin = _step_outputs(x, rep, want_next)
+    rc = _lib().pfd_cfg_step_masked(eps.data_ptr(), nb, x.data_ptr(), MASKED_SOLVERS[solver], _ptr(x0_prev),
+                                    keep_key.data_ptr(), int(step), float(noise_mul), coef.data_ptr(), _ptr(scale),
+                                    x0_keep.data_ptr(), mask.data_ptr(), int(mask.shape[0]), float(ksq), float(ks),
+                                    x_out.data_ptr(), pred_x0.data_ptr(), _ptr(xin), rep, B, Cc, h, w, _stream())
+    _b.check(rc, "pfd_cfg_step_masked")
+    return x_out, pred_x0, xin
+
+
+def mask_grid_u8(mask, gh, gw, dtype=torch.float32):
+    """uint8 mask(s) [Hm, Wm] | [Bm, Hm, Wm] on the device (>= 128: regenerate) -> the binary grid [Bm, gh, gw] in `dtype`
+    (float32 for the latent grid of cfg_step_masked, uint8 for the pixel grid of composite_u8): a cell is set if any pixel
+    of its footprint is (pfd_mask_grid_u8, lib/inpaint.py::mask_grid) -- the rule dilates and never erodes."""
+    if not (torch.is_tensor(mask) and mask.dtype == torch.uint8 and mask.dim() in (2, 3)):
+        raise ValueError("mask_grid_u8: a uint8 tensor [Hm, Wm] or [Bm, Hm, Wm] expected")
+    if dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"mask_grid_u8: the grid is float32 or uint8, not {dtype}")
+    gh, gw = int(gh), int(gw)
+    m = mask[None] if mask.dim() == 2 else mask
+    Bm, Hm, Wm = m.shape
+    from ..image_io import MAX_SIDE
+    if min(Bm, Hm, Wm, gh, gw) < 1 or max(Hm, Wm, gh, gw) > MAX_SIDE:
+        raise ValueError(f"mask_grid_u8: sides must be in [1, {MAX_SIDE}], got {Hm} x {Wm} -> {gh} x {gw}")
+    if not mask.is_cuda:
+        raise RuntimeError("mask_grid_u8: the mask must live on the GPU; the HIP path has no CPU fallback")
+    m = m.contiguous()
+    out = torch.empty((Bm, gh, gw), dtype=dtype, device=m.device)
+    _b.check(_lib().pfd_mask_grid_u8(m.data_ptr(), Bm, Hm, Wm, out.data_ptr(), 1 if dtype == torch.float32 else 0, gh, gw,
+                                     _stream()), "pfd_mask_grid_u8")
+    return out
+
+
+def composite_u8(decoded, init, sel):
+    """out[i, y, x, :] = sel[i or 0, y, x] ? decoded[i, y, x, :] : init[i or 0, y, x, :] (pfd_composite_u8): decoded uint8
+    [n, H, W, C], init uint8 [1 | n, H, W, C] (the init picture at the output size), sel uint8 [1 | n, H, W]
+    (mask_grid_u8 at the pixel grid) -> uint8 [n, H, W, C]"""
+    for t, what, nd in ((decoded, 'decoded', 4), (init, 'init', 4), (sel, 'sel', 3)):
+        if not (torch.is_tensor(t) and t.dtype == torch.uint8 and t.dim() == nd):
+            raise ValueError(f"composite_u8: {what} must be a uint8 tensor of {nd} dimensions")
+    n, H, W_, Cc = decoded.shape
+    if init.shape[0] not in (1, n) or tuple(init.shape[1:]) != (H, W_, Cc):
+        raise ValueError(f"composite_u8: init must be [1 | {n}, {H}, {W_}, {Cc}], got {tuple(init.shape)}")
+    if sel.shape[0] not in (1, n) or tuple(sel.shape[1:]) != (H, W_):
+        raise ValueError(f"composite_u8: sel must be [1 | {n}, {H}, {W_}], got {tuple(sel.shape)}")
+    if n < 1 or Cc > 4:
+        raise ValueError("composite_u8: at least one picture of at most 4 channels expected")
+    if not decoded.is_cuda:
+        raise RuntimeError("composite_u8: the pictures must live on the GPU; the HIP path has no CPU fallback")
+    if init.device != decoded.device or sel.device != decoded.device:
+        raise ValueError("composite_u8: init and sel must live next to decoded")
+    decoded, init, sel = decoded.contiguous(), init.contiguous(), sel.contiguous()
+    out = torch.empty_like(decoded)
+    _b.check(_lib().pfd_composite_u8(decoded.data_ptr(), init.data_ptr(), int(init.shape[0]), sel.data_ptr(),
+                                     int(sel.shape[0]), out.data_ptr(), n, H, W_, Cc, _stream()), "pfd_composite_u8")
+    return out
+
+
 def add(a, b, out=None):
     _chk16(a, "add a")
     _chk16(b, "add b")

@@ -11,6 +11,7 @@ holds what those kernels need from the host and nothing else:
   * `check_control_preprocess`: argument checks of the optional edge detector in front of the hint encoder (csrc/canny.hip).
   * `check_init_picture` / `check_img2img`: argument checks of an img2img request's init picture, strength and posterior
     (lib/img2img.py, csrc/latent.hip).
+  * `check_mask`: argument checks of an inpainting request's mask and composite switch (lib/inpaint.py, csrc/inpaint.hip).
 """
 import math
 
@@ -144,6 +145,51 @@ def check_img2img(init, height, width, steps, strength, posterior='sample', what
     check_posterior(posterior)
     check_init_picture(init, height, width, what)
     return k
+
+
+def check_mask(mask, init, height, width, composite=False, as_uint8=False, n=None, what="mask"):
+    """the `mask` / `composite` pair of an inpainting request (lib/inpaint.py): the mask is a uint8 picture [Hm, Wm] or
+    [Hm, Wm, 1] of any size the picture checks allow (>= 128: regenerate), reduced on the device to the latent grid, or a
+    float tensor already at latent resolution, [height/8, width/8] with optional leading [1 | n] or [1 | n, 1] axes, values
+    in [0, 1].  A mask needs `init`; composite needs as_uint8, a uint8 init and a uint8 mask (the pixels outside the mask
+    are the init picture's bytes).  -> 'u8' | 'latent' | None (no mask).  Raises ValueError; touches no device."""
+    if mask is None:
+        if composite:
+            raise ValueError("composite=True without a mask")
+        return None
+    if init is None:
+        raise ValueError(f"{what}: masked regeneration needs an init picture (init=)")
+    height, width = int(height), int(width)
+    if height < 8 or width < 8 or height % 8 or width % 8:
+        raise ValueError(f"{what}: the output size must be a positive multiple of 8 (the VAE's stride), got {height} x {width}")
+    if wants_ingest(mask):
+        shape, dtype = getattr(mask, "shape", None), str(getattr(mask, "dtype", ""))
+        if shape is None or not dtype.endswith("uint8"):
+            raise ValueError(f"{what}: a uint8 mask [Hm, Wm] expected, got {type(mask).__name__} {dtype}")
+        shape = tuple(int(v) for v in shape)
+        if len(shape) == 3 and shape[2] == 1:
+            shape = shape[:2]
+        if len(shape) != 2:
+            raise ValueError(f"{what}: a uint8 mask must be [Hm, Wm] or [Hm, Wm, 1], got {tuple(mask.shape)}")
+        if min(shape) < 1 or max(shape) > MAX_SIDE:
+            raise ValueError(f"{what}: mask sides must be in [1, {MAX_SIDE}], got {shape[0]} x {shape[1]}")
+        check_resize(shape, (height, width), what)
+        kind = 'u8'
+    else:
+        shape = tuple(int(v) for v in mask.shape)
+        lead = shape[:-2]
+        ok = mask.is_floating_point() and len(shape) in (2, 3, 4) and shape[-2:] == (height // 8, width // 8) and \
+            (len(lead) == 0 or lead[0] == 1 or (n is not None and lead[0] == int(n))) and (len(lead) < 2 or lead[1] == 1)
+        if not ok:
+            raise ValueError(f"{what}: a float mask must be [{height // 8}, {width // 8}] at latent resolution (leading "
+                             f"[1 | n] or [1 | n, 1] allowed), got {shape} {mask.dtype}")
+        kind = 'latent'
+    if composite:
+        if not as_uint8:
+            raise ValueError("composite=True needs as_uint8=True: the composite is made of the init picture's bytes")
+        if not wants_ingest(init) or kind != 'u8':
+            raise ValueError("composite=True needs a uint8 init picture and a uint8 mask")
+    return kind
 
 
 def wants_ingest(x):

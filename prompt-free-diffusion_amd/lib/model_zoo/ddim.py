@@ -42,10 +42,22 @@ ddim_timesteps[:k] from that latent, which the caller noised to the level of ddi
 start of ops.latent_start, lib/img2img.py); every solver, the multi-context loop included.  The graph key already
 carries the step count and the timesteps.  Without 'xt_steps' nothing changes; the x_info['x0'] branch keeps the
 reference's convention (noised to ddim_timesteps[k]).
+
+Masked regeneration (opt-in, inpainting): x_info['mask'] (fp32 [1 | B, h, w] or [1 | B, 1, h, w], 1 = regenerate, soft
+values legal) together with x_info['x0_keep'] (the clean latent of the init picture, ops.latent_start(..., want_x0=True))
+and x_info['keep_key'] (int64 [B, 2] rows (seed, sample_id)) -- all three or none.  Every step of the loop is then the
+masked kernel (pfd_cfg_step_masked, lib/inpaint.py): outside the mask the latent is x0_keep noised to the level the step
+goes to, with noise that is a function of (key row, step index, element), and x0_keep itself after the last step.  Every
+solver; a keep_key is no noise_key and does not make a multistep solver refuse.  eta > 0 needs x_info['noise_key'], equal
+to keep_key (the kernel draws the step noise from the same rows): the masked kernel draws nothing from the global
+generator.  The loop is captured like any keyed loop, the three tensors being static inputs behind the other five, and the
+graph key gains a trailing element.  The multi-context loop and the single-step entry points refuse a mask.  Without a
+mask every path, launch sequence and graph key is what it was.
 """
 import numpy as np
 import torch
 
+from .. import inpaint as _inpaint
 from .. import solver as _solver
 from ..hip import ops
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps, noise_like
@@ -79,6 +91,39 @@ def _refuse_noise(solver, eta, noise_dropout, x_info):
         raise ValueError(f"solver {solver!r} is deterministic: noise_dropout > 0 is not available")
     if x_info.get('noise_key', None) is not None:
         raise ValueError(f"solver {solver!r} is deterministic: x_info['noise_key'] is not available")
+
+
+_MASK_KEYS = ('mask', 'x0_keep', 'keep_key')
+
+
+def _refuse_mask(x_info, what):
+    """the entry points without a masked form say so"""
+    if any(x_info.get(k, None) is not None for k in _MASK_KEYS):
+        raise ValueError(f"{what} has no masked form: x_info['mask'] / ['x0_keep'] / ['keep_key'] go with sample / ddim_sampling")
+
+
+def _masked_inputs(x_info, x, nkey, stochastic):
+    """-> (mask fp32 [1 | B, h, w], x0_keep fp32 like x, keep_key int64 [B, 2]) next to x, or (None, None, None): all
+    three of x_info['mask'], ['x0_keep'], ['keep_key'] or none"""
+    given = [x_info.get(k, None) is not None for k in _MASK_KEYS]
+    if not any(given):
+        return None, None, None
+    if not all(given):
+        raise ValueError("x_info['mask'], x_info['x0_keep'] and x_info['keep_key'] go together: all three or none")
+    B, C, h, w = x.shape
+    mask, x0_keep, kkey = (x_info[k] for k in _MASK_KEYS)
+    mask = ops.mask_rows(mask, B, h, w).to(x.device).contiguous()
+    if not (torch.is_tensor(x0_keep) and tuple(x0_keep.shape) == tuple(x.shape) and x0_keep.is_floating_point()):
+        raise ValueError(f"x_info['x0_keep'] must be a float tensor {tuple(x.shape)}, the clean latent of the init picture")
+    kkey = ops.noise_key_rows(kkey, B, x.device)
+    if stochastic:
+        if nkey is None:
+            raise ValueError("a masked request with eta > 0 needs x_info['noise_key']: the masked kernel draws nothing from "
+                             "the global generator")
+        if not torch.equal(nkey, kkey):
+            raise ValueError("x_info['noise_key'] and x_info['keep_key'] must be equal: the masked kernel draws the step "
+                             "noise and the kept region's noise from the same key rows")
+    return mask, x0_keep.to(device=x.device, dtype=torch.float32).contiguous(), kkey
 
 
 def _guidance(c_info, bs, device):
@@ -115,7 +160,7 @@ def _step_noise(x, sigma, index, nkey, temperature, noise_dropout, repeat_noise=
 
 class _CapturedLoop:
     """one captured trajectory: the hipGraph, its static inputs in the order (x, c_in, hint, nkey, sps) -- None where the
-    request has none --, its static outputs and what must live as long as the graph"""
+    request has none --, behind them (mask, x0_keep, keep_key) of a masked request, its static outputs and what must live as long as the graph"""
 
     def __init__(self, graph, inputs, outs, keep):
         self.graph, self.inputs, self.outs, self.keep = graph, inputs, outs, keep
@@ -240,12 +285,13 @@ class DDIMSampler(object):
                 raise ValueError("noise_dropout > 0 is not available with x_info['noise_key'] (dropout draws from the "
                                  "global generator: leave the key out)")
             nkey = ops.noise_key_rows(nkey, bs, device)
+        mask, x0_keep, kkey = _masked_inputs(x_info, x, nkey, stochastic)
 
         def make_loop():
             """the whole trajectory as a pure function of device tensors (capturable as one hipGraph), and its timestep table"""
             t_table = t_col.repeat(1, nb * bs)
 
-            def run_loop(x, c_in, hint, nkey, sps):
+            def run_loop(x, c_in, hint, nkey, sps, mask=None, x0_keep=None, kkey=None):
                 from .controlnet import PreparedHint
                 ps = {} if sps is None else {'scale': sps}
                 ctx = model.prepare_context(c_in)
@@ -266,7 +312,16 @@ class DDIMSampler(object):
                     index = total_steps - i - 1
                     eps = model.apply_model_nhwc(x_type, xin, t_table[i], c_type, ctx, control=ctl,
                                                  emb_table=emb_all[i:i + 1], cfg_pair=pair)
-                    if order is not None:
+                    if mask is not None:
+                        # masked regeneration: the same step, blended with the init picture's own trajectory outside the mask
+                        ksq, ks = _inpaint.step_constants(self.ddim_alphas_prev[index], index)
+                        first_order = order is None or order == 1 or i == 0 or index == 0
+                        x, pred_x0, xin = ops.cfg_step_masked(
+                            eps, nb, x, coef[index], solver='ddim' if order is None else 'dpmpp',
+                            x0_prev=None if first_order else x0_last, keep_key=kkey, step=index, x0_keep=x0_keep, mask=mask,
+                            ksq=float(ksq), ks=float(ks), noise_mul=temperature, want_next=True, rep=rep, **ps)
+                        x0_last = pred_x0
+                    elif order is not None:
                         # multistep: this step's pred_x0 is the next step's history; none on the first step of a run
                         # (an img2img start included) nor on the last, nor at order 1
                         first_order = order == 1 or i == 0 or index == 0
@@ -285,6 +340,8 @@ class DDIMSampler(object):
             return run_loop, t_table
 
         inputs = (x, c_in, hint, nkey, sps)
+        if mask is not None:
+            inputs = inputs + (mask, x0_keep, kkey)
         # a keyed schedule draws nothing from a generator: capturable whatever eta is
         if self.use_graph and (not stochastic or nkey is not None) and callback is None and x.is_cuda:
             # one hipGraph per (shape, schedule, weights version, flags); static input buffers, replayed per request.
@@ -296,6 +353,8 @@ class DDIMSampler(object):
                    None if nkey is None else (float(temperature), hash(np.asarray(self.ddim_sigmas).tobytes())))
             if order is not None:
                 key = key + (solver,)          # the DDIM key is what it was
+            if mask is not None:
+                key = key + (('mask', tuple(mask.shape)),)     # ... and so is every key without a mask
             xf, ixt, ix0 = self._graph_for(key, lambda: self._capture(*make_loop(), inputs, coef)).replay(inputs)
         else:
             xf, ixt, ix0 = make_loop()[0](*inputs)
@@ -347,6 +406,7 @@ class DDIMSampler(object):
                             verbose=True, log_every_t=100, solver='ddim'):
         if _solver.solver_order(solver) is not None:
             raise ValueError(f"solver {solver!r} is not available for multi-context sampling: use 'ddim'")
+        _refuse_mask(x_info, "sample_multicontext")
         self.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=verbose)
         if verbose:
             print(f'Data shape for DDIM sampling is {shape}, eta {eta}')
@@ -380,6 +440,7 @@ class DDIMSampler(object):
     @torch.no_grad()
     def ddim_sampling_multicontext(self, shape, x_info, c_info_list, noise_dropout=0., temperature=1.,
                                    log_every_t=100):
+        _refuse_mask(x_info, "ddim_sampling_multicontext")
         model = self.model
         device = model.device
         dtype = c_info_list[0]['conditioning'].dtype
@@ -410,6 +471,7 @@ class DDIMSampler(object):
     @torch.no_grad()
     def p_sample_ddim_multicontext(self, x_info, c_info_list, t, index, repeat_noise=False,
                                    use_original_steps=False, noise_dropout=0., temperature=1.):
+        _refuse_mask(x_info, "p_sample_ddim_multicontext")
         x = x_info['x']
         mix, scale, nb = self._mix_for(c_info_list, x.shape[0])
         t_in = torch.cat([t] * nb)
@@ -477,6 +539,7 @@ class DDIMSampler(object):
         """one step with the reference's calling convention (x NCHW in x_info['x'], returns
         (x_prev, pred_x0) in x.dtype); the loop above uses the same kernels without the
         per-step layout conversions."""
+        _refuse_mask(x_info, "p_sample_ddim")
         x = x_info['x']
         sps, scale, uc, cfg, nb = _guidance(c_info, x.shape[0], x.device)
         if cfg:

@@ -261,13 +261,14 @@ class PromptFreePipeline:
 
     @serialised
     @torch.no_grad()
-    def init_latent(self, init, height, width, steps, strength, keys, posterior='sample'):
+    def init_latent(self, init, height, width, steps, strength, keys, posterior='sample', want_x0=False):
         """the seeded start of an img2img request -> (x_t fp32 [n, 4, height/8, width/8] on the device, k): the latent of
         `init` -- a uint8 HWC picture of any size, resized to (height, width) on the device straight into the f16 NHWC
         the encoder reads, or a float tensor [1, 3, height, width] in [0, 1] -- sampled from the VAE posterior (or its
         mode), scaled and noised to the level of the first of the k = start_steps(steps, strength) steps the request
         runs, in one launch behind the encoder (ops.latent_start).  keys: int64 [n, 2] rows (seed, sample_id): sample i's
-        start is a function of the picture and keys[i] alone (lib/img2img.py); the picture is encoded once."""
+        start is a function of the picture and keys[i] alone (lib/img2img.py); the picture is encoded once.
+        want_x0: -> (x_t, k, x0), x0 the clean latent of the same draw, what a masked request keeps outside its mask."""
         k = image_io.check_img2img(init, height, width, steps, strength, posterior)
         dev = self.net.device
         if image_io.wants_ingest(init):
@@ -276,15 +277,51 @@ class PromptFreePipeline:
             pic = init.to(dev)
         moments = self._enc_stage(pic) if self._enc_stage is not None else self.net.vae_encode_moments(pic, 'image')
         sf = (getattr(self.net, 'latent_scale_factor', None) or {}).get('image', None)
+        if want_x0:
+            x0, x_t = ops.latent_start(moments, keys.to(dev), 1.0 if sf is None else sf, self._level(steps, k),
+                                       posterior=posterior, want_x0=True)
+            return x_t, k, x0
         x_t = ops.latent_start(moments, keys.to(dev), 1.0 if sf is None else sf, self._level(steps, k), posterior=posterior)
         return x_t, k
+
+    @serialised
+    @torch.no_grad()
+    def mask_grid(self, mask, height, width, n=None):
+        """the mask of an inpainting request at latent resolution -> fp32 [1 | n, height/8, width/8] on the device, 1 =
+        regenerate: a uint8 mask [Hm, Wm] of any size (>= 128: regenerate) is reduced on the device by the dilating rule of
+        lib/inpaint.py (ops.mask_grid_u8: a marked pixel always lies in a regenerated cell); a float tensor already at
+        latent resolution passes through after the shape check (soft values in [0, 1] are legal; a leading axis of n gives
+        each of the n samples its own mask)."""
+        kind = image_io.check_mask(mask, True, height, width, n=n)
+        dev = self.net.device
+        gh, gw = int(height) // 8, int(width) // 8
+        if kind == 'u8':
+            return ops.mask_grid_u8(self._mask_u8(mask), gh, gw, torch.float32)
+        return mask.to(device=dev, dtype=torch.float32).reshape(-1, gh, gw).contiguous()
+
+    def _mask_u8(self, mask):
+        """a checked uint8 mask -> contiguous uint8 [Hm, Wm] on the device"""
+        m = mask if torch.is_tensor(mask) else torch.from_numpy(mask)
+        return m.reshape(int(m.shape[0]), int(m.shape[1])).contiguous().to(self.net.device)
+
+    @serialised
+    @torch.no_grad()
+    def composite(self, images_u8, init, mask, height, width):
+        """decoded uint8 images [n, H, W, 3] with everything outside the mask replaced by the bytes of the init picture
+        (resized to the output size as the request's start was): the selection is the mask reduced to the PIXEL grid by
+        the same dilating rule (ops.mask_grid_u8), so it covers every marked pixel; one launch (ops.composite_u8)"""
+        dev = self.net.device
+        H, W = int(height), int(width)
+        init_u8 = ops.image_from_u8(image_io.to_device_u8(init, dev, 'init'), (H, W), layout='u8')
+        sel = ops.mask_grid_u8(self._mask_u8(mask), H, W, torch.uint8)
+        return ops.composite_u8(images_u8, init_u8, sel)
 
     @serialised
     @torch.no_grad()
     def generate(self, image, n_global, height, width, steps=50, scale=2.0, eta=0.0, seed=20, control=None,
                  uncond=None, decode=True, gather=False, verbose=False, timings=None, as_uint8=False,
                  device_noise=False, solver='ddim', control_preprocess=None, control_thresholds=(100, 200), init=None,
-                 strength=0.75, init_posterior='sample'):
+                 strength=0.75, init_posterior='sample', mask=None, composite=False):
         """returns (images, latents [n_local,4,h,w]); images = [n_local | n_global (gather), 3, H, W] in [0,1]
         in the model dtype, or -- as_uint8 -- packed uint8 [n, H, W, 3] (the bytes ToPILImage would produce,
         app.py:273-275; 4x fewer bytes through the all-gather); decode=False returns the latents twice.
@@ -307,7 +344,14 @@ class PromptFreePipeline:
         k = min(steps, int(steps * strength)) steps it runs (`init_latent`) instead of from x_T: no x_T is drawn, sample j
         of the GLOBAL batch draws its posterior and forward noise keyed (seed, j), so the result does not depend on the
         world size.  strength in (0, 1]: 1 runs every step (the picture only shades the start), small values stay close
-        to the picture.  init_posterior: 'sample' or 'mode' (the posterior mean).  timings gains init_encode_ms."""
+        to the picture.  init_posterior: 'sample' or 'mode' (the posterior mean).  timings gains init_encode_ms.
+        mask: inpainting (needs init) -- a uint8 mask [Hm, Wm] of any size, >= 128 marking what to regenerate, or a float
+        tensor at latent resolution (`mask_grid`).  Every step of the loop then keeps the latent outside the mask on the init
+        picture's own noised trajectory (pfd_cfg_step_masked, lib/inpaint.py), keyed (seed, j) per sample of the GLOBAL batch
+        like the start: no generator, the result does not depend on the world size, the loop replays as a hipGraph.  The
+        final latent outside the mask is the picture's clean latent itself.  eta > 0 needs device_noise.  composite (needs
+        as_uint8, a uint8 init and a uint8 mask): the pixels outside the mask are the init picture's bytes (`composite`),
+        before the gather."""
         from .model_zoo.ddim import is_per_sample
         from .solver import solver_order
         if solver_order(solver) is not None and (eta != 0. or device_noise):     # an unknown name raises here too
@@ -331,6 +375,12 @@ class PromptFreePipeline:
             image_io.check_img2img(init, height, width, steps, strength, init_posterior)
             if n_global % P:
                 raise ValueError("global batch must divide over the ranks")
+        image_io.check_mask(mask, init, height, width, composite, as_uint8, n=n_global // P)
+        if mask is not None and eta != 0. and not device_noise:
+            raise ValueError("a masked request with eta > 0 needs device_noise=True: the masked step draws nothing from "
+                             "the global generator")
+        if composite and not decode:
+            raise ValueError("composite=True needs decode=True")
         mk = _Marks(torch.device(dev).type == 'cuda') if timings is not None else None
         if mk:
             mk.mark()
@@ -355,9 +405,14 @@ class PromptFreePipeline:
             x_info = {'type': 'image', 'xt': xT.to(dev)}
             shape = list(xT.shape)
         else:
-            x_t, k = self.init_latent(init, height, width, steps, strength, shard_noise_keys(n_global, seed, r, P),
-                                      init_posterior)
-            x_info = {'type': 'image', 'xt': x_t, 'xt_steps': k}
+            keys = shard_noise_keys(n_global, seed, r, P)
+            if mask is None:
+                x_t, k = self.init_latent(init, height, width, steps, strength, keys, init_posterior)
+                x_info = {'type': 'image', 'xt': x_t, 'xt_steps': k}
+            else:
+                x_t, k, x0 = self.init_latent(init, height, width, steps, strength, keys, init_posterior, want_x0=True)
+                x_info = {'type': 'image', 'xt': x_t, 'xt_steps': k, 'mask': self.mask_grid(mask, height, width, n=n),
+                          'x0_keep': x0, 'keep_key': keys.to(dev)}
             shape = list(x_t.shape)
             if mk:
                 mk.mark()
@@ -376,6 +431,8 @@ class PromptFreePipeline:
             return x, x
         if as_uint8:
             img = self.net.vae_decode(x, 'image', out_uint8=True)
+            if composite:
+                img = self.composite(img, init, mask, height, width)
         else:
             img = self._vae_stage(x) if self._vae_stage is not None else self.net.vae_decode(x, 'image')
         if mk:

@@ -34,7 +34,7 @@ from .solver import solver_order
 class _Request:
     __slots__ = ("image", "n", "height", "width", "steps", "scale", "eta", "seed", "control", "uncond", "as_uint8",
                  "device_noise", "future", "mixed", "solver", "control_preprocess", "control_thresholds", "init", "strength",
-                 "init_k")
+                 "init_k", "mask", "composite")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -45,6 +45,8 @@ class _Request:
         how = () if self.solver in (None, 'ddim') else (self.solver,)     # a batch runs ONE solver; the DDIM keys are unchanged
         if self.init is not None:     # img2img: a batch runs ONE number of steps; every other key is unchanged
             how = how + (('init', int(self.init_k)),)
+        if self.mask is not None:     # inpainting: masked requests share batches with each other only; every other key is unchanged
+            how = how + (('mask', bool(self.composite)),)
         if self.mixed:
             return (self.height, self.width, self.steps, float(self.scale) == 1.0, float(self.eta),
                     self.control is None, self.uncond is None, bool(self.as_uint8), bool(self.device_noise)) + how
@@ -78,7 +80,7 @@ class PromptFreeServer:
     # ---- client side (any thread) -------------------------------------------------------------------
     def submit(self, image, n_samples=1, height=512, width=512, steps=50, scale=2.0, eta=0.0, seed=20,
                control=None, uncond=None, as_uint8=True, device_noise=False, solver='ddim', control_preprocess=None,
-               control_thresholds=(100, 200), init=None, strength=0.75):
+               control_thresholds=(100, 200), init=None, strength=0.75, mask=None, composite=False):
         """image [1,3,h,w] in [0,1] (any size); control [1,3,H,W] or None; uncond [1,148,768] or None (zeros).
         image and control may each be a uint8 HWC picture [h,w,3] (torch or numpy, any size; the reference picture
         at least 32 a side) instead: the request carries the bytes and the worker converts them on the device
@@ -95,6 +97,11 @@ class PromptFreeServer:
         [1,3,height,width] tensor: the request starts from that picture's latent, noised for the
         k = min(steps, int(steps * strength)) steps it runs, sample j keyed (seed, j).  Such requests share a batch with
         each other when k (and the rest of the key) is equal, each with its own picture and keys.
+        mask: inpainting (needs init; PromptFreePipeline.generate) -- a uint8 mask [Hm, Wm] of any size, >= 128 marking what
+        to regenerate, or a float tensor [height/8, width/8]: outside the mask the result stays the init picture.  Masked
+        requests of equal k share a batch with each other, each with its own picture, mask and keys; never with unmasked
+        ones.  eta > 0 needs device_noise.  composite (needs as_uint8, a uint8 init and a uint8 mask): the pixels outside
+        the mask are the init picture's bytes.
         -> Future of uint8 [n,H,W,3] (as_uint8) or float [n,3,H,W] images"""
         if self._stop:
             raise RuntimeError("server is closed")
@@ -123,8 +130,11 @@ class PromptFreeServer:
             raise ValueError(f"control must be a float tensor [1, 3, {height}, {width}] or a uint8 picture [h, w, 3]")
         thresholds = image_io.check_control_preprocess(control, control_preprocess, control_thresholds)
         init_k = None if init is None else image_io.check_img2img(init, int(height), int(width), int(steps), strength)
+        image_io.check_mask(mask, init, int(height), int(width), composite, as_uint8, n=1)
+        if mask is not None and float(eta) != 0.0 and not device_noise:
+            raise ValueError("a masked request with eta > 0 needs device_noise=True")
         r = _Request(image=image, n=int(n_samples), height=int(height), width=int(width), steps=int(steps), init=init,
-                     strength=strength, init_k=init_k,
+                     strength=strength, init_k=init_k, mask=mask, composite=bool(composite) if mask is not None else None,
                      scale=scale, eta=eta, seed=int(seed), control=control, uncond=uncond, as_uint8=as_uint8,
                      device_noise=bool(device_noise), future=Future(), mixed=self.mixed_batches or None, solver=solver,
                      control_preprocess=control_preprocess, control_thresholds=thresholds)
@@ -226,7 +236,7 @@ class PromptFreeServer:
         with DEVICE_LOCK:
             if float(r0.eta) != 0.0 and not r0.device_noise:   # runs alone (shareable()): its noise stream is a function
                 torch.manual_seed(r0.seed)                      # of ITS seed only
-            conds, xts, unconds, keys = [], [], [], []
+            conds, xts, unconds, keys, masks, x0s = [], [], [], [], [], []
             for r in batch:
                 img = self.pipe.ingest(r.image) if image_io.wants_ingest(r.image) else r.image.to(dev)
                 c, z = self.pipe.encode_reference(img, r.n)
@@ -235,8 +245,13 @@ class PromptFreeServer:
                 keys.append(shard_noise_keys(r.n, r.seed, 0, 1))                # each request keeps ITS noise keys (seed, j)
                 if r.init is None:
                     xts.append(shard_xT(r.n, r.height, r.width, r.seed, 0, 1))  # ... and ITS x_T stream
-                else:                                                           # ... or ITS picture, noised under ITS keys
+                elif r.mask is None:                                            # ... or ITS picture, noised under ITS keys
                     xts.append(self.pipe.init_latent(r.init, r.height, r.width, r.steps, r.strength, keys[-1])[0])
+                else:                                                           # ... and ITS mask over ITS clean latent
+                    x_t, _, x0 = self.pipe.init_latent(r.init, r.height, r.width, r.steps, r.strength, keys[-1], want_x0=True)
+                    xts.append(x_t)
+                    x0s.append(x0)
+                    masks.append(self.pipe.mask_grid(r.mask, r.height, r.width)[:1].expand(r.n, -1, -1))
             cond, uncond, xT = torch.cat(conds), torch.cat(unconds), torch.cat(xts).to(dev)
             c_info = {'type': 'image', 'conditioning': cond, 'unconditional_conditioning': uncond,
                       'unconditional_guidance_scale': r0.scale}
@@ -256,6 +271,8 @@ class PromptFreeServer:
                 x_info['xt_steps'] = r0.init_k       # equal over the batch: part of the key
             if r0.device_noise:
                 x_info['noise_key'] = torch.cat(keys).to(dev)
+            if r0.mask is not None:                  # masks stacked to [B, h, w]: one per sample
+                x_info.update(mask=torch.cat(masks).contiguous(), x0_keep=torch.cat(x0s), keep_key=torch.cat(keys).to(dev))
             how = {} if r0.solver in (None, 'ddim') else {'solver': r0.solver}
             x, _ = self.pipe.sampler.sample(steps=r0.steps, shape=list(xT.shape), x_info=x_info, c_info=c_info,
                                             eta=r0.eta, verbose=False, **how)
@@ -263,6 +280,9 @@ class PromptFreeServer:
             self.batches.append(int(xT.shape[0]))
         outs, off = [], 0
         for r in batch:
-            outs.append(img[off:off + r.n])
+            o = img[off:off + r.n]
+            if r.composite:                          # each request with its own picture and mask
+                o = self.pipe.composite(o.contiguous(), r.init, r.mask, r.height, r.width)
+            outs.append(o)
             off += r.n
         return outs
