@@ -11,7 +11,9 @@ step index `step` is output word e & 3 -> normal of
 
 `stream` is 0 for the step noise (the word was always 0: those draws are what they were), 1 for the forward-noising
 noise and 2 for the posterior noise of an img2img start (lib/img2img.py, csrc/latent.hip), both at step 0, and 3 for the
-noise the kept region of a masked step is re-noised with (lib/inpaint.py, csrc/inpaint.hip), at that step's index;
+noise the kept region of a masked step is re-noised with (lib/inpaint.py, csrc/inpaint.hip), at that step's index, and 4
+for the noise the enlarged latent of a two-pass request is re-noised with (lib/hires.py; host only so far), at step 0 and
+indexed by the element of the enlarged latent;
 
 with words (r0, r1) -> (z0, z1) and (r2, r3) -> (z2, z3) by Box-Muller:
 
@@ -53,6 +55,7 @@ def key_words(seed):
 
 STREAM_STEP, STREAM_Q, STREAM_POSTERIOR = 0, 1, 2
 STREAM_KEEP = 3
+STREAM_HIRES = 4
 
 
 def normal(seed, sample_id, step, n, stream=0):
