@@ -280,6 +280,27 @@ typedef struct PfdAttnDesc {
 int pfd_attention_f16(const PfdAttnDesc* d, pfd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * The same attention with an additive logit per key (several reference pictures mixed in one
+ * UNet pass, lib/refmix.py; -inf masks a key, so samples with different numbers of references
+ * share a batch):
+ *   O[b,i,h,:] = sum_j w[b,j] exp(s_ij) V[b,j,h,:] / sum_j w[b,j] exp(s_ij),   w = 2^kbias,
+ *   s_ij = scale * <Q[b,i,h,:], K[b,j,h,:]>
+ * This is NOT the reference's `context_mixing` (pfd.py:366-386, a weighted sum of whole
+ * transformer outputs; lib ContextMix) and is not compared with it numerically.
+ *   kbias[b*kb_bs + j], j < Nk: fp32, in log2 units; it is added to scale * log2(e) * <q, k>
+ *     BEFORE the running maximum is taken.  Values are finite or -inf.
+ *   kbias[b*kb_bs + 0] must be finite (it keeps the maximum of the first key tile finite).
+ *   K and V of a -inf key must be finite (the host zero-pads them): 0 x NaN is not masked
+ *     inside Nk.
+ *   kb_bs % 4 == 0, kb_bs >= Nk, kbias 16-byte aligned; elements j >= Nk of a row are never read.
+ *   scale > 0.  An all-zero kbias gives the bits of pfd_attention_f16 wherever that launches the
+ *     same kernel (it hands some d = 40 shapes to a kernel without this operand).
+ *   D in {40, 80, 160}; other head sizes answer PFD_ESHAPE.  kbias == NULL answers PFD_EINVAL,
+ *   as does everything pfd_attention_f16 answers it for.  PfdAttnDesc is unchanged.
+ * ---------------------------------------------------------------------------------- */
+int pfd_attention_kbias_f16(const PfdAttnDesc* d, const float* kbias, int64_t kb_bs, pfd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Swin (shifted-)window attention core for one image: pad to multiples of `ws`, cyclic
  * roll by -shift, window partition, q*scale, QK^T + relative-position bias + shift mask
  * (-100, not -inf), softmax, .V, window reverse, roll back, crop -- all as index math.

@@ -15,6 +15,19 @@ struct AttnParams {
   float scale_log2;
 };
 
+// pfd_attention_kbias_f16: the same block followed by the per-key logits (fp32, log2 units; element (b, j) at kbias[b * kb_bs + j]).
+// A type of its own, so that the argument block -- and with it the code -- of the kernels without the operand stays what it is.
+struct AttnParamsKB : AttnParams {
+  const float* kbias;
+  long kb_bs;
+  float inv_scale_log2;   // 1 / scale_log2: the unfolded builds stage kbias / (scale log2 e), the units of their raw scores
+};
+// (the kernel text is compiled for both blocks: what only the second one has is read through these)
+__device__ __forceinline__ const float* attn_kbias_row(const AttnParams&, int) { return nullptr; }
+__device__ __forceinline__ const float* attn_kbias_row(const AttnParamsKB& p, int b) { return p.kbias + (long)b * p.kb_bs; }
+__device__ __forceinline__ float attn_inv_scale_log2(const AttnParams&) { return 0.f; }
+__device__ __forceinline__ float attn_inv_scale_log2(const AttnParamsKB& p) { return p.inv_scale_log2; }
+
 // attention3.hip: the software-pipelined d = 40 kernel (64 queries per wave); `takes` = shapes it is built for
 bool pfd_attention3_takes(const AttnParams& p);
 void pfd_attention3_launch(const AttnParams& p, hipStream_t s);

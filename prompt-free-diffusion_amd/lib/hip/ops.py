@@ -537,12 +537,44 @@ def conv_narrow(x, w, ksize, *, stride=1, pad=None, bias=None, rowvec=None, res=
 # ----------------------------------------------------------------------------------------------
 # attention
 # ----------------------------------------------------------------------------------------------
-def attention(q, k, vt, B, H, Nq, Nk, D, scale, *, ldq, ldk, ldvt, q_bs, k_bs, vt_bs, out=None):
+def _chk_kbias(kbias, kb_bs, B, Nk, device):
+    """the key-logit operand of pfd_attention_kbias_f16: fp32 on `device`, dense, 16-byte aligned, rows of kb_bs % 4 == 0
+    elements of which the first Nk are read.  -> kb_bs"""
+    if not isinstance(kbias, torch.Tensor) or kbias.dtype != torch.float32:
+        raise TypeError(f"attention kbias: expected a float32 tensor, got {getattr(kbias, 'dtype', type(kbias).__name__)}")
+    if not kbias.is_cuda:
+        raise RuntimeError("attention kbias: tensor on the CPU (no CPU fallback)")
+    if kbias.device != device:
+        raise ValueError(f"attention kbias: on {kbias.device}, the operands are on {device}")
+    if not kbias.is_contiguous():
+        raise ValueError("attention kbias: must be contiguous")
+    if kb_bs is None:
+        if kbias.dim() != 2:
+            raise ValueError("attention kbias: kb_bs is needed unless kbias is a [B, kb_bs] matrix")
+        kb_bs = kbias.shape[1]
+    kb_bs = int(kb_bs)
+    if kb_bs % 4 or kb_bs < Nk:
+        raise ValueError(f"attention kbias: kb_bs {kb_bs} must be a multiple of 4 and at least Nk = {Nk}")
+    if kbias.numel() < (B - 1) * kb_bs + Nk:
+        raise ValueError(f"attention kbias: {kbias.numel()} elements, {B} rows of stride {kb_bs} with {Nk} keys need "
+                         f"{(B - 1) * kb_bs + Nk}")
+    if kbias.data_ptr() % 16:
+        raise ValueError("attention kbias: must start on a 16-byte boundary")
+    return kb_bs
+
+
+def attention(q, k, vt, B, H, Nq, Nk, D, scale, *, ldq, ldk, ldvt, q_bs, k_bs, vt_bs, out=None, kbias=None, kb_bs=None):
     """Fused attention; see pfd_attention_f16.  q/k/vt may be views into wider buffers; out (optional): [>= B*Nq, >= H*D]
-    rows of stride % 8 == 0 (a column slice of a wider matrix is fine), the first B*Nq rows and H*D columns are written."""
+    rows of stride % 8 == 0 (a column slice of a wider matrix is fine), the first B*Nq rows and H*D columns are written.
+    kbias (optional): fp32 per-key logits in log2 units, element (b, j) at kbias.view(-1)[b * kb_bs + j] (kb_bs defaults to the
+    row length of a [B, kb_bs] matrix); see pfd_attention_kbias_f16.  None is the plain entry point, exactly."""
     _chk16(q, "attention q")
     _chk16(k, "attention k")
     _chk16(vt, "attention vt")
+    if kbias is not None:
+        kb_bs = _chk_kbias(kbias, kb_bs, B, Nk, q.device)
+    elif kb_bs is not None:
+        raise ValueError("attention: kb_bs without kbias")
     if out is None:
         out = torch.empty((B * Nq, H * D), dtype=torch.float16, device=q.device)
     else:
@@ -556,6 +588,10 @@ def attention(q, k, vt, B, H, Nq, Nk, D, scale, *, ldq, ldk, ldvt, q_bs, k_bs, v
     d.q_bs, d.k_bs, d.vt_bs, d.o_bs = q_bs, k_bs, vt_bs, Nq * out.stride(-2)
     d.B, d.H, d.Nq, d.Nk, d.D = B, H, Nq, Nk, D
     d.scale = scale
+    if kbias is not None:
+        _b.check(_lib().pfd_attention_kbias_f16(_byref(d), kbias.data_ptr(), kb_bs, _stream()),
+                 f"pfd_attention_kbias_f16 B{B} H{H} Nq{Nq} Nk{Nk} D{D}")
+        return out
     _b.check(_lib().pfd_attention_f16(_byref(d), _stream()), f"pfd_attention_f16 B{B} H{H} Nq{Nq} Nk{Nk} D{D}")
     return out
 

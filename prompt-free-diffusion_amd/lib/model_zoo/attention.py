@@ -40,13 +40,22 @@ class ContextKV:
     CrossAttention layer that consumes `context` [B, Nk, Cctx], K = to_k(context) and
     V^T = to_v(context)^T are computed once (SURVEY §8a saving (ii)) instead of once per DDIM
     step.  Context rows are zero-padded to a multiple of 8 tokens so every V^T row is 16-byte
-    aligned (pfd_attention_f16 contract)."""
+    aligned (pfd_attention_f16 contract).
+    bias (optional): fp32 [B, Nk] per-key logits in log2 units (lib/refmix.key_bias: several references mixed in one pass,
+    -inf on keys that are padding); kept as [B, Nkp] with -inf next to the zero context rows and passed to every
+    cross-attention (pfd_attention_kbias_f16).  Key 0 of every sample must be finite, the context rows of -inf keys too."""
 
-    def __init__(self, context):
+    def __init__(self, context, bias=None):
         L._require_gpu(context, "HIP path: context must be on the GPU (no CPU fallback)")
         B, Nk, Cd = context.shape
         self.B, self.Nk, self.Cd = B, Nk, Cd
         self.Nkp = (Nk + 7) // 8 * 8
+        self.bias = None
+        if bias is not None:
+            if not torch.is_tensor(bias) or tuple(bias.shape) != (B, Nk) or not bias.is_floating_point():
+                raise ValueError(f"ContextKV: bias must be a float tensor [{B}, {Nk}], one logit per key")
+            self.bias = torch.full((B, self.Nkp), float('-inf'), dtype=torch.float32, device=context.device)
+            self.bias[:, :Nk] = bias.to(device=context.device, dtype=torch.float32)
         ctx = torch.zeros((B, self.Nkp, Cd), dtype=torch.float16, device=context.device)
         ctx[:, :Nk] = context.to(torch.float16)
         self.ctx2d = ctx.view(B * self.Nkp, Cd)
@@ -83,6 +92,8 @@ class ContextMix:
 
     def mix(self, modules, h, emb):
         assert len(modules) == len(self.contexts)
+        if any(getattr(c, 'bias', None) is not None for c in self.contexts):
+            raise ValueError("ContextMix takes no per-key bias: it mixes transformer outputs, not keys")
         if self.mixing_type == 'layer':
             ni = npr.choice(len(modules), p=self.ratios)
             return modules[ni].hip(h, emb, self.contexts[ni])
@@ -93,14 +104,18 @@ class ContextMix:
         return out
 
 
-def as_context_kv(context):
+def as_context_kv(context, bias=None):
     if isinstance(context, ContextMix):
+        if bias is not None:
+            raise ValueError("ContextMix takes no per-key bias")
         return context
     if context is None or isinstance(context, ContextKV):
+        if bias is not None:
+            raise ValueError("a per-key bias goes with a context tensor, not with a prepared context")
         return context
     if isinstance(context, (list, tuple)):
         context = context[0]
-    return ContextKV(context)
+    return ContextKV(context, bias)
 
 
 class GEGLU(nn.Module, L._Packed):
@@ -250,6 +265,9 @@ class CrossAttention(nn.Module, L._Packed):
                 raise ValueError("CrossAttention.hip(single=True) needs the zero-context shortcut on half the batch, a residual, "
                                  "statistics and the wide-tile out-projection (SpatialTransformer.hip checks before it asks)")
             k, vt = context.get(self)
+            # per-key logits (several references in one pass): sliced [z:] like K; the zero-context shortcut stays what it
+            # is -- with K = V = 0 the weights of those samples cannot matter
+            kb = {} if context.bias is None else dict(kbias=context.bias[z:], kb_bs=context.Nkp)
             if single:
                 w_o, b_o = self.to_out[0]._pk()
                 out = torch.empty((B * N, res.shape[1]), dtype=torch.float16, device=res.device)
@@ -257,7 +275,7 @@ class CrossAttention(nn.Module, L._Packed):
                 q = self.to_q.hip(x, ln=ln)                       # the one copy = the conditional half
                 o = ops.attention(q, k[z * context.Nkp:], vt[:, z * context.Nkp:], B - z, H, N, context.Nk, D,
                                   self.scale, ldq=Cd, ldk=Cd, ldvt=B * context.Nkp, q_bs=N * Cd,
-                                  k_bs=context.Nkp * Cd, vt_bs=context.Nkp)
+                                  k_bs=context.Nkp * Cd, vt_bs=context.Nkp, **kb)
                 ops.gemm(o, w_o, bias=b_o, res=res, out=out, zero_rows=z * N, ln_out=st_o, res_rows=z * N)
                 return out, st_o
             if 0 < z < B and res is not None:
@@ -271,7 +289,7 @@ class CrossAttention(nn.Module, L._Packed):
                 q = self.to_q.hip(x[z * N:], ln=None if ln is None else (ln[0], ln[1][z * N:]))
                 o = ops.attention(q, k[z * context.Nkp:], vt[:, z * context.Nkp:], Bc, H, N, context.Nk, D,
                                   self.scale, ldq=Cd, ldk=Cd, ldvt=B * context.Nkp, q_bs=N * Cd,
-                                  k_bs=context.Nkp * Cd, vt_bs=context.Nkp)
+                                  k_bs=context.Nkp * Cd, vt_bs=context.Nkp, **kb)
                 if ops.wide_tile_ok(w_o.shape[0], Cd):
                     # ONE out-projection launch for the whole batch: the zero-context rows are `zero_rows` of the
                     # operand (their tiles skip the K loop: bias + residual, statistics from the same store pass)
@@ -285,7 +303,7 @@ class CrossAttention(nn.Module, L._Packed):
                 return out
             q = self.to_q.hip(x, ln=ln)
             o = ops.attention(q, k, vt, B, H, N, context.Nk, D, self.scale, ldq=Cd, ldk=Cd,
-                              ldvt=B * context.Nkp, q_bs=N * Cd, k_bs=context.Nkp * Cd, vt_bs=context.Nkp)
+                              ldvt=B * context.Nkp, q_bs=N * Cd, k_bs=context.Nkp * Cd, vt_bs=context.Nkp, **kb)
         return self.to_out[0].hip(o, res=res, ln_out=True if stats_out else None)
 
     def forward(self, x, context=None, mask=None):

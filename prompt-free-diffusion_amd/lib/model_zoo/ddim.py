@@ -53,6 +53,14 @@ to keep_key (the kernel draws the step noise from the same rows): the masked ker
 generator.  The loop is captured like any keyed loop, the three tensors being static inputs behind the other five, and the
 graph key gains a trailing element.  The multi-context loop and the single-step entry points refuse a mask.  Without a
 mask every path, launch sequence and graph key is what it was.
+
+Several references in one pass (opt-in): c_info['key_bias'] and / or c_info['unconditional_key_bias'], fp32 [bs, Nk], one
+logit per context token in log2 units (lib/refmix.key_bias; -inf on padding tokens, whose context rows are zero).  A missing
+one of the pair is all zeros; they are concatenated like the contexts and every cross-attention of the UNet and of the
+ControlNet attends with them (pfd_attention_kbias_f16).  Every solver, seeded noise, per-sample scale, img2img start and mask.
+The bias is one more static graph input behind the others and the graph key gains a trailing element.  This is not the
+reference's context_mixing: the multi-context loop stays what it is and refuses a bias.  Without a bias every path, launch
+sequence and graph key is what it was.
 """
 import numpy as np
 import torch
@@ -138,6 +146,32 @@ def _guidance(c_info, bs, device):
         scale = 1.0
     cfg = sps is not None or not ((scale == 1.) or (uc is None))
     return sps, scale, uc, cfg, (2 if cfg else 1)
+
+
+_BIAS_KEYS = ('key_bias', 'unconditional_key_bias')
+
+
+def _refuse_bias(c_infos, what):
+    if any(ci.get(k, None) is not None for ci in c_infos for k in _BIAS_KEYS):
+        raise ValueError(f"{what} takes no c_info['key_bias']: per-key weights go with sample / ddim_sampling / p_sample_ddim")
+
+
+def _key_bias(c_info, cond, cfg, device):
+    """-> None, or the fp32 [nb * bs, Nk] logits next to c_in (unconditional rows first): c_info['key_bias'] /
+    ['unconditional_key_bias'], a missing one all zeros"""
+    kb, ukb = (c_info.get(k, None) for k in _BIAS_KEYS)
+    if kb is None and ukb is None:
+        return None
+    want = tuple(cond.shape[:2])
+
+    def rows(t, name):
+        if t is None:
+            return torch.zeros(want, dtype=torch.float32, device=device)
+        if not torch.is_tensor(t) or tuple(t.shape) != want or not t.is_floating_point():
+            raise ValueError(f"c_info[{name!r}] must be a float tensor {list(want)}, one logit per context token")
+        return t.to(device=device, dtype=torch.float32)
+    kb = rows(kb, 'key_bias')
+    return (torch.cat([rows(ukb, 'unconditional_key_bias'), kb]) if cfg else kb).contiguous()
 
 
 def _draw_noise(x, temperature, noise_dropout, repeat_noise=False):
@@ -264,6 +298,7 @@ class DDIMSampler(object):
             uc = uc.expand(cond.shape[0], -1, -1)
         c_in = torch.cat([uc, cond]) if cfg else cond   # uncond first, like ddim.py:147
         c_info['c'] = c_in
+        kbias = _key_bias(c_info, cond, cfg, device)
         # all-zero unconditional context (SeeCoder / SeeCoder-PA, app.py:236): its cross-attention is
         # exactly `x + to_out.bias`; one host sync per request decides
         zero_lead = bs if (cfg and self.zero_uncond_shortcut and not bool(uc.any())) else 0
@@ -291,10 +326,10 @@ class DDIMSampler(object):
             """the whole trajectory as a pure function of device tensors (capturable as one hipGraph), and its timestep table"""
             t_table = t_col.repeat(1, nb * bs)
 
-            def run_loop(x, c_in, hint, nkey, sps, mask=None, x0_keep=None, kkey=None):
+            def run_loop(x, c_in, hint, nkey, sps, mask=None, x0_keep=None, kkey=None, kbias=None):
                 from .controlnet import PreparedHint
                 ps = {} if sps is None else {'scale': sps}
-                ctx = model.prepare_context(c_in)
+                ctx = model.prepare_context(c_in) if kbias is None else model.prepare_context(c_in, kbias)
                 ctx.zero_lead = zero_lead
                 ctl = PreparedHint(hint) if hint is not None else None
                 # every ResBlock's time-embedding projection for ALL steps in one GEMM (t is the same for
@@ -340,8 +375,10 @@ class DDIMSampler(object):
             return run_loop, t_table
 
         inputs = (x, c_in, hint, nkey, sps)
-        if mask is not None:
+        if mask is not None or kbias is not None:
             inputs = inputs + (mask, x0_keep, kkey)
+        if kbias is not None:
+            inputs = inputs + (kbias,)
         # a keyed schedule draws nothing from a generator: capturable whatever eta is
         if self.use_graph and (not stochastic or nkey is not None) and callback is None and x.is_cuda:
             # one hipGraph per (shape, schedule, weights version, flags); static input buffers, replayed per request.
@@ -355,6 +392,8 @@ class DDIMSampler(object):
                 key = key + (solver,)          # the DDIM key is what it was
             if mask is not None:
                 key = key + (('mask', tuple(mask.shape)),)     # ... and so is every key without a mask
+            if kbias is not None:
+                key = key + ('key_bias',)                      # ... and without a bias
             xf, ixt, ix0 = self._graph_for(key, lambda: self._capture(*make_loop(), inputs, coef)).replay(inputs)
         else:
             xf, ixt, ix0 = make_loop()[0](*inputs)
@@ -407,6 +446,7 @@ class DDIMSampler(object):
         if _solver.solver_order(solver) is not None:
             raise ValueError(f"solver {solver!r} is not available for multi-context sampling: use 'ddim'")
         _refuse_mask(x_info, "sample_multicontext")
+        _refuse_bias(c_info_list, "sample_multicontext")
         self.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=verbose)
         if verbose:
             print(f'Data shape for DDIM sampling is {shape}, eta {eta}')
@@ -419,6 +459,7 @@ class DDIMSampler(object):
         first) and hoist its K / V^T; -> (ContextMix, scale, nb)"""
         model = self.model
         scale = None
+        _refuse_bias(c_info_list, "multi-context sampling")
         for ci in c_info_list:
             if is_per_sample(ci['unconditional_guidance_scale']):
                 raise ValueError("a per-sample guidance scale is out of scope for multi-context sampling: give one "
@@ -550,7 +591,8 @@ class DDIMSampler(object):
         c_info['c'] = c_in
         if cfg:
             x_info['x'] = torch.cat([x] * 2)
-        ctx = self.model.prepare_context(c_in)
+        kbias = _key_bias(c_info, c_info['conditioning'], cfg, x.device)
+        ctx = self.model.prepare_context(c_in) if kbias is None else self.model.prepare_context(c_in, kbias)
         xf = x.to(torch.float32).contiguous()
         eps = self.model.apply_model_nhwc(x_info['type'], ops.to_nhwc(xf, rep=nb), t_in, c_info['type'], ctx,
                                           control=c_info.get('control', None))

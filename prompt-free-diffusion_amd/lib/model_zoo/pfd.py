@@ -156,10 +156,11 @@ class PromptFreeDiffusion(nn.Module):
 
     ctx_encode_trainable = ctx_encode
 
-    def prepare_context(self, c):
+    def prepare_context(self, c, bias=None):
         """Wrap a context tensor so the 16 cross-attention K/V^T projections are computed once per
-        request instead of once per step; `apply_model` accepts either form in c_info['c']."""
-        return as_context_kv(c)
+        request instead of once per step; `apply_model` accepts either form in c_info['c'].
+        bias: fp32 [B, Nk] per-key logits (lib/refmix.py), or None."""
+        return as_context_kv(c, bias)
 
     def _control_residuals(self, x_nhwc, timesteps, context, control, cfg_pair=False):
         return None

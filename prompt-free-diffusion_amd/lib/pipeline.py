@@ -17,6 +17,7 @@ import os
 import torch
 
 from . import image_io
+from . import refmix
 from .hip import ops
 from .hip.ops import serialised
 
@@ -181,6 +182,28 @@ def max_over_ranks(seconds, world_size, device='cpu'):
     return float(t.item())
 
 
+def check_references(image, image_weights):
+    """the reference argument(s) of a request, checked on the host.  -> None for a plain request (one picture, no weights),
+    else (references kept, their weights): references of weight 0 are dropped here, before anything is encoded.  One
+    reference left = the plain request of that picture (the caller passes no bias then).
+    image: a list / tuple of references, each a uint8 HWC picture of any size (at least 32 a side) or a float [1, 3, h, w]
+    tensor; image_weights: one finite number >= 0 per reference, not all 0; at most refmix.MAX_REFS references."""
+    listed = isinstance(image, (list, tuple))
+    if image_weights is None and not listed:
+        return None
+    if image_weights is None or not listed:
+        raise ValueError("several references are given as image=[ref0, ref1, ...] together with image_weights=[w0, w1, ...]")
+    if len(image) != len(image_weights):
+        raise ValueError(f"{len(image)} reference pictures but {len(image_weights)} image_weights")
+    keep, w = refmix.drop_zero_weights(image_weights)
+    for i, ref in enumerate(image):
+        if image_io.wants_ingest(ref):
+            image_io.check_u8_picture(ref, f'image[{i}]', min_side=32)
+        elif not (ref.dim() == 4 and ref.shape[0] == 1 and ref.shape[1] == 3 and ref.is_floating_point()):
+            raise ValueError(f"image[{i}] must be a float tensor [1, 3, h, w] in [0, 1] or a uint8 picture [h, w, 3]")
+    return [image[i] for i in keep], w
+
+
 class PromptFreePipeline:
     """One rank's view of a (possibly multi-GPU) request: shard -> encode -> DDIM loop -> decode -> gather.
     `sampler` is injectable (the gloo CPU tests drive this very code with a stand-in for the GPU compute)."""
@@ -212,6 +235,49 @@ class PromptFreePipeline:
         c = self._ctx_stage(image) if self._ctx_stage is not None else self.net.ctx_encode(image, 'image')
         cond = c.repeat(n, 1, 1)
         return cond, torch.zeros_like(cond)
+
+    @serialised
+    @torch.no_grad()
+    def encode_references(self, images, weights, n):
+        """several references mixed in one UNet pass (lib/refmix.py): images, a list of uint8 HWC pictures / float [1,3,H,W]
+        tensors, with one weight > 0 each -> (cond [n, R*Nk, C], zeros like it, bias fp32 [n, R*Nk]).  SeeCoder runs once
+        per reference (through the graphed stage when graphs are on), the tokens are concatenated and every token carries
+        log2(w_r / max w) (refmix.key_bias).  Not the reference's context_mixing."""
+        w = refmix.check_weights(weights)
+        if len(images) != w.size:
+            raise ValueError(f"{len(images)} references but {w.size} weights")
+        dev = self.net.device
+        toks = []
+        for ref in images:
+            img = self.ingest(ref) if image_io.wants_ingest(ref) else ref.to(dev)
+            toks.append(self._ctx_stage(img) if self._ctx_stage is not None else self.net.ctx_encode(img, 'image'))
+        nk = int(toks[0].shape[1])
+        cond = torch.cat(toks, 1).repeat(n, 1, 1)
+        bias = torch.from_numpy(refmix.key_bias(w, nk, len(toks) * nk)).to(dev)[None].repeat(n, 1)
+        return cond, torch.zeros_like(cond), bias
+
+    @staticmethod
+    def pad_context(ctx, bias, nk):
+        """a context [n, Nc, C] and its logits [n, Nc] padded to nk tokens: zero tokens at -inf"""
+        nc = int(ctx.shape[1])
+        if nc == nk:
+            return ctx, bias
+        pad = torch.zeros((ctx.shape[0], nk - nc, ctx.shape[2]), dtype=ctx.dtype, device=ctx.device)
+        pb = torch.full((bias.shape[0], nk - nc), float('-inf'), dtype=bias.dtype, device=bias.device)
+        return torch.cat([ctx, pad], 1), torch.cat([bias, pb], 1)
+
+    @staticmethod
+    def pad_uncond(uncond, bias_like):
+        """an unconditional context [*, Nu, C] with fewer tokens than the mix [*, Nk]: zero tokens behind it and the logits
+        of its rows, 0 on its own tokens and -inf on the padding -> (uncond [*, Nk, C], fp32 [*, Nk])"""
+        nu, nk = int(uncond.shape[1]), int(bias_like.shape[1])
+        if nu > nk:
+            raise ValueError(f"uncond has {nu} tokens, the mixed context {nk}: an unconditional context longer than the mix "
+                             "is not served")
+        pad = torch.zeros((uncond.shape[0], nk - nu, uncond.shape[2]), dtype=uncond.dtype, device=uncond.device)
+        ub = torch.zeros((uncond.shape[0], nk), dtype=torch.float32, device=uncond.device)
+        ub[:, nu:] = float('-inf')
+        return torch.cat([uncond, pad], 1), ub
 
     @serialised
     @torch.no_grad()
@@ -321,7 +387,7 @@ class PromptFreePipeline:
     def generate(self, image, n_global, height, width, steps=50, scale=2.0, eta=0.0, seed=20, control=None,
                  uncond=None, decode=True, gather=False, verbose=False, timings=None, as_uint8=False,
                  device_noise=False, solver='ddim', control_preprocess=None, control_thresholds=(100, 200), init=None,
-                 strength=0.75, init_posterior='sample', mask=None, composite=False):
+                 strength=0.75, init_posterior='sample', mask=None, composite=False, image_weights=None):
         """returns (images, latents [n_local,4,h,w]); images = [n_local | n_global (gather), 3, H, W] in [0,1]
         in the model dtype, or -- as_uint8 -- packed uint8 [n, H, W, 3] (the bytes ToPILImage would produce,
         app.py:273-275; 4x fewer bytes through the all-gather); decode=False returns the latents twice.
@@ -351,13 +417,23 @@ class PromptFreePipeline:
         like the start: no generator, the result does not depend on the world size, the loop replays as a hipGraph.  The
         final latent outside the mask is the picture's clean latent itself.  eta > 0 needs device_noise.  composite (needs
         as_uint8, a uint8 init and a uint8 mask): the pixels outside the mask are the init picture's bytes (`composite`),
-        before the gather."""
+        before the gather.
+        image_weights: several references mixed in ONE UNet pass -- image=[ref0, ref1, ...] (each a uint8 HWC picture of any
+        size or a float [1,3,H,W] tensor, shared by all samples) with one number >= 0 per reference: every cross-attention
+        attends over the union of the references' tokens, each key weighted by its reference's weight (lib/refmix.py,
+        `encode_references`; pfd_attention_kbias_f16).  Only the ratios matter.  A reference of weight 0 is dropped before it
+        is encoded; with one reference left the request IS the plain request of that picture.  An `uncond` with fewer tokens
+        than the mix is padded with zero tokens that carry weight 0.  Works with every other argument; draws nothing, so the
+        result does not depend on the world size.  Not the reference's context_mixing (sample_multicontext)."""
         from .model_zoo.ddim import is_per_sample
         from .solver import solver_order
         if solver_order(solver) is not None and (eta != 0. or device_noise):     # an unknown name raises here too
             raise ValueError(f"solver {solver!r} is deterministic: eta must be 0 and device_noise off")
         P, r = self.world_size, self.rank
         dev = self.net.device
+        refs = check_references(image, image_weights)     # checked before anything touches the device
+        if refs is not None and len(refs[0]) == 1:
+            image, refs = refs[0][0], None                # one reference left: the plain request
         if is_per_sample(scale):     # checked before anything touches the device
             if tuple(torch.as_tensor(scale).shape) != (n_global,):
                 raise ValueError(f"scale must be one number or {n_global} numbers, one per sample of the global batch")
@@ -365,7 +441,8 @@ class PromptFreePipeline:
         if torch.is_tensor(control) and control.dim() == 4 and control.shape[0] not in (1, n_global // P):
             raise ValueError(f"control must be [1, 3, H, W] (shared) or [{n_global // P}, 3, H, W] (one hint per local "
                              f"sample): got {control.shape[0]} hints")
-        u8_image, u8_control = image_io.wants_ingest(image), control is not None and image_io.wants_ingest(control)
+        u8_image = refs is None and image_io.wants_ingest(image)
+        u8_control = control is not None and image_io.wants_ingest(control)
         if u8_image:                 # checked before anything touches the device
             image_io.check_u8_picture(image, 'image', min_side=32)
         if u8_control:
@@ -386,9 +463,12 @@ class PromptFreePipeline:
             mk.mark()
         xT = shard_xT(n_global, height, width, seed, r, P) if init is None else None
         n = xT.shape[0] if init is None else n_global // P
+        kbias = None
         if u8_image:
             image = self.ingest(image)
-        if image.shape[0] > 1:
+        if refs is not None:
+            cond, zeros, kbias = self.encode_references(refs[0], refs[1], n)
+        elif image.shape[0] > 1:
             # one reference image PER SAMPLE (the "+737 GFLOP/img" variant): SeeCoder is run once per image
             # (its decoder MHA attends across the batch axis, seecoder.py:70,83 -- a batch of images would mix them)
             if image.shape[0] != n:
@@ -397,8 +477,13 @@ class PromptFreePipeline:
             cond, zeros = torch.cat([c for c, _ in pairs]), torch.cat([z for _, z in pairs])
         else:
             cond, zeros = self.encode_reference(image.to(dev), n)
+        ukb = None
         if uncond is None:
             uncond = zeros
+        elif kbias is not None and uncond.shape[1] != cond.shape[1]:
+            uncond, ukb = self.pad_uncond(uncond.to(dev).to(cond.dtype), kbias)
+            if uncond.shape[0] == 1 and n > 1:
+                uncond, ukb = uncond.expand(n, -1, -1), ukb.expand(n, -1)
         if mk:
             mk.mark()
         if init is None:
@@ -420,6 +505,10 @@ class PromptFreePipeline:
             x_info['noise_key'] = shard_noise_keys(n_global, seed, r, P).to(dev)
         c_info = {'type': 'image', 'conditioning': cond, 'unconditional_conditioning': uncond,
                   'unconditional_guidance_scale': scale}
+        if kbias is not None:
+            c_info['key_bias'] = kbias
+            if ukb is not None:
+                c_info['unconditional_key_bias'] = ukb
         if control is not None:
             c_info['control'] = self.control_hint(control, height, width, control_preprocess, control_thresholds)
         how = {} if solver == 'ddim' else {'solver': solver}     # the default call is what it was

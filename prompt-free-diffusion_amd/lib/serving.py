@@ -27,14 +27,14 @@ from concurrent.futures import Future
 import torch
 
 from . import image_io
-from .pipeline import PromptFreePipeline, shard_noise_keys, shard_xT
+from .pipeline import PromptFreePipeline, check_references, shard_noise_keys, shard_xT
 from .solver import solver_order
 
 
 class _Request:
     __slots__ = ("image", "n", "height", "width", "steps", "scale", "eta", "seed", "control", "uncond", "as_uint8",
                  "device_noise", "future", "mixed", "solver", "control_preprocess", "control_thresholds", "init", "strength",
-                 "init_k", "mask", "composite")
+                 "init_k", "mask", "composite", "weights")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -47,6 +47,8 @@ class _Request:
             how = how + (('init', int(self.init_k)),)
         if self.mask is not None:     # inpainting: masked requests share batches with each other only; every other key is unchanged
             how = how + (('mask', bool(self.composite)),)
+        if self.weights is not None:  # several references: with each other only, whatever their number; every other key is unchanged
+            how = how + ('refmix',)
         if self.mixed:
             return (self.height, self.width, self.steps, float(self.scale) == 1.0, float(self.eta),
                     self.control is None, self.uncond is None, bool(self.as_uint8), bool(self.device_noise)) + how
@@ -80,7 +82,7 @@ class PromptFreeServer:
     # ---- client side (any thread) -------------------------------------------------------------------
     def submit(self, image, n_samples=1, height=512, width=512, steps=50, scale=2.0, eta=0.0, seed=20,
                control=None, uncond=None, as_uint8=True, device_noise=False, solver='ddim', control_preprocess=None,
-               control_thresholds=(100, 200), init=None, strength=0.75, mask=None, composite=False):
+               control_thresholds=(100, 200), init=None, strength=0.75, mask=None, composite=False, image_weights=None):
         """image [1,3,h,w] in [0,1] (any size); control [1,3,H,W] or None; uncond [1,148,768] or None (zeros).
         image and control may each be a uint8 HWC picture [h,w,3] (torch or numpy, any size; the reference picture
         at least 32 a side) instead: the request carries the bytes and the worker converts them on the device
@@ -102,6 +104,11 @@ class PromptFreeServer:
         requests of equal k share a batch with each other, each with its own picture, mask and keys; never with unmasked
         ones.  eta > 0 needs device_noise.  composite (needs as_uint8, a uint8 init and a uint8 mask): the pixels outside
         the mask are the init picture's bytes.
+        image_weights: several references mixed in one UNet pass (PromptFreePipeline.generate, lib/refmix.py) --
+        image=[ref0, ref1, ...] with one number >= 0 per reference.  Such requests share a batch with each other (equal in
+        the other key fields) whatever their numbers of references: contexts are padded to the longest of the batch with
+        zero tokens of weight 0, each sample with its own row of logits.  A request without image_weights never shares a
+        batch with one that has them.  One reference left after dropping zero weights is the plain request.
         -> Future of uint8 [n,H,W,3] (as_uint8) or float [n,3,H,W] images"""
         if self._stop:
             raise RuntimeError("server is closed")
@@ -115,7 +122,16 @@ class PromptFreeServer:
             raise ValueError("steps must be >= 1")
         if solver_order(solver) is not None and (float(eta) != 0.0 or device_noise):     # an unknown name raises here too
             raise ValueError(f"solver {solver!r} is deterministic: eta must be 0 and device_noise off")
-        if image_io.wants_ingest(image):            # a uint8 picture (anything that is not a torch tensor is checked as one)
+        refs = check_references(image, image_weights)
+        weights = None
+        if refs is not None:
+            for ref in refs[0]:
+                if torch.is_tensor(ref) and ref.is_floating_point() and min(ref.shape[2:]) < 32:
+                    raise ValueError("a reference picture must be at least 32 a side")
+            image, weights = (refs[0][0], None) if len(refs[0]) == 1 else (list(refs[0]), [float(w) for w in refs[1]])
+        if weights is not None:
+            pass                                    # every reference was checked by check_references
+        elif image_io.wants_ingest(image):          # a uint8 picture (anything that is not a torch tensor is checked as one)
             image_io.check_u8_picture(image, "image", min_side=32)
         elif not (image.dim() == 4 and image.shape[0] == 1 and image.shape[1] == 3 and image.is_floating_point() and
                   min(image.shape[2:]) >= 32):
@@ -137,7 +153,7 @@ class PromptFreeServer:
                      strength=strength, init_k=init_k, mask=mask, composite=bool(composite) if mask is not None else None,
                      scale=scale, eta=eta, seed=int(seed), control=control, uncond=uncond, as_uint8=as_uint8,
                      device_noise=bool(device_noise), future=Future(), mixed=self.mixed_batches or None, solver=solver,
-                     control_preprocess=control_preprocess, control_thresholds=thresholds)
+                     control_preprocess=control_preprocess, control_thresholds=thresholds, weights=weights)
         self._q.put(r)
         return r.future
 
@@ -236,10 +252,14 @@ class PromptFreeServer:
         with DEVICE_LOCK:
             if float(r0.eta) != 0.0 and not r0.device_noise:   # runs alone (shareable()): its noise stream is a function
                 torch.manual_seed(r0.seed)                      # of ITS seed only
-            conds, xts, unconds, keys, masks, x0s = [], [], [], [], [], []
+            conds, xts, unconds, keys, masks, x0s, biases, ubiases = [], [], [], [], [], [], [], []
             for r in batch:
-                img = self.pipe.ingest(r.image) if image_io.wants_ingest(r.image) else r.image.to(dev)
-                c, z = self.pipe.encode_reference(img, r.n)
+                if r.weights is not None:           # several references: ITS tokens and ITS row of logits
+                    c, z, kb = self.pipe.encode_references(r.image, r.weights, r.n)
+                    biases.append(kb)
+                else:
+                    img = self.pipe.ingest(r.image) if image_io.wants_ingest(r.image) else r.image.to(dev)
+                    c, z = self.pipe.encode_reference(img, r.n)
                 conds.append(c)
                 unconds.append(z if r.uncond is None else r.uncond.to(dev).to(c.dtype).expand(r.n, -1, -1))
                 keys.append(shard_noise_keys(r.n, r.seed, 0, 1))                # each request keeps ITS noise keys (seed, j)
@@ -252,9 +272,21 @@ class PromptFreeServer:
                     xts.append(x_t)
                     x0s.append(x0)
                     masks.append(self.pipe.mask_grid(r.mask, r.height, r.width)[:1].expand(r.n, -1, -1))
+            if r0.weights is not None:
+                # contexts of different lengths: padded to the longest of the batch with zero tokens at -inf
+                nk = max(int(t.shape[1]) for t in conds + unconds)      # (an uncond longer than every mix is padded to as well)
+                for i, (c, u, kb) in enumerate(zip(conds, unconds, biases)):
+                    conds[i], biases[i] = self.pipe.pad_context(c, kb, nk)
+                    ub = torch.zeros((u.shape[0], u.shape[1]), dtype=torch.float32, device=u.device)
+                    unconds[i], ub = self.pipe.pad_context(u, ub, nk)
+                    ubiases.append(ub)
             cond, uncond, xT = torch.cat(conds), torch.cat(unconds), torch.cat(xts).to(dev)
             c_info = {'type': 'image', 'conditioning': cond, 'unconditional_conditioning': uncond,
                       'unconditional_guidance_scale': r0.scale}
+            if r0.weights is not None:
+                c_info['key_bias'] = torch.cat(biases)
+                if any(r.uncond is not None for r in batch):
+                    c_info['unconditional_key_bias'] = torch.cat(ubiases)
             per_sample = bool(r0.mixed) and float(r0.scale) != 1.0    # the scale-1 key keeps the batch without CFG
             if per_sample:                                            # fp32 [N]: r.scale for each of r's samples, batch order
                 c_info['unconditional_guidance_scale'] = torch.tensor(

@@ -2,6 +2,8 @@
 """Build the CPU emulation of csrc/gemm_glds.hip, csrc/norm.hip, csrc/attention.hip, csrc/image.hip, csrc/canny.hip, csrc/latent.hip and csrc/inpaint.hip (tools/cpu_emu/emu_*.cpp): write
 <file>_emu.inc = the kernel file with its gfx950 inline-asm statements replaced by their C meaning, then compile the
 drivers for the host with clang++.
+(emu_attn drives pfd_attention_f16 and, with --kbias, pfd_attention_kbias_f16: the LDS-DMA load of the key logits is the shim's
+__builtin_amdgcn_global_load_lds, the opaque register pins of its KBIAS builds fall under the first substitution below.)
 usage: [EMU_DEFINES="-DPFD_FAST_PROLOGUE ..."] build.py [outdir]   (default /tmp/pfd_cpu_emu)  -> <outdir>/emu_gemm, <outdir>/emu_norm, <outdir>/emu_attn, <outdir>/emu_image, <outdir>/emu_canny, <outdir>/emu_latent, <outdir>/emu_inpaint"""
 import os
 import re
@@ -27,15 +29,15 @@ SUBST = [
 ]
 
 
-def preprocess(name, out, required=True):
-    src = open(os.path.join(CSRC, name + ".hip")).read()
+def preprocess(name, out, required=True, ext=".hip", outname=None):
+    src = open(os.path.join(CSRC, name + ext)).read()
     for pat, rep in SUBST:
         src, n = re.subn(pat, rep, src)
     # (the PFD_ARG_BATCH_* macro bodies are compiled only outside the emulation: #if ... && !defined(PFD_CPU_EMU))
     left = [l for l in src.splitlines() if "asm volatile" in l and 'asm volatile("" :::' not in l and '"s"((p).tiles_m)' not in l]
     if left:
         sys.exit(f"build.py: inline asm in {name}.hip the emulation does not translate:\n" + "\n".join(left))
-    with open(os.path.join(out, name + "_emu.inc"), "w") as f:
+    with open(os.path.join(out, outname or name + "_emu.inc"), "w") as f:
         f.write(src)
 
 
@@ -49,6 +51,8 @@ def main():
         if only and driver not in only:
             continue
         preprocess(name, out)
+        if name == "attention":     # the kernel text attention.hip includes twice (with and without the key logits), under its own name
+            preprocess("attention2_kernel", out, ext=".inc", outname="attention2_kernel.inc")
         exe = os.path.join(out, driver)
         cmd = [CXX, "-std=c++17", os.environ.get("EMU_OPT", "-O0"), "-pthread", "-w", f"-I{HERE}", f"-I{out}", f"-I{REPO}/include", f"-I{CSRC}",
                os.path.join(HERE, driver + ".cpp"), "-o", exe] + os.environ.get("EMU_DEFINES", "").split()
