@@ -1,10 +1,10 @@
 // Boundary and elementwise kernels: layout conversion at the NCHW <-> NHWC boundary, im2col for
-// the few narrow-channel convolutions, timestep embedding, the fused CFG + DDIM update, adds.
+// the few narrow-channel convolutions, timestep embedding, the seeded noise on its own, adds
+// (the fused CFG + sampler step: step.hip).
 // All HBM-bound; small tensors (latents are 4 channels), so simplicity over peak bandwidth
 // except pfd_nhwc_to_nchw / pfd_add_f16 which see full-size images.
 #include "pfd_common.h"
 #include "philox.h"
-#include "step_common.h"
 
 namespace {
 
@@ -90,75 +90,6 @@ __global__ void timestep_embedding_kernel(const int64_t* __restrict__ t, half_t*
   out[i] = (half_t)v;
 }
 
-// ---- the fused CFG + sampler step -------------------------------------------------------------------------------------
-// What the three step kernels (cfg_ddim_kernel, cfg_dpmpp_kernel, cfg_ddim_rng_kernel) compute per element -- the guided
-// eps, pred_x0, the emit of the next UNet input -- is step_common.h, shared with the masked step of inpaint.hip.
-
-// PS (per-sample guidance scale, pfd_cfg_ddim_step_ps): scale_ps[b] in place of coef[4]; nothing else differs, and the
-// PS = false instantiation never reads scale_ps.
-template <bool PS>
-__global__ void cfg_ddim_kernel(const half_t* __restrict__ eps, int nb, const float* __restrict__ x,
-                                const float* __restrict__ noise, const float* __restrict__ coef,
-                                float* __restrict__ x_prev, float* __restrict__ pred_x0,
-                                half_t* __restrict__ xin_next, int rep, int B, int C, int h, int w,
-                                const float* __restrict__ scale_ps) {
-  const long n = (long)B * C * h * w;
-  const DdimStep k(coef);
-  const float scale_all = PS ? 0.f : coef[4];
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    // i indexes NCHW
-    const int xw = (int)(i % w);
-    long t = i / w;
-    const int yh = (int)(t % h);
-    t /= h;
-    const int c = (int)(t % C);
-    const int b = (int)(t / C);
-    const long ei = nhwc_index(b, c, yh, xw, C, h, w);
-    const float e = guided_eps(eps, nb, n, ei, PS ? scale_ps[b] : scale_all);
-    const float p0 = pred_x0_of(x[i], e, k.s1mat, k.isq_at);
-    float xp = k.update(p0, e);
-    if (noise) xp += k.sigma * noise[i];
-    x_prev[i] = xp;
-    pred_x0[i] = p0;
-    emit_next(xin_next, rep, n, ei, xp);
-  }
-}
-
-// DPM-Solver++(2M) step (pfd_cfg_dpmpp_step): the guided e and pred_x0 are the shared functions above; then
-// x_next = c_x x + c_d D with D = pred_x0 (x0_prev == NULL: a first-order step, the weights are not read) or
-// D = w_cur pred_x0 + w_prev x0_prev.  coef: {a_t, sqrt(1-a_t), c_x, c_d, w_cur, w_prev, guidance scale, 0}
-// (lib/solver.py).  PS as in cfg_ddim_kernel: scale_ps[b] in place of coef[6].
-template <bool PS>
-__global__ void cfg_dpmpp_kernel(const half_t* __restrict__ eps, int nb, const float* __restrict__ x,
-                                 const float* __restrict__ x0_prev, const float* __restrict__ coef,
-                                 float* __restrict__ x_next, float* __restrict__ pred_x0,
-                                 half_t* __restrict__ xin_next, int rep, int B, int C, int h, int w,
-                                 const float* __restrict__ scale_ps) {
-  const long n = (long)B * C * h * w;
-  const float a_t = coef[0], s1mat = coef[1], c_x = coef[2], c_d = coef[3], scale_all = PS ? 0.f : coef[6];
-  const float w_cur = x0_prev ? coef[4] : 1.f, w_prev = x0_prev ? coef[5] : 0.f;
-  const float isq_at = 1.0f / sqrtf(a_t);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    // i indexes NCHW
-    const int xw = (int)(i % w);
-    long t = i / w;
-    const int yh = (int)(t % h);
-    t /= h;
-    const int c = (int)(t % C);
-    const int b = (int)(t / C);
-    const long ei = nhwc_index(b, c, yh, xw, C, h, w);
-    const float e = guided_eps(eps, nb, n, ei, PS ? scale_ps[b] : scale_all);
-    const float xv = x[i];
-    const float p0 = pred_x0_of(xv, e, s1mat, isq_at);
-    float d = p0;
-    if (x0_prev) d = w_cur * p0 + w_prev * x0_prev[i];
-    const float xn = c_x * xv + c_d * d;
-    x_next[i] = xn;
-    pred_x0[i] = p0;
-    emit_next(xin_next, rep, n, ei, xn);
-  }
-}
-
 // The generator on its own: one thread per quad (one Philox call), out[b, 4q .. 4q+3].  VEC: n_per_sample % 4 == 0 and
 // `out` 16-byte aligned -> one 16-byte store; otherwise scalar stores, the tail of a sample's last quad dropped.
 template <bool VEC>
@@ -178,70 +109,6 @@ __global__ void philox_normal_kernel(const int64_t* __restrict__ key, int step, 
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (q * 4 + j < ns) o[j] = z[j];
-    }
-  }
-}
-
-// cfg_ddim_kernel with the noise evaluated in place: thread = four consecutive NCHW elements of ONE sample = one Philox
-// call.  VEC (w % 4 == 0, 16-byte aligned x / x_prev / pred_x0): the four share a row, 16-byte accesses; otherwise the
-// scalar path computes the same values.  The arithmetic is the shared functions of cfg_ddim_kernel.  PS as there: the
-// four elements of a thread belong to one sample, so scale_ps[b] is read once per quad.
-template <bool VEC, bool PS>
-__global__ void cfg_ddim_rng_kernel(const half_t* __restrict__ eps, int nb, const float* __restrict__ x,
-                                    const int64_t* __restrict__ key, int step, float noise_mul,
-                                    const float* __restrict__ coef, float* __restrict__ x_prev,
-                                    float* __restrict__ pred_x0, half_t* __restrict__ xin_next, int rep, int B, int C,
-                                    int h, int w, const float* __restrict__ scale_ps) {
-  const long ns = (long)C * h * w;
-  const long n = (long)B * ns;
-  const long nq = (ns + 3) >> 2;
-  const long total = (long)B * nq;
-  const DdimStep k(coef);
-  const float scale_all = PS ? 0.f : coef[4];
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int b = (int)(i / nq);
-    const long q = i - (long)b * nq;
-    const long e0 = q * 4;
-    const long base = (long)b * ns + e0;
-    const float scale = PS ? scale_ps[b] : scale_all;
-    float z[4], xv[4], xp4[4], p04[4];
-    pfd_philox_normal4(key[2 * b], key[2 * b + 1], step, (uint32_t)q, PFD_STREAM_STEP, z);
-    if (VEC) {
-      const float4 v = *reinterpret_cast<const float4*>(x + base);
-      xv[0] = v.x; xv[1] = v.y; xv[2] = v.z; xv[3] = v.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) xv[j] = e0 + j < ns ? x[base + j] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      xp4[j] = p04[j] = 0.f;
-      if (!VEC && e0 + j >= ns) continue;
-      const long el = e0 + j;   // (c*h + y)*w + x inside the sample
-      const int xw = (int)(el % w);
-      const long t = el / w;
-      const int yh = (int)(t % h);
-      const int c = (int)(t / h);
-      const long ei = nhwc_index(b, c, yh, xw, C, h, w);
-      const float e = guided_eps(eps, nb, n, ei, scale);
-      const float nz = noise_mul * z[j];
-      const float p0 = pred_x0_of(xv[j], e, k.s1mat, k.isq_at);
-      float xp = k.update(p0, e);
-      xp += k.sigma * nz;
-      xp4[j] = xp;
-      p04[j] = p0;
-      emit_next(xin_next, rep, n, ei, xp);
-    }
-    if (VEC) {
-      *reinterpret_cast<float4*>(x_prev + base) = make_float4(xp4[0], xp4[1], xp4[2], xp4[3]);
-      *reinterpret_cast<float4*>(pred_x0 + base) = make_float4(p04[0], p04[1], p04[2], p04[3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (e0 + j < ns) {
-          x_prev[base + j] = xp4[j];
-          pred_x0[base + j] = p04[j];
-        }
     }
   }
 }
@@ -356,33 +223,6 @@ __global__ void image_u8_kernel(const half_t* __restrict__ x, uint8_t* __restric
   }
 }
 
-// ---- the step entry points' shared host side ---------------------------------------------------------------------------
-// (grid_for, step_args_ok and quad_vec_ok: step_common.h)
-
-// The two launches of the DDIM step on checked arguments: the plain kernel, and the seeded one in the VEC form that the
-// alignment allows.  The entry point hands in its instantiations (PS or not) and its name for the launch check.
-template <class Kernel>
-int launch_ddim(Kernel kernel, const void* eps, int nb, const float* x, const float* noise, const float* coef,
-                const float* scale, float* x_prev, float* pred_x0, void* xin_next, int rep, int B, int C, int h, int w,
-                pfd_stream_t stream, const char* name) {
-  PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
-  hipLaunchKernelGGL(kernel, dim3(grid_for((long)B * C * h * w, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const half_t*)eps, nb, x, noise, coef, x_prev, pred_x0, (half_t*)xin_next, rep, B, C, h, w, scale);
-  return pfd_check_launch(name);
-}
-
-template <class Kernel>
-int launch_ddim_rng(Kernel vec_kernel, Kernel scalar_kernel, const void* eps, int nb, const float* x, const int64_t* key,
-                    int step, float noise_mul, const float* coef, const float* scale, float* x_prev, float* pred_x0,
-                    void* xin_next, int rep, int B, int C, int h, int w, pfd_stream_t stream, const char* name) {
-  const long nq = ((long)C * h * w + 3) >> 2;
-  PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
-  hipLaunchKernelGGL(quad_vec_ok(w, x, x_prev, pred_x0) ? vec_kernel : scalar_kernel, dim3(grid_for((long)B * nq, 256)),
-                     dim3(256), 0, (hipStream_t)stream, (const half_t*)eps, nb, x, key, step, noise_mul, coef, x_prev,
-                     pred_x0, (half_t*)xin_next, rep, B, C, h, w, scale);
-  return pfd_check_launch(name);
-}
-
 }  // namespace
 
 extern "C" int pfd_nchw_to_nhwc_f16(const void* x, int32_t src_f32, void* y, int32_t B, int32_t C, int32_t H,
@@ -429,15 +269,6 @@ extern "C" int pfd_timestep_embedding_f16(const int64_t* t, void* out, int32_t B
   return pfd_check_launch("pfd_timestep_embedding_f16");
 }
 
-extern "C" int pfd_cfg_ddim_step(const void* eps, int32_t nb, const float* x, const float* noise, const float* coef,
-                                 float* x_prev, float* pred_x0, void* xin_next, int32_t rep, int32_t B, int32_t C,
-                                 int32_t h, int32_t w, pfd_stream_t stream) {
-  if (!eps || !x || !coef || !x_prev || !pred_x0) return PFD_EINVAL;
-  if (!step_args_ok(nb, B, C, h, w, xin_next, rep)) return PFD_EINVAL;
-  return launch_ddim(cfg_ddim_kernel<false>, eps, nb, x, noise, coef, nullptr, x_prev, pred_x0, xin_next, rep, B, C, h, w,
-                     stream, "pfd_cfg_ddim_step");
-}
-
 extern "C" int pfd_philox_normal_f32(const int64_t* key, int32_t step, float* out, int32_t B, int64_t n_per_sample,
                                      pfd_stream_t stream) {
   if (!key || !out || B <= 0 || n_per_sample <= 0 || step < 0) return PFD_EINVAL;
@@ -452,47 +283,6 @@ extern "C" int pfd_philox_normal_f32(const int64_t* key, int32_t step, float* ou
     hipLaunchKernelGGL(philox_normal_kernel<false>, dim3(grid_for((long)B * nq, 256)), dim3(256), 0,
                        (hipStream_t)stream, key, step, out, B, (long)n_per_sample);
   return pfd_check_launch("pfd_philox_normal_f32");
-}
-
-extern "C" int pfd_cfg_ddim_step_rng(const void* eps, int32_t nb, const float* x, const int64_t* key, int32_t step,
-                                     float noise_mul, const float* coef, float* x_prev, float* pred_x0, void* xin_next,
-                                     int32_t rep, int32_t B, int32_t C, int32_t h, int32_t w, pfd_stream_t stream) {
-  if (!eps || !x || !key || !coef || !x_prev || !pred_x0 || step < 0) return PFD_EINVAL;
-  if (!step_args_ok(nb, B, C, h, w, xin_next, rep)) return PFD_EINVAL;
-  if ((long)C * h * w > ((long)1 << 34)) return PFD_ESHAPE;   // the quad index is one 32-bit counter word
-  return launch_ddim_rng(cfg_ddim_rng_kernel<true, false>, cfg_ddim_rng_kernel<false, false>, eps, nb, x, key, step,
-                         noise_mul, coef, nullptr, x_prev, pred_x0, xin_next, rep, B, C, h, w, stream,
-                         "pfd_cfg_ddim_step_rng");
-}
-
-extern "C" int pfd_cfg_ddim_step_ps(const void* eps, int32_t nb, const float* x, const float* noise, const int64_t* key,
-                                    int32_t step, float noise_mul, const float* coef, const float* scale,
-                                    float* x_prev, float* pred_x0, void* xin_next, int32_t rep, int32_t B, int32_t C,
-                                    int32_t h, int32_t w, pfd_stream_t stream) {
-  if (!eps || !x || !coef || !scale || !x_prev || !pred_x0 || (noise && key) || (key && step < 0)) return PFD_EINVAL;
-  if (!step_args_ok(nb, B, C, h, w, xin_next, rep)) return PFD_EINVAL;
-  if (key && (long)C * h * w > ((long)1 << 34)) return PFD_ESHAPE;
-  if (!key)
-    return launch_ddim(cfg_ddim_kernel<true>, eps, nb, x, noise, coef, scale, x_prev, pred_x0, xin_next, rep, B, C, h, w,
-                       stream, "pfd_cfg_ddim_step_ps");
-  return launch_ddim_rng(cfg_ddim_rng_kernel<true, true>, cfg_ddim_rng_kernel<false, true>, eps, nb, x, key, step,
-                         noise_mul, coef, scale, x_prev, pred_x0, xin_next, rep, B, C, h, w, stream,
-                         "pfd_cfg_ddim_step_ps");
-}
-
-extern "C" int pfd_cfg_dpmpp_step(const void* eps, int32_t nb, const float* x, const float* x0_prev, const float* coef,
-                                  const float* scale, float* x_next, float* pred_x0, void* xin_next, int32_t rep,
-                                  int32_t B, int32_t C, int32_t h, int32_t w, pfd_stream_t stream) {
-  if (!eps || !x || !coef || !x_next || !pred_x0) return PFD_EINVAL;
-  if (!step_args_ok(nb, B, C, h, w, xin_next, rep)) return PFD_EINVAL;
-  if (x0_prev && (x0_prev == x_next || x0_prev == pred_x0)) return PFD_EINVAL;   // the history is read while both are written
-  const long ns = (long)C * h * w;
-  if (ns > ((long)1 << 34)) return PFD_EINVAL;   // the per-sample bound of the seeded siblings
-  PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
-  const auto kernel = scale ? cfg_dpmpp_kernel<true> : cfg_dpmpp_kernel<false>;
-  hipLaunchKernelGGL(kernel, dim3(grid_for((long)B * ns, 256)), dim3(256), 0, (hipStream_t)stream, (const half_t*)eps,
-                     nb, x, x0_prev, coef, x_next, pred_x0, (half_t*)xin_next, rep, B, C, h, w, scale);
-  return pfd_check_launch("pfd_cfg_dpmpp_step");
 }
 
 extern "C" int pfd_add_f16(const void* a, const void* b, void* y, int64_t n, pfd_stream_t stream) {

@@ -164,6 +164,14 @@ struct PfdProfScope {
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
+// blocks of a grid-stride launch over n items: at most 4096
+inline int grid_for(long n, int block) {
+  long g = (n + block - 1) / block;
+  if (g > 4096) g = 4096;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
 // host-side error plumbing (defined in capi.cpp)
 int pfd_check_launch(const char* what);
 void pfd_set_error(const char* msg);

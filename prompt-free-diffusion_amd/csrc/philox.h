@@ -45,7 +45,7 @@ PFD_HD void pfd_box_muller(uint32_t ra, uint32_t rb, float* z0, float* z1) {
 // the fourth counter word names the stream a draw belongs to: the same (seed, sample_id, step, element) gives unrelated
 // normals in different streams.  0: the step noise (what the word always was); 1 / 2: the forward-noising noise and the
 // posterior noise of an img2img start (latent.hip), both at step 0; 3: the noise the kept region of a masked step is
-// re-noised with (inpaint.hip), at the step's index
+// re-noised with (step.hip), at the step's index
 #define PFD_STREAM_STEP 0u
 #define PFD_STREAM_Q 1u
 #define PFD_STREAM_POSTERIOR 2u

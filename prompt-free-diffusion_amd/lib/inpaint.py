@@ -1,6 +1,6 @@
 """Masked regeneration (inpainting) on the host -- numpy only.
 
-The device evaluates the same functions in csrc/inpaint.hip (pfd_cfg_step_masked, pfd_mask_grid_u8, pfd_composite_u8);
+The device evaluates the same functions in csrc/step.hip (pfd_cfg_step_masked) and csrc/inpaint.hip (pfd_mask_grid_u8, pfd_composite_u8);
 this module is the specification restated in fp64, the oracle of the tests, and the way to reproduce a masked request
 without a GPU.  The reference has no masked path (its ddim.py has none): the specification is this file.
 

@@ -11,7 +11,7 @@ step index `step` is output word e & 3 -> normal of
 
 `stream` is 0 for the step noise (the word was always 0: those draws are what they were), 1 for the forward-noising
 noise and 2 for the posterior noise of an img2img start (lib/img2img.py, csrc/latent.hip), both at step 0, and 3 for the
-noise the kept region of a masked step is re-noised with (lib/inpaint.py, csrc/inpaint.hip), at that step's index, and 4
+noise the kept region of a masked step is re-noised with (lib/inpaint.py, csrc/step.hip), at that step's index, and 4
 for the noise the enlarged latent of a two-pass request is re-noised with (lib/hires.py; host only so far), at step 0 and
 indexed by the element of the enlarged latent;
 

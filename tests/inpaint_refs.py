@@ -13,7 +13,7 @@ keys = I.keys
 scaled_err = I.scaled_err
 
 # (B, C, h, w): w % 4 != 0 forces the scalar path; (2, 3, 3, 5) has an odd sample length; the last is one quad past the
-# 4096 x 256 threads of the largest grid (csrc/step_common.h grid_for), B = 1 only
+# 4096 x 256 threads of the largest grid (csrc/pfd_common.h grid_for), B = 1 only
 SHAPES = [(2, 4, 8, 8), (1, 4, 3, 5), (3, 4, 1, 1), (2, 3, 3, 5)]
 PAST_THE_GRID = (1, 4, 1, (1 << 20) + 1)
 

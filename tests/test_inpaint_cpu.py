@@ -147,14 +147,23 @@ def test_every_mutant_leaves_the_gpu_tests_tolerance():
 
 
 # ---- the kernels on the CPU emulation --------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def emu_inpaint(tmp_path_factory):
+def _build_emu(tmp_path_factory, driver):
     if not os.path.exists(CXX):
         pytest.skip("clang++ of the ROCm toolchain not available")
-    out = str(tmp_path_factory.mktemp("pfd_cpu_emu_inpaint"))
+    out = str(tmp_path_factory.mktemp("pfd_cpu_" + driver))
     subprocess.run([sys.executable, os.path.join(REPO, "tools", "cpu_emu", "build.py"), out], check=True,
-                   stdout=subprocess.DEVNULL, env=dict(os.environ, EMU_ONLY="emu_inpaint", EMU_OPT="-O1"))
-    return os.path.join(out, "emu_inpaint")
+                   stdout=subprocess.DEVNULL, env=dict(os.environ, EMU_ONLY=driver, EMU_OPT="-O1"))
+    return os.path.join(out, driver)
+
+
+@pytest.fixture(scope="module")
+def emu_inpaint(tmp_path_factory):
+    return _build_emu(tmp_path_factory, "emu_inpaint")
+
+
+@pytest.fixture(scope="module")
+def emu_step(tmp_path_factory):
+    return _build_emu(tmp_path_factory, "emu_step")
 
 
 def _emu_step_case(tmp, i, c, offset=0):
@@ -168,8 +177,8 @@ def _emu_step_case(tmp, i, c, offset=0):
     with open(path, "wb") as f:
         f.write(b"".join(np.ascontiguousarray(p).tobytes() for p in parts))
     B, C, h, w = c['shape']
-    return (f"step,{B},{c['Bm']},{C},{h},{w},{c['nb']},{c['rep']},{0 if c['solver'] == 'ddim' else 1},"
-            f"{int(c['scale'] is not None)},{int(c['x0_prev'] is not None)},{c['index']},{float(c['noise_mul']).hex()},"
+    return (f"masked,{B},{c['Bm']},{C},{h},{w},{c['nb']},{c['rep']},{0 if c['solver'] == 'ddim' else 1},"
+            f"{int(c['scale'] is not None)},{int(c['x0_prev'] is not None)},0,1,{c['index']},{float(c['noise_mul']).hex()},"
             f"{float(c['ksq']).hex()},{float(c['ks']).hex()},{offset},{path}"), path
 
 
@@ -181,8 +190,8 @@ def _run_emu(exe, args):
     return lines
 
 
-def test_step_kernel_on_the_emulation_matches_the_specification(emu_inpaint, tmp_path):
-    """csrc/inpaint.hip compiled for the host: every shared case (all shapes but the one past the grid, which the GPU test
+def test_step_kernel_on_the_emulation_matches_the_specification(emu_step, tmp_path):
+    """csrc/step.hip compiled for the host, through pfd_cfg_step_masked: every shared case (all shapes but the one past the grid, which the GPU test
     covers: a million emulated quads are minutes of host threads), both solvers, plus the scalar path forced by misaligned
     tensors -- return code, one launch, guard bands, the instantiation, and x_out / pred_x0 / xin_next against
     lib/inpaint.py at the GPU test's tolerance (xin_next beyond the half ulp of its own f16 rounding, inpaint_refs.xin_err);
@@ -190,13 +199,12 @@ def test_step_kernel_on_the_emulation_matches_the_specification(emu_inpaint, tmp
     cases = [(c, 0) for c in R.cases()]
     cases += [(R.case(f, R.SHAPES[0], 2, 'soft'), 1) for f in ('ddim_seeded', 'dpm2')]          # misaligned: scalar accesses
     args, paths = zip(*[_emu_step_case(str(tmp_path), i, c, off) for i, (c, off) in enumerate(cases)])
-    lines = _run_emu(emu_inpaint, args)
+    lines = _run_emu(emu_step, args)
     seen = set()
     for (c, off), path, line in zip(cases, paths, lines):
         B, C, h, w = c['shape']
         vec = off == 0 and w % 4 == 0
-        inst = f"cfg_masked_kernel<{'true' if vec else 'false'}, {0 if c['solver'] == 'ddim' else 1}, " \
-               f"{'true' if c['scale'] is not None else 'false'}>"
+        inst = f"cfg_step_kernel<{0 if c['solver'] == 'ddim' else 1}, true, true, {'true' if vec else 'false'}>"
         assert inst in line, (inst, line)
         seen.add(inst)
         ref = R.reference(c)
@@ -210,7 +218,7 @@ def test_step_kernel_on_the_emulation_matches_the_specification(emu_inpaint, tmp
             assert np.array_equal(xin[r], np.transpose(xout, (0, 2, 3, 1)).astype(np.float16)), line
         if c['mask_kind'] == 'zeros' and c['index'] == 0:
             assert np.array_equal(xout, c['x0'])
-    assert len(seen) == 6, seen      # VEC x {ddim, ddim per-sample, dpmpp}: every instantiation the cases can reach
+    assert len(seen) == 4, seen      # VEC x {ddim, dpmpp}: every masked instantiation (a per-sample scale is a runtime branch)
 
 
 def test_mask_and_composite_kernels_on_the_emulation_are_byte_exact(emu_inpaint, tmp_path):
@@ -258,12 +266,13 @@ def test_header_declares_and_binding_lists_the_entry_points():
     assert re.search(r"#define\s+PFD_ABI_VERSION\s+10\b", src) and binding.ABI_VERSION == 10     # entry points added only
     mk = open(os.path.join(REPO, "prompt-free-diffusion_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SRCS\s*:=.*\binpaint\.hip\b", mk, flags=re.M)
-    # the shared per-element functions exist once, in the header both kernel files include
+    assert re.search(r"^SRCS\s*:=.*\bstep\.hip\b", mk, flags=re.M)
+    # the shared per-element functions exist once, in the file of the one step kernel
     csrc = os.path.join(REPO, "prompt-free-diffusion_amd", "csrc")
     for fn in ("guided_eps", "pred_x0_of", "emit_next", "nhwc_index", "struct DdimStep"):
-        defs = [f for f in ("elementwise.hip", "inpaint.hip", "step_common.h")
+        defs = [f for f in ("elementwise.hip", "inpaint.hip", "step.hip")
                 if re.search(r"(float|void|long)\s+" + fn + r"\s*\(|" + re.escape(fn) + r"\s*\{", open(os.path.join(csrc, f)).read())]
-        assert defs == ["step_common.h"], (fn, defs)
+        assert defs == ["step.hip"], (fn, defs)
 
 
 def test_cabi_argument_checks_need_no_gpu():

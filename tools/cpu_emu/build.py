@@ -1,10 +1,10 @@
 #!/usr/bin/env python
-"""Build the CPU emulation of csrc/gemm_glds.hip, csrc/norm.hip, csrc/attention.hip, csrc/image.hip, csrc/canny.hip, csrc/latent.hip and csrc/inpaint.hip (tools/cpu_emu/emu_*.cpp): write
+"""Build the CPU emulation of csrc/gemm_glds.hip, csrc/norm.hip, csrc/attention.hip, csrc/image.hip, csrc/canny.hip, csrc/latent.hip, csrc/inpaint.hip and csrc/step.hip (tools/cpu_emu/emu_*.cpp): write
 <file>_emu.inc = the kernel file with its gfx950 inline-asm statements replaced by their C meaning, then compile the
 drivers for the host with clang++.
 (emu_attn drives pfd_attention_f16 and, with --kbias, pfd_attention_kbias_f16: the LDS-DMA load of the key logits is the shim's
 __builtin_amdgcn_global_load_lds, the opaque register pins of its KBIAS builds fall under the first substitution below.)
-usage: [EMU_DEFINES="-DPFD_FAST_PROLOGUE ..."] build.py [outdir]   (default /tmp/pfd_cpu_emu)  -> <outdir>/emu_gemm, <outdir>/emu_norm, <outdir>/emu_attn, <outdir>/emu_image, <outdir>/emu_canny, <outdir>/emu_latent, <outdir>/emu_inpaint"""
+usage: [EMU_DEFINES="-DPFD_FAST_PROLOGUE ..."] build.py [outdir]   (default /tmp/pfd_cpu_emu)  -> <outdir>/emu_gemm, <outdir>/emu_norm, <outdir>/emu_attn, <outdir>/emu_image, <outdir>/emu_canny, <outdir>/emu_latent, <outdir>/emu_inpaint, <outdir>/emu_step"""
 import os
 import re
 import subprocess
@@ -47,7 +47,7 @@ def main():
     procs = []
     only = os.environ.get("EMU_ONLY", "").split()     # e.g. EMU_ONLY=emu_gemm: just that driver
     for name, driver in (("gemm_glds", "emu_gemm"), ("norm", "emu_norm"), ("attention", "emu_attn"), ("image", "emu_image"),
-                         ("canny", "emu_canny"), ("latent", "emu_latent"), ("inpaint", "emu_inpaint")):
+                         ("canny", "emu_canny"), ("latent", "emu_latent"), ("inpaint", "emu_inpaint"), ("step", "emu_step")):
         if only and driver not in only:
             continue
         preprocess(name, out)

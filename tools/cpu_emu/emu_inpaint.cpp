@@ -1,16 +1,10 @@
 // CPU emulation of csrc/inpaint.hip (test infrastructure; see hip/hip_runtime.h in this directory for the execution model): the
-// three kernels run through the library's own entry points, Philox rounds, Box-Muller and all, on cases given on the command
-// line.  The driver checks the return code and the guard bands around every output, prints one line per case (with the
+// two kernels run through the library's own entry points on cases given on the command line (the masked step: emu_step.cpp).  The driver checks the return code and the guard bands around every output, prints one line per case (with the
 // instantiated kernel) and leaves the outputs next to the input for the test to judge against lib/inpaint.py.
 //
 // usage: emu_inpaint <case> ...
-//   step,B,Bm,C,h,w,nb,rep,solver,ps,hist,index,noise_mul,ksq,ks,offset,path
-//     <path>: int64 [B][2] key rows, f32 [8] coefficient row, f32 [B] scales (ps), f16 [nb*B][h][w][C] eps, f32 x, f32 x0_prev
-//     (hist), f32 x0_keep, f32 [Bm][h][w] mask;  written: <path>.xout, <path>.pred (f32 NCHW), <path>.xin (f16 [rep*B][h][w][C])
 //   grid,Bm,Hm,Wm,gh,gw,f32,path      <path>: u8 [Bm][Hm][Wm];  written: <path>.out (f32 or u8 [Bm][gh][gw])
 //   comp,n,Bi,Bs,H,W,C,path           <path>: u8 decoded [n][H][W][C], init [Bi][H][W][C], sel [Bs][H][W];  written: <path>.out
-// Floats are read with strtof (hex floats pass exactly).  offset: the fp32 tensors start that many floats behind a 16-byte
-// boundary (0: the 16-byte accesses where w allows them; 1: the scalar path).
 #include <stdio.h>
 
 #include <string>
@@ -64,57 +58,10 @@ static std::vector<std::string> split(const std::string& s, size_t nfields, std:
 }
 
 static std::string kernel_and_reset() {
-  std::string k = emu::launch_log.empty() ? "" : emu::launch_log[0].kernel;
-  // the demangler of the host's C++ runtime does not know _Float16 parameters: read the step kernel's template arguments
-  // off the mangled name ("cfg_masked_kernelILb1ELi0ELb0EE" -> "cfg_masked_kernel<true, 0, false>")
-  int vec = 0, solver = 0, ps = 0;
-  const size_t at = k.find("cfg_masked_kernelI");
-  if (at != std::string::npos && sscanf(k.c_str() + at, "cfg_masked_kernelILb%dELi%dELb%dEE", &vec, &solver, &ps) == 3)
-    k = std::string("cfg_masked_kernel<") + (vec ? "true" : "false") + ", " + std::to_string(solver) + ", " + (ps ? "true" : "false") + ">";
+  const std::string k = emu::launch_log.empty() ? "" : emu::launch_log[0].kernel;
   emu::launched.clear();
   emu::launch_log.clear();
   return k;
-}
-
-static int run_step(const std::string& s) {
-  std::string path;
-  const std::vector<std::string> f = split(s, 16, &path);
-  if (f.size() != 16) { fprintf(stderr, "emu_inpaint: malformed case %s\n", s.c_str()); exit(2); }
-  auto I = [&](int i) { return atoi(f[i].c_str()); };
-  const int B = I(1), Bm = I(2), C = I(3), h = I(4), w = I(5), nb = I(6), rep = I(7), solver = I(8), ps = I(9), hist = I(10), index = I(11);
-  const float noise_mul = strtof(f[12].c_str(), nullptr), ksq = strtof(f[13].c_str(), nullptr), ks = strtof(f[14].c_str(), nullptr);
-  const int offset = I(15);
-  if (B < 1 || Bm < 1 || C < 1 || h < 1 || w < 1 || nb < 1 || nb > 2 || rep < 1 || rep > 2) { fprintf(stderr, "emu_inpaint: %s: bad dimensions\n", s.c_str()); exit(2); }
-  const size_t n = (size_t)B * C * h * w;
-  std::vector<int64_t> key((size_t)B * 2);
-  std::vector<float> coef(8), scale(B);
-  std::vector<half_t> eps((size_t)nb * n);
-  Guarded<float> x(n, offset), hprev(n, offset), x0(n, offset), xout(n, offset), pred(n, offset), mask((size_t)Bm * h * w, 0);
-  Guarded<half_t> xin((size_t)rep * n, 0);
-  FILE* in = fopen(path.c_str(), "rb");
-  if (!in) { fprintf(stderr, "emu_inpaint: cannot read %s\n", path.c_str()); exit(2); }
-  read_exact(in, key.data(), key.size() * 8, path);
-  read_exact(in, coef.data(), 32, path);
-  if (ps) read_exact(in, scale.data(), (size_t)B * 4, path);
-  read_exact(in, eps.data(), eps.size() * 2, path);
-  read_exact(in, x.p(), n * 4, path);
-  if (hist) read_exact(in, hprev.p(), n * 4, path);
-  read_exact(in, x0.p(), n * 4, path);
-  read_exact(in, mask.p(), (size_t)Bm * h * w * 4, path);
-  if (fgetc(in) != EOF) { fprintf(stderr, "emu_inpaint: %s is longer than its case\n", path.c_str()); exit(2); }
-  fclose(in);
-  const int rc = pfd_cfg_step_masked(eps.data(), nb, x.p(), solver, hist ? hprev.p() : nullptr, key.data(), index, noise_mul,
-                                     coef.data(), ps ? scale.data() : nullptr, x0.p(), mask.p(), Bm, ksq, ks, xout.p(), pred.p(),
-                                     xin.p(), rep, B, C, h, w, nullptr);
-  const bool guards = x.intact() && hprev.intact() && x0.intact() && xout.intact() && pred.intact() && mask.intact() && xin.intact();
-  const bool ok = rc == 0 && guards && emu::launch_log.size() == 1;
-  printf("%s step %dx%dx%dx%d Bm %d nb %d rep %d solver %d offset %d  rc %d%s | %s\n", ok ? "ok  " : "FAIL", B, C, h, w, Bm, nb, rep,
-         solver, offset, rc, guards ? "" : ", WRITE OUTSIDE A BUFFER", kernel_and_reset().c_str());
-  fflush(stdout);
-  write_file(path + ".xout", xout.p(), n * 4);
-  write_file(path + ".pred", pred.p(), n * 4);
-  write_file(path + ".xin", xin.p(), (size_t)rep * n * 2);
-  return !ok;
 }
 
 static int run_grid(const std::string& s) {
@@ -168,12 +115,11 @@ static int run_comp(const std::string& s) {
 }
 
 int main(int argc, char** argv) {
-  if (argc < 2) { fprintf(stderr, "usage: emu_inpaint step,...|grid,...|comp,... (see the head of emu_inpaint.cpp)\n"); return 2; }
+  if (argc < 2) { fprintf(stderr, "usage: emu_inpaint grid,...|comp,... (see the head of emu_inpaint.cpp)\n"); return 2; }
   int fail = 0;
   for (int a = 1; a < argc; ++a) {
     const std::string s = argv[a];
-    if (s.rfind("step,", 0) == 0) fail += run_step(s);
-    else if (s.rfind("grid,", 0) == 0) fail += run_grid(s);
+    if (s.rfind("grid,", 0) == 0) fail += run_grid(s);
     else if (s.rfind("comp,", 0) == 0) fail += run_comp(s);
     else { fprintf(stderr, "emu_inpaint: unknown case %s\n", argv[a]); return 2; }
   }

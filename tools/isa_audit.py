@@ -27,7 +27,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{REPO}/include", f"-I{CSRC}", "-Wno-unused-result",
          "-mllvm", "-amdgpu-mfma-vgpr-form", "-S", "--cuda-device-only"]
 # per-kernel override of the accepted count of single loads waited for immediately (default 2: a lone operand load in
-# a prologue is fine).  swin_attn.hip (relative-position-bias gathers) and elementwise.hip (cfg_ddim tables) are not
+# a prologue is fine).  swin_attn.hip (relative-position-bias gathers) and step.hip (the sampler step's eps gathers) are not
 # in the default file list: once per image / once per step, < 0.1 % of the loop (DESIGN.md work queue)
 KNOWN = {}
 
