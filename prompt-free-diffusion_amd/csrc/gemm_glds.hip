@@ -5,7 +5,7 @@
 // Block tile BM x BN x 64 with BM = WAVES_M * WMB * 16, BN = 32 * NT; waves laid out WAVES_M (M) x 2 (N);
 // each wave owns a (WMB*16) x (16*NT) sub-tile = WMB x NT MFMA tiles of 16x16 (fp32 accumulators:
 // WMB*NT*4 registers).  Variants: <4,4> 256xBN (8 waves), <2,4> 128xBN, <2,2> 64xBN (4 waves);
-// small-MN / huge-K problems add split-K over gridDim.z with fp32 slabs and a reduce+epilogue kernel.
+// small-MN / huge-K problems add split-K over gridDim.z with f16 slabs and a reduce+epilogue kernel.
 //
 // Staging is LDS-DMA (global_load_lds_dwordx4): one wave instruction moves 8 rows x 128 B straight
 // from global memory into LDS, two LDS stages, the next K tile in flight during the MFMAs of the
@@ -31,6 +31,7 @@
 #include <stdlib.h>
 
 #include "pfd_common.h"
+#include "gn_stages.h"   // the split-K epilogue tail and the slab GroupNorm stages shared with norm.hip
 
 int pfd_ln_rowstats_launch(const half_t* x, long ldx, int M, int C, float* out, hipStream_t s, bool prof);   // norm.hip
 
@@ -1724,7 +1725,8 @@ __global__ __launch_bounds__(768) void conv3x3_patch_ws_kernel(const G160Params 
 //  barrier per tap -- forced variant 95, bit-identical, validated on hardware -- measured +0.2 % per batch and was removed,
 //  profiles/r05_e2e_ab_candidates.log; the protocol and its failed two-counter draft are in the git history.)
 
-// sum the split-K slabs and apply the epilogue (bias, row vector, activation, residual)
+// sum the split-K slabs and apply the epilogue (bias, row vector, activation, residual: splitk_tail, gn_stages.h, in all
+// three reduction kernels)
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const G160Params p) {
   const int nv = p.N / 8;
   const long nvec = (long)p.M * nv;
@@ -1774,14 +1776,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const G160Params p) 
     }
     Pack16 o;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float x = v[e] + (float)bb.e[e];
-      x += (float)rv.e[e];
-      if (p.act == PFD_ACT_GELU) x = pfd_gelu(x);
-      else if (p.act == PFD_ACT_RELU) x = fmaxf(x, 0.f);
-      else if (p.act == PFD_ACT_SILU) x = pfd_silu(x);
-      o.e[e] = (half_t)(x + (float)rr.e[e]);
-    }
+    for (int e = 0; e < 8; ++e) o.e[e] = splitk_tail(v[e], bb.e[e], rv.e[e], rr.e[e], p.act);
     gst_t<PFD_ST_REDUCE>(reinterpret_cast<uint4*>(p.C + (long)m * p.ldc + n), o.u);
   }
 }
@@ -1790,7 +1785,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const G160Params p) 
 // tile, the store-pass mapping of epilogue_store_gn (a wave = 3 rows x 20 chunks), statistics through gn_slab_reduce.  The
 // 64-row slab is walked in six sweeps of 12 rows; the loads of THREE sweeps (row vector / residual / 4-8 slab slices) are
 // requested before the first add (round 5: the one-sweep-at-a-time form was six dependent round trips, 14.7 us per launch for
-// 2-10 MB at the 8^2 / 16^2 levels; same slab order per element, same order of the rows in the statistics = the same bits;
+// 2-10 MB at the 8^2 / 16^2 levels; same slab order per element, same order of the rows in the statistics: the bits it had;
 // adopted with the GroupNorm apply's grouped partial loads at -0.3 % per batch, profiles/r05_e2e_ab_candidates.log).
 // Up to 8 splits x 3 sweeps x 32 bytes = 96 + 24 VGPRs of loads.
 // (round 5: 16 waves per slab -- the whole 64 rows requested in one round trip -- measured +0.3 % per batch against these 4,
@@ -1850,12 +1845,7 @@ __global__ __launch_bounds__(RGN_T) void splitk_reduce_gn_kernel(const G160Param
       const float mk = ok[u] ? 1.f : 0.f;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        float x = v[u][e] + (float)bb.e[e];
-        x += (float)rv[u].e[e];
-        if (p.act == PFD_ACT_GELU) x = pfd_gelu(x);
-        else if (p.act == PFD_ACT_RELU) x = fmaxf(x, 0.f);
-        else if (p.act == PFD_ACT_SILU) x = pfd_silu(x);
-        o.e[e] = (half_t)(x + (float)rr[u].e[e]);
+        o.e[e] = splitk_tail(v[u][e], bb.e[e], rv[u].e[e], rr[u].e[e], p.act);
         const float f = (float)o.e[e] * mk;
         cs[e] += f;
         cq[e] = fmaf(f, f, cq[e]);
@@ -1872,9 +1862,9 @@ __global__ __launch_bounds__(RGN_T) void splitk_reduce_gn_kernel(const G160Param
 // 16^2 levels of the UNet every 3x3 convolution splits K, a reduction launch stores the f16 result and the single-launch
 // GroupNorm (gn_small_kernel, norm.hip) reads it again: 20 such pairs per UNet pass, ~8 us + a launch boundary each.  Here
 // a block owns one (sample, group) slab of the OUTPUT -- gnf_rows rows x N / 32 channels, the unit gn_small_kernel owns --
-// and forms it from the fp32 slabs: epilogue as in splitk_reduce_kernel (same slab order, same operation order: the same
-// f16 values), statistics and normalisation as in gn_small_kernel (same thread -> chunk mapping, same order of the adds,
-// same expressions: the same bits).  The raw result is stored too unless skip_raw.  Loads are unconditional and issued a
+// and forms it from the f16 slabs: the slab order of splitk_reduce_kernel and its epilogue tail (splitk_tail), then, on
+// gn_small_kernel's thread -> chunk mapping, that kernel's statistics and normalisation (gn_slab_stats, gn_affine,
+// gn_normalise; all in gn_stages.h).  The raw result is stored too unless skip_raw.  Loads are unconditional and issued a
 // group of two chunks x four slabs at a time (8 x 16 bytes in flight per thread, 1024 threads), indices walk incrementally (no
 // division per chunk), gamma / beta of the group sit in LDS before the statistics barrier.
 struct GnFuse {
@@ -1885,29 +1875,22 @@ struct GnFuse {
   float eps;
   int act, rows, skip_raw;
 };
-// 1024 threads per (sample, group) slab: the job is one round trip of 40-660 KB per block, i.e. bound by how many loads a
-// block has in flight; with 256 threads it took as long as the plain reduction (2048 blocks) + gn_small_kernel together
-// (16.8 us, profiles/r05_fused_gnorm_ab.log)
-#ifndef PFD_GN_THREADS
-#define PFD_GN_THREADS 1024   // (-DPFD_GN_THREADS=256: A/B builds; must match norm.hip for the bit identity)
-#endif
-constexpr int GNF_T = PFD_GN_THREADS;
-constexpr int GNF_MAX = 8192 / GNF_T;      // chunks (4 halfs) per thread: rows * (N / 128) <= GNF_T * GNF_MAX
+// GNS_T threads per (sample, group) slab and GNS_MAX chunks (4 halfs) per thread (gn_stages.h): rows * (N / 128) <= GNS_T * GNS_MAX
 constexpr int GNF_U = 2;        // chunks whose slab slices are requested together: 2 x 4 slabs x 16 bytes = 32 VGPRs of loads (128-VGPR budget at 16 waves per CU)
 
-__global__ __launch_bounds__(GNF_T) void splitk_reduce_gnorm_kernel(const G160Params p, const GnFuse f) {
-  __shared__ float red[2 * GNF_T / 64];
+__global__ __launch_bounds__(GNS_T) void splitk_reduce_gnorm_kernel(const G160Params p, const GnFuse f) {
+  __shared__ float red[2 * GNS_T / 64];
   __shared__ float gam_s[256], bet_s[256];
   const int cpg = p.N / 32, cpr = cpg / 4;
   // XCD-aware order: the 32 group slabs of a sample are 160-byte column strips of the same rows, i.e. neighbours share
   // cache lines -- all of them on one XCD (one L2), as many samples per XCD as the grid has (round 5: the plain (g, b) grid
   // spread the groups of a sample over all eight L2s and every strip edge was fetched twice from the memory side)
   const int lin = xcd_remap(blockIdx.x, gridDim.x);
-  const int g = lin & 31, b = lin >> 5, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lin & 31, b = lin >> 5, tid = threadIdx.x;
   const int HW = f.rows, total = HW * cpr;
   const int n_g = g * cpg;
   const long m_b = (long)b * HW;
-  const int dr = GNF_T / cpr, dc = GNF_T - dr * cpr;
+  const int dr = GNS_T / cpr, dc = GNS_T - dr * cpr;
   // one row vector per sample (host: rows_per_rv % rows == 0 or rows_per_rv >= M)
   const half_t* rvb = p.rowvec ? p.rowvec + (m_b / p.rows_per_rv) * p.ldrv + n_g : g_zero_page;
   const int rv_step = p.rowvec ? 4 : 0, b_step = p.bias ? 4 : 0;
@@ -1915,11 +1898,11 @@ __global__ __launch_bounds__(GNF_T) void splitk_reduce_gnorm_kernel(const G160Pa
   const long r_ld = p.R ? p.ldr : 0;
   const int r_step = p.R ? 4 : 0;
   const half_t* rb = p.R ? p.R + m_b * p.ldr + n_g : g_zero_page;
-  uint2 v[GNF_MAX];
+  uint2 v[GNS_MAX];
   int r = tid / cpr, ch = tid - r * cpr;
 #pragma unroll
-  for (int k0 = 0; k0 < GNF_MAX; k0 += GNF_U) {
-    if (GNF_T * k0 >= total) {          // block-uniform: nothing of this group (or any later one) exists
+  for (int k0 = 0; k0 < GNS_MAX; k0 += GNF_U) {
+    if (GNS_T * k0 >= total) {          // block-uniform: nothing of this group (or any later one) exists
 #pragma unroll
       for (int u = 0; u < GNF_U; ++u) v[k0 + u] = make_uint2(0, 0);
       continue;
@@ -1928,7 +1911,7 @@ __global__ __launch_bounds__(GNF_T) void splitk_reduce_gnorm_kernel(const G160Pa
     bool on[GNF_U];
 #pragma unroll
     for (int u = 0; u < GNF_U; ++u) {
-      on[u] = tid + GNF_T * (k0 + u) < total;
+      on[u] = tid + GNS_T * (k0 + u) < total;
       ru[u] = on[u] ? r : 0;          // slots past the slab read the slab's first chunk and are dropped below
       cu[u] = on[u] ? ch : 0;
       r += dr;
@@ -1971,14 +1954,7 @@ __global__ __launch_bounds__(GNF_T) void splitk_reduce_gnorm_kernel(const G160Pa
     for (int u = 0; u < GNF_U; ++u) {
       Pack8 o;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float x = acc[u][e] + (float)bq[u].e[e];
-        x += (float)rq[u].e[e];
-        if (p.act == PFD_ACT_GELU) x = pfd_gelu(x);
-        else if (p.act == PFD_ACT_RELU) x = fmaxf(x, 0.f);
-        else if (p.act == PFD_ACT_SILU) x = pfd_silu(x);
-        o.e[e] = (half_t)(x + (float)xq[u].e[e]);
-      }
+      for (int e = 0; e < 4; ++e) o.e[e] = splitk_tail(acc[u][e], bq[u].e[e], rq[u].e[e], xq[u].e[e], p.act);
       if (on[u] && !f.skip_raw) gst_t<PFD_ST_REDUCE>(reinterpret_cast<uint2*>(p.C + (m_b + ru[u]) * p.ldc + n_g + cu[u] * 4), o.u);
       v[k0 + u] = on[u] ? o.u : make_uint2(0, 0);
     }
@@ -1989,7 +1965,7 @@ __global__ __launch_bounds__(GNF_T) void splitk_reduce_gnorm_kernel(const G160Pa
   }
   float sm = 0.f, sq = 0.f;
 #pragma unroll
-  for (int k = 0; k < GNF_MAX; ++k) {   // gn_small_kernel's order: chunk k of this thread, element e
+  for (int k = 0; k < GNS_MAX; ++k) {   // gn_small_kernel's thread loop (see gn_slab_stats): chunk k, element e; f16 squares are exact
     Pack8 q;
     q.u = v[k];
 #pragma unroll
@@ -1999,38 +1975,22 @@ __global__ __launch_bounds__(GNF_T) void splitk_reduce_gnorm_kernel(const G160Pa
       sq += x * x;
     }
   }
-  sm = wave_sum(sm);
-  sq = wave_sum(sq);
-  constexpr int NWV = GNF_T / 64;
-  if (lane == 0) {
-    red[wave] = sm;
-    red[NWV + wave] = sq;
-  }
-  __syncthreads();
-  const float count = (float)HW * (float)cpg;
-  float ts = red[0], tq = red[NWV];
-#pragma unroll
-  for (int w = 1; w < NWV; ++w) {   // gn_small_kernel's order
-    ts += red[w];
-    tq += red[NWV + w];
-  }
-  const float mean = ts / count;
-  const float rstd = rsqrtf(fmaxf(tq / count - mean * mean, 0.f) + f.eps);
+  float mean, rstd;
+  gn_slab_stats(sm, sq, HW, cpg, f.eps, red, mean, rstd);
   half_t* yb = f.y + m_b * f.ldy + n_g;
   r = tid / cpr;
   ch = tid - r * cpr;
   asm volatile("" : "+v"(r), "+v"(ch));   // a second walk, not the index registers of the first one kept alive
 #pragma unroll
-  for (int k = 0; k < GNF_MAX; ++k) {
-    if (tid + GNF_T * k < total) {
+  for (int k = 0; k < GNS_MAX; ++k) {
+    if (tid + GNS_T * k < total) {
       Pack8 q, o;
       q.u = v[k];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float w = rstd * gam_s[ch * 4 + e];
-        float t = (float)q.e[e] * w + (bet_s[ch * 4 + e] - mean * w);
-        if (f.act == PFD_ACT_SILU) t = pfd_silu(t);
-        o.e[e] = (half_t)t;
+        float w, sh;
+        gn_affine(mean, rstd, gam_s[ch * 4 + e], bet_s[ch * 4 + e], w, sh);
+        o.e[e] = gn_normalise((float)q.e[e], w, sh, f.act);
       }
       gst_t<PFD_ST_REDUCE>(reinterpret_cast<uint2*>(yb + (long)r * f.ldy + ch * 4), o.u);
     }
@@ -2049,14 +2009,14 @@ __global__ __launch_bounds__(GNF_T) void splitk_reduce_gnorm_kernel(const G160Pa
 inline void launch_splitk_reduce(const G160Params& p, const GnFuse* gnf, hipStream_t s) {
   // Round 6: the reduction is timed as its own bucket (it is HBM-bound glue, not part of the GEMM's MFMA time): the caller's
   // event pair is closed here and a new one covers the reduction launch(es); the caller's pfd_prof_end then closes this one.
-  // Algorithmic bytes: the fp32 slabs once + the f16 result (+ residual, + the normalised copy of the fused GroupNorm form).
+  // Algorithmic bytes: the f16 slabs once + the f16 result (+ residual, + the normalised copy of the fused GroupNorm form).
   if (pfd_prof_on()) {
     pfd_prof_end(s);
     const double mn = (double)p.M * p.N;
     pfd_prof_begin(21, 0.0, 2.0 * p.splits * mn + 2.0 * mn * (1 + (p.R ? 1 : 0) + (gnf ? 1 : 0)), s);
   }
   if (gnf) {   // (host: no gn_out / ln_out with it)
-    hipLaunchKernelGGL(splitk_reduce_gnorm_kernel, dim3(32 * (p.M / gnf->rows)), dim3(GNF_T), 0, s, p, *gnf);
+    hipLaunchKernelGGL(splitk_reduce_gnorm_kernel, dim3(32 * (p.M / gnf->rows)), dim3(GNS_T), 0, s, p, *gnf);
     return;
   }
   if (p.gn_out) {
@@ -2235,7 +2195,7 @@ int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s
   if (gnf) {
     const int cpg = d->N / 32;
     if (bn != 160 || (d->N % 32) || (cpg % 4) || cpg < 20 || cpg > 256 || d->gnf_rows <= 0 || (d->M % d->gnf_rows) ||
-        (long)d->gnf_rows * (cpg / 4) > (long)GNF_T * GNF_MAX || (long)(d->M / d->gnf_rows) * 32 < 128 || !d->gnf_gamma || !d->gnf_beta ||
+        (long)d->gnf_rows * (cpg / 4) > (long)GNS_T * GNS_MAX || (long)(d->M / d->gnf_rows) * 32 < 128 || !d->gnf_gamma || !d->gnf_beta ||
         (d->gnf_ldy & 3) || !aligned8(d->gnf_y) || d->act == PFD_ACT_GEGLU || d->Ct || d->ln_stats ||
         d->ln_out || d->gn_out || d->bias_per_row || !d->ws ||
         (d->gnf_act != PFD_ACT_NONE && d->gnf_act != PFD_ACT_SILU))

@@ -5,28 +5,14 @@
 // GroupNorm algorithmic HBM bytes per element: 2 (stats read) + 2 (apply read) + 2 (write).
 #include <stdlib.h>
 
-#include "pfd_common.h"
+#include "gn_stages.h"   // GnSrc, gn_load and every stage that more than one kernel has (also of gemm_glds.hip)
 
 namespace {
 
 constexpr int GN_MAX_CHUNKS = 256;
-constexpr int GN_MAX_G = 64;
 #ifndef GN_ROWS
 #define GN_ROWS 8   // rows a statistics thread keeps in flight
 #endif
-
-struct GnSrc {
-  const half_t* x1;
-  const half_t* x2;
-  long ld1, ld2;
-  int C1, C2;
-};
-
-__device__ __forceinline__ uint4 gn_load(const GnSrc& s, long row, int v) {
-  const int c = v * 8;
-  if (c < s.C1) return *reinterpret_cast<const uint4*>(s.x1 + row * s.ld1 + c);
-  return *reinterpret_cast<const uint4*>(s.x2 + row * s.ld2 + (c - s.C1));
-}
 
 // Thread (v, rt): owns 8 channels v*8.. (two vec slots when C > 2048) and rows rt, rt+RT, ...
 // of its chunk, so a wave's loads sweep contiguous memory when ld == C.
@@ -115,78 +101,12 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnSrc s, const half_t* __
   __shared__ float sc[4096], sh[4096];
   __shared__ float ra[256], rq[256], gmean[GN_MAX_G], grstd[GN_MAX_G];
   const int C = s.C1 + s.C2;
-  const int nvec = C / 8;
-  const int cpg = C / G;
-  const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
-  // finalize in the prologue (was a separate 5 us launch): every block reduces the nchunks x G
-  // partial sums of ITS sample (<= 64 KB, L2 resident) -- thread (part, g) sums chunks part, part+P, ...
-  {
-    const int P = 256 / G;
-    const int g = tid % G, part = tid / G;
-    float a = 0.f, q = 0.f;
-    if (part < P) {
-      for (int k = part; k < nchunks; k += P) {
-        const float2 v = *reinterpret_cast<const float2*>(partial + (((long)b * nchunks + k) * G + g) * 2);
-        a += v.x;
-        q += v.y;
-      }
-    }
-    ra[tid] = a;
-    rq[tid] = q;
-    __syncthreads();
-    if (tid < G) {
-      for (int k = 1; k < P; ++k) {
-        a += ra[k * G + tid];
-        q += rq[k * G + tid];
-      }
-      const float mean = a / count;
-      gmean[tid] = mean;
-      grstd[tid] = rsqrtf(fmaxf(q / count - mean * mean, 0.f) + eps);
-    }
-    __syncthreads();
-  }
-  for (int c = tid; c < C; c += 256) {
-    const int g = c / cpg;
-    const float mean = gmean[g];
-    const float rstd = grstd[g];
-    const float w = rstd * (float)gamma[c];
-    sc[c] = w;
-    sh[c] = (float)beta[c] - mean * w;
-  }
+  const int b = blockIdx.y;
+  // finalize in the prologue (was a separate 5 us launch): every block folds the partial sums of ITS sample
+  gn_fold_partials(partial, b, nchunks, G, count, eps, ra, rq, gmean, grstd);
+  gn_channel_maps(gamma, beta, gmean, grstd, C, C / G, sc, sh);
   __syncthreads();
-  const int VT = nvec < 256 ? nvec : 256;
-  const int RT = 256 / VT;
-  const int v0 = tid % VT, rt = tid / VT;
-  if (rt >= RT) return;
-  const int r_beg = chunk * rows_per_chunk;
-  const int r_end = min(HW, r_beg + rows_per_chunk);
-  for (int v = v0; v < nvec; v += 256) {
-    float w[8], o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      w[e] = sc[v * 8 + e];
-      o[e] = sh[v * 8 + e];
-    }
-    for (int r = r_beg + rt; r < r_end; r += 4 * RT) {
-      Pack16 p[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (r + u * RT < r_end) p[u].u = gn_load(s, (long)b * HW + r + u * RT, v);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (r + u * RT >= r_end) break;
-        const long row = (long)b * HW + r + u * RT;
-        Pack16 q;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float t = (float)p[u].e[e] * w[e] + o[e];
-          if (act == PFD_ACT_SILU) t = pfd_silu(t);
-          q.e[e] = (half_t)t;
-        }
-        gst_t<PFD_ST_NORM>(reinterpret_cast<uint4*>(y + row * ldy + v * 8), q.u);
-      }
-    }
-  }
+  gn_apply_rows<4>(s, sc, sh, y, ldy, HW, b, blockIdx.x, rows_per_chunk, act);
 }
 
 // ---- GroupNorm apply with the statistics of the PRODUCERS (pfd_groupnorm_pstats_f16, round 4) ----
@@ -194,7 +114,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnSrc s, const half_t* __
 // f16 values they stored (PfdGemmDesc.gn_out: st[(slab * (C_src / 160) + tile) * 16 + local group], slab = row / 64 over
 // the whole batch).  A group of THIS GroupNorm (cpg = (C1 + C2) / G channels of the virtual concat) is a whole number of
 // producer groups of one source (checked by the host), so its statistics are sums of producer partials: no pass over the
-// tensor.  Same apply loop as gn_apply_kernel.
+// tensor.  From the LDS stage of the fold on, gn_apply_kernel's stages (gn_stages.h).
 struct GnPStats {
   const float2* st1;
   const float2* st2;
@@ -205,7 +125,8 @@ struct GnPStats {
 // PAR (the default wherever npg <= 2, round 5): the fold of the partials issues the loads of eight slabs before the first
 // add instead of one dependent load per slab (64^2: 8 L2 round trips per block in front of the first row), and the apply
 // loop requests eight rows per round trip instead of four (a block's 64 rows at 64^2 x 320: two trips instead of three);
-// same values added in the same order -- `selftest --r5` compares the two forms bit for bit (281 checks green on MI355X).
+// same values added in the same order (the products of the grouped gather have a factor 0 or 1: exact) and every later stage
+// shared (gn_stages.h) -- `selftest --r5` compares the two forms bit for bit (281 checks green on MI355X).
 template <bool PAR>
 __global__ __launch_bounds__(256) void gn_apply_pstats_kernel(GnSrc s, GnPStats ps, const half_t* __restrict__ gamma,
                                                               const half_t* __restrict__ beta, half_t* __restrict__ y,
@@ -214,9 +135,8 @@ __global__ __launch_bounds__(256) void gn_apply_pstats_kernel(GnSrc s, GnPStats 
   __shared__ float sc[4096], sh[4096];
   __shared__ float ra[256], rq[256], gmean[GN_MAX_G], grstd[GN_MAX_G];
   const int C = s.C1 + s.C2;
-  const int nvec = C / 8;
   const int cpg = C / G;
-  const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+  const int b = blockIdx.y, tid = threadIdx.x;
   {
     const int nslab = HW / 64;
     const int P = 256 / G;
@@ -263,102 +183,25 @@ __global__ __launch_bounds__(256) void gn_apply_pstats_kernel(GnSrc s, GnPStats 
         }
       }
     }
-    ra[tid] = a;
-    rq[tid] = q;
-    __syncthreads();
-    if (tid < G) {
-      for (int k = 1; k < P; ++k) {
-        a += ra[k * G + tid];
-        q += rq[k * G + tid];
-      }
-      const float mean = a / count;
-      gmean[tid] = mean;
-      grstd[tid] = rsqrtf(fmaxf(q / count - mean * mean, 0.f) + eps);
-    }
-    __syncthreads();
+    gn_fold_lds(a, q, G, count, eps, ra, rq, gmean, grstd);
   }
-  for (int c = tid; c < C; c += 256) {
-    const int g = c / cpg;
-    const float w = grstd[g] * (float)gamma[c];
-    sc[c] = w;
-    sh[c] = (float)beta[c] - gmean[g] * w;
-  }
+  gn_channel_maps(gamma, beta, gmean, grstd, C, cpg, sc, sh);
   __syncthreads();
-  const int VT = nvec < 256 ? nvec : 256;
-  const int RT = 256 / VT;
-  const int v0 = tid % VT, rt = tid / VT;
-  if (rt >= RT) return;
-  const int r_beg = chunk * rows_per_chunk;
-  const int r_end = min(HW, r_beg + rows_per_chunk);
-  for (int v = v0; v < nvec; v += 256) {
-    float w[8], o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      w[e] = sc[v * 8 + e];
-      o[e] = sh[v * 8 + e];
-    }
-    constexpr int U = PAR ? 8 : 4;   // rows requested per round trip
-    for (int r = r_beg + rt; r < r_end; r += U * RT) {
-      Pack16 p[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (r + u * RT < r_end) p[u].u = gn_load(s, (long)b * HW + r + u * RT, v);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (r + u * RT >= r_end) break;
-        const long row = (long)b * HW + r + u * RT;
-        Pack16 qv;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float t = (float)p[u].e[e] * w[e] + o[e];
-          if (act == PFD_ACT_SILU) t = pfd_silu(t);
-          qv.e[e] = (half_t)t;
-        }
-        gst_t<PFD_ST_NORM>(reinterpret_cast<uint4*>(y + row * ldy + v * 8), qv.u);
-      }
-    }
-  }
+  gn_apply_rows<(PAR ? 8 : 4)>(s, sc, sh, y, ldy, HW, b, blockIdx.x, rows_per_chunk, act);   // rows requested per round trip
 }
 
 // GroupNorm folded into the consumer (pfd_groupnorm_table_f16): instead of writing the normalised tensor, write the
-// per-(sample, channel) affine map  y = x * scale + shift  as two planes [B][2][C]  (scale = rstd * gamma, shift = beta - mean * scale; the
-// same fp32 expressions, reduced in the same order, as gn_apply_kernel) -- the 3x3 patch convolution applies it
+// per-(sample, channel) affine map  y = x * scale + shift  as two planes [B][2][C]  (gn_apply_kernel's fold and channel maps,
+// gn_stages.h: the planes hold what that kernel keeps in LDS) -- the 3x3 patch convolution applies it
 // (+ SiLU) while it stages its input patch (gemm_glds.hip, conv3x3_patch_ws_kernel<true>).
 __global__ __launch_bounds__(256) void gn_table_kernel(const half_t* __restrict__ gamma, const half_t* __restrict__ beta,
                                                        const float* __restrict__ partial, float* __restrict__ table,
                                                        int C, int G, int nchunks, float count, float eps) {
   __shared__ float ra[256], rq[256], gmean[GN_MAX_G], grstd[GN_MAX_G];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int cpg = C / G;
-  const int P = 256 / G;
-  const int g = tid % G, part = tid / G;
-  float a = 0.f, q = 0.f;
-  if (part < P) {
-    for (int k = part; k < nchunks; k += P) {
-      const float2 v = *reinterpret_cast<const float2*>(partial + (((long)b * nchunks + k) * G + g) * 2);
-      a += v.x;
-      q += v.y;
-    }
-  }
-  ra[tid] = a;
-  rq[tid] = q;
-  __syncthreads();
-  if (tid < G) {
-    for (int k = 1; k < P; ++k) {
-      a += ra[k * G + tid];
-      q += rq[k * G + tid];
-    }
-    const float mean = a / count;
-    gmean[tid] = mean;
-    grstd[tid] = rsqrtf(fmaxf(q / count - mean * mean, 0.f) + eps);
-  }
-  __syncthreads();
-  for (int c = tid; c < C; c += 256) {
-    const int gg = c / cpg;
-    const float w = grstd[gg] * (float)gamma[c];
-    table[(long)b * 2 * C + c] = w;                                  // scale plane
-    table[(long)b * 2 * C + C + c] = (float)beta[c] - gmean[gg] * w;    // shift plane
-  }
+  const int b = blockIdx.x;
+  gn_fold_partials(partial, b, nchunks, G, count, eps, ra, rq, gmean, grstd);
+  float* planes = table + (long)b * 2 * C;
+  gn_channel_maps(gamma, beta, gmean, grstd, C, C / G, planes, planes + C);   // scale plane, shift plane
 }
 
 // ---- GroupNorm, small-slab form: one block per (sample, group) keeps the group's HW x C/G slab in
@@ -366,24 +209,17 @@ __global__ __launch_bounds__(256) void gn_table_kernel(const half_t* __restrict_
 // and the input is read once (4 B/element).  Serves the 8^2 / 16^2 / 32^2 UNet levels, where the
 // two-launch form is bound by launch latency (1280 @ 8^2: 10 us for 1.3 MB).  Needs (C/G) % 4 == 0.
 // 1024 threads per block since round 5 (four times fewer before): the launch is one round trip of the slab, so its time is set
-// by the loads a block has in flight.  The fused split-K reduction + GroupNorm of gemm_glds.hip (splitk_reduce_gnorm_kernel)
-// uses the SAME thread -> chunk mapping and the same order of the adds: the two give the same bits.
-#ifndef PFD_GN_THREADS
-#define PFD_GN_THREADS 1024   // (-DPFD_GN_THREADS=256: A/B builds)
-#endif
-constexpr int GNS_T = PFD_GN_THREADS;
-constexpr int GNS_MAX = 8192 / GNS_T;
-
+// by the loads a block has in flight (GNS_T, gn_stages.h).  The fused split-K reduction + GroupNorm of gemm_glds.hip
+// (splitk_reduce_gnorm_kernel) uses the SAME thread -> chunk mapping and calls the same statistics and normalisation stages.
 __global__ __launch_bounds__(GNS_T) void gn_small_kernel(GnSrc s, const half_t* __restrict__ gamma,
                                                        const half_t* __restrict__ beta, half_t* __restrict__ y,
                                                        long ldy, int HW, int G, int act, float eps) {
   __shared__ float red[2 * GNS_T / 64];
   const int C = s.C1 + s.C2;
   const int cpg = C / G, cpr = cpg / 4;
-  const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int total = HW * cpr;
   uint2 v[GNS_MAX];
-  float sm = 0.f, sq = 0.f;
 #pragma unroll
   for (int k = 0; k < GNS_MAX; ++k) {
     const int idx = tid + GNS_T * k;
@@ -395,8 +231,9 @@ __global__ __launch_bounds__(GNS_T) void gn_small_kernel(GnSrc s, const half_t* 
                       : *reinterpret_cast<const uint2*>(s.x2 + row * s.ld2 + (c - s.C1));
     }
   }
+  float sm = 0.f, sq = 0.f;
 #pragma unroll
-  for (int k = 0; k < GNS_MAX; ++k) {   // padding slots hold zeros: they add nothing to either sum
+  for (int k = 0; k < GNS_MAX; ++k) {   // padding slots hold zeros: they add nothing to either sum; f16 squares are exact in fp32
     Pack8 p;
     p.u = v[k];
 #pragma unroll
@@ -406,23 +243,8 @@ __global__ __launch_bounds__(GNS_T) void gn_small_kernel(GnSrc s, const half_t* 
       sq += x * x;
     }
   }
-  sm = wave_sum(sm);
-  sq = wave_sum(sq);
-  constexpr int NWV = GNS_T / 64;
-  if (lane == 0) {
-    red[wave] = sm;
-    red[NWV + wave] = sq;
-  }
-  __syncthreads();
-  const float count = (float)HW * (float)cpg;
-  float ts = red[0], tq = red[NWV];
-#pragma unroll
-  for (int w = 1; w < NWV; ++w) {
-    ts += red[w];
-    tq += red[NWV + w];
-  }
-  const float mean = ts / count;
-  const float rstd = rsqrtf(fmaxf(tq / count - mean * mean, 0.f) + eps);
+  float mean, rstd;
+  gn_slab_stats(sm, sq, HW, cpg, eps, red, mean, rstd);
 #pragma unroll
   for (int k = 0; k < GNS_MAX; ++k) {
     const int idx = tid + GNS_T * k;
@@ -434,10 +256,9 @@ __global__ __launch_bounds__(GNS_T) void gn_small_kernel(GnSrc s, const half_t* 
       be.u = *reinterpret_cast<const uint2*>(beta + c);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float w = rstd * (float)ga.e[e];
-        float t = (float)p.e[e] * w + ((float)be.e[e] - mean * w);
-        if (act == PFD_ACT_SILU) t = pfd_silu(t);
-        o.e[e] = (half_t)t;
+        float w, sh;
+        gn_affine(mean, rstd, (float)ga.e[e], (float)be.e[e], w, sh);
+        o.e[e] = gn_normalise((float)p.e[e], w, sh, act);
       }
       gst_t<PFD_ST_NORM>(reinterpret_cast<uint2*>(y + ((long)b * HW + r) * ldy + c), o.u);
     }
@@ -715,40 +536,47 @@ extern "C" size_t pfd_groupnorm_ws_bytes(int32_t B, int32_t C, int32_t HW) {
   return (size_t)B * (GN_MAX_CHUNKS + 1) * GN_MAX_G * 2 * sizeof(float);
 }
 
-extern "C" int pfd_groupnorm_f16(const void* x1, int32_t C1, int64_t ldx1, const void* x2, int32_t C2,
-                                 int64_t ldx2, const void* gamma, const void* beta, void* y, int64_t ldy,
-                                 int32_t B, int32_t HW, int32_t G, float eps, int32_t act, void* ws,
-                                 size_t ws_bytes, pfd_stream_t stream) {
-  if (!x1 || !gamma || !beta || !y || !ws) return PFD_EINVAL;
+// the argument checks pfd_groupnorm_f16 and pfd_groupnorm_table_f16 share, in their order (`out`: y | the table): PFD_OK or
+// the code of the first one that fails.  Each caller goes on with the alignment of what it writes, then its workspace.
+static int check_gn_src(const void* x1, int C1, int64_t ldx1, const void* x2, int C2, int64_t ldx2, const void* gamma,
+                        const void* beta, const void* out, const void* ws, int B, int HW, int G) {
+  if (!x1 || !gamma || !beta || !out || !ws) return PFD_EINVAL;
   if (C2 > 0 && !x2) return PFD_EINVAL;
   if (C2 < 0 || C1 <= 0 || B <= 0 || HW <= 0 || G <= 0 || G > GN_MAX_G) return PFD_EINVAL;
   const int C = C1 + C2;
   if ((C1 & 7) || (C2 & 7) || (C % G) || C > 4096) return PFD_ESHAPE;
-  if ((ldx1 & 7) || (ldx2 & 7) || (ldy & 7)) return PFD_EINVAL;
+  if ((ldx1 & 7) || (ldx2 & 7)) return PFD_EINVAL;
+  return PFD_OK;
+}
+
+extern "C" int pfd_groupnorm_f16(const void* x1, int32_t C1, int64_t ldx1, const void* x2, int32_t C2,
+                                 int64_t ldx2, const void* gamma, const void* beta, void* y, int64_t ldy,
+                                 int32_t B, int32_t HW, int32_t G, float eps, int32_t act, void* ws,
+                                 size_t ws_bytes, pfd_stream_t stream) {
+  if (const int rc = check_gn_src(x1, C1, ldx1, x2, C2, ldx2, gamma, beta, y, ws, B, HW, G)) return rc;
+  const int C = C1 + C2;
+  if (ldy & 7) return PFD_EINVAL;
   if (act != PFD_ACT_NONE && act != PFD_ACT_SILU) return PFD_EINVAL;
   if (ws_bytes < pfd_groupnorm_ws_bytes(B, C, HW)) return PFD_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   GnSrc src{(const half_t*)x1, (const half_t*)x2, ldx1, ldx2, C1, C2};
-  const bool prof = pfd_prof_on();
   if (gn_is_small(B, C, HW, G)) {  // narrower groups: 40-byte row segments, the two-launch form wins (640 @ 32^2: 15 vs 17 us)
-    if (prof) pfd_prof_begin(10, 8.0 * B * HW * C, 4.0 * B * HW * C, s);  // 2B read + 2B write
+    PfdProfScope prof_scope(10, 8.0 * B * HW * C, 4.0 * B * HW * C, s);  // 2B read + 2B write
     // (round 5: a form with incremental indices and gamma / beta in LDS -- 5419 -> 3172 instructions -- measured -0.04 %
     //  per batch, profiles/r05_e2e_ab_candidates.log: not kept; the fused split-K reduction + GroupNorm of gemm_glds.hip
     //  takes most of these launches instead)
     hipLaunchKernelGGL(gn_small_kernel, dim3(G, B), dim3(GNS_T), 0, s, src, (const half_t*)gamma, (const half_t*)beta,
                        (half_t*)y, (long)ldy, HW, G, act, eps);
-    if (prof) pfd_prof_end(s);
     return pfd_check_launch("pfd_groupnorm_f16(small)");
   }
   int nchunks, rpc;
   gn_chunks(B, C, HW, &nchunks, &rpc);
   float* partial = (float*)ws;
-  if (prof) pfd_prof_begin(10, 8.0 * B * HW * C, 6.0 * B * HW * C, s);  // 2B stats read + 2B read + 2B write
+  PfdProfScope prof_scope(10, 8.0 * B * HW * C, 6.0 * B * HW * C, s);  // 2B stats read + 2B read + 2B write
   hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunks, B), dim3(256), 0, s, src, HW, G, rpc, partial);
   hipLaunchKernelGGL(gn_apply_kernel, dim3(nchunks, B), dim3(256), 0, s, src, (const half_t*)gamma,
                      (const half_t*)beta, partial, (half_t*)y, (long)ldy, HW, G, rpc, act, nchunks,
                      (float)HW * (float)(C / G), eps);
-  if (prof) pfd_prof_end(s);
   return pfd_check_launch("pfd_groupnorm_f16");
 }
 
@@ -797,23 +625,18 @@ extern "C" int pfd_groupnorm_table_f16(const void* x1, int32_t C1, int64_t ldx1,
                                        int64_t ldx2, const void* gamma, const void* beta, void* table, int32_t B,
                                        int32_t HW, int32_t G, float eps, void* ws, size_t ws_bytes,
                                        pfd_stream_t stream) {
-  if (!x1 || !gamma || !beta || !table || !ws) return PFD_EINVAL;
-  if (C2 > 0 && !x2) return PFD_EINVAL;
-  if (C2 < 0 || C1 <= 0 || B <= 0 || HW <= 0 || G <= 0 || G > GN_MAX_G) return PFD_EINVAL;
+  if (const int rc = check_gn_src(x1, C1, ldx1, x2, C2, ldx2, gamma, beta, table, ws, B, HW, G)) return rc;
   const int C = C1 + C2;
-  if ((C1 & 7) || (C2 & 7) || (C % G) || C > 4096) return PFD_ESHAPE;
-  if ((ldx1 & 7) || (ldx2 & 7) || (reinterpret_cast<uintptr_t>(table) & 15)) return PFD_EINVAL;
+  if (reinterpret_cast<uintptr_t>(table) & 15) return PFD_EINVAL;
   if (ws_bytes < pfd_groupnorm_ws_bytes(B, C, HW)) return PFD_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   GnSrc src{(const half_t*)x1, (const half_t*)x2, ldx1, ldx2, C1, C2};
   int nchunks, rpc;
   gn_chunks(B, C, HW, &nchunks, &rpc);
-  const bool prof = pfd_prof_on();
-  if (prof) pfd_prof_begin(10, 4.0 * B * HW * C, 2.0 * B * HW * C, s);   // one read of the input
+  PfdProfScope prof_scope(10, 4.0 * B * HW * C, 2.0 * B * HW * C, s);   // one read of the input
   hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunks, B), dim3(256), 0, s, src, HW, G, rpc, (float*)ws);
   hipLaunchKernelGGL(gn_table_kernel, dim3(B), dim3(256), 0, s, (const half_t*)gamma, (const half_t*)beta,
                      (const float*)ws, (float*)table, C, G, nchunks, (float)HW * (float)(C / G), eps);
-  if (prof) pfd_prof_end(s);
   return pfd_check_launch("pfd_groupnorm_table_f16");
 }
 
