@@ -301,6 +301,28 @@ int pfd_attention_f16(const PfdAttnDesc* d, pfd_stream_t stream);
 int pfd_attention_kbias_f16(const PfdAttnDesc* d, const float* kbias, int64_t kb_bs, pfd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * The same attention with a logit per key that depends on the REGION of the query (regional
+ * reference mixing, lib/regions.py): query i of sample b lies in region g = qregion[b*qr_bs + i]
+ * and sees key j at the logit rbias[b*rb_bs + g*rb_rs + j]:
+ *   O[b,i,h,:] = sum_j 2^rbias[b,g,j] exp(s_ij) V[b,j,h,:] / sum_j 2^rbias[b,g,j] exp(s_ij)
+ *   rbias: fp32, log2 units, finite (>= -2^90) or -inf; nr rows per sample, 1 <= nr <= 8;
+ *     16-byte aligned, rb_rs % 4 == 0, rb_rs >= Nk, rb_bs % 4 == 0 and rb_bs >= nr*rb_rs, or
+ *     rb_bs == 0 for one table shared by the batch.  Elements j >= Nk of a row are never read.
+ *   qregion: one byte per query, values < nr (a larger one is read as nr - 1); qr_bs >= Nq, or
+ *     qr_bs == 0 for one map shared by the batch.
+ *   Contract (weaker than "key 0 is finite" above): for every sample, every region id that
+ *     occurs among its queries has at least one finite key; whole leading key tiles may be
+ *     masked.  K and V of a -inf key must be finite.  2^-28 < scale * log2(e) < 2^10.
+ *   For a region whose row has key 0 finite, the outputs of its queries are the bits of
+ *     pfd_attention_kbias_f16 with that row wherever both launch the same kernel class.
+ *   D in {40, 80, 160} (PFD_ESHAPE otherwise); there is no folded 8-wave build: the 4-wave
+ *     d = 40 kernel serves every d = 40 shape.  PFD_EINVAL for NULL / misaligned pointers,
+ *     strides as above, nr outside 1..8, and everything pfd_attention_f16 answers it for.
+ * ---------------------------------------------------------------------------------- */
+int pfd_attention_rbias_f16(const PfdAttnDesc* d, const float* rbias, int64_t rb_rs, int64_t rb_bs, int nr,
+                            const uint8_t* qregion, int64_t qr_bs, pfd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Swin (shifted-)window attention core for one image: pad to multiples of `ws`, cyclic
  * roll by -shift, window partition, q*scale, QK^T + relative-position bias + shift mask
  * (-100, not -inf), softmax, .V, window reverse, roll back, crop -- all as index math.

@@ -82,10 +82,25 @@ namespace {
 //    every p is exp2(-inf) = 0 and -- K and V being finite by contract -- the accumulators and the row sum stay as they were.
 //    Key 0 is finite by contract, so the running maximum is finite from the first tile on and (-inf) - (-inf) never occurs.
 //    Without KBIAS nothing of this is compiled: the kernels of pfd_attention_f16 are the code they were (tools/isa_diff.py).
-// (the kernel text is attention2_kernel.inc, compiled once without the key logits and once with them)
+//  * RBIAS (pfd_attention_rbias_f16): the logit row depends on the REGION of the query -- a table rbias[b, g, j] of nr <= 8 rows and
+//    one region id per query.  In the S^T layout a lane IS a query (l31), so the only change to the arithmetic is WHICH row the
+//    accumulator start reads: all nr rows of a tile are staged (row g by wave g % NWAVES, one LDS-DMA dword load each, 2 x 8 x 256
+//    bytes of LDS), and the four 16-byte reads per 32-key half go to row `region of this lane` -- no broadcasts any more (lanes of
+//    one region still share an address).  The block's QB region ids are staged into LDS once (as row offsets, clamped to nr - 1)
+//    and the lane re-reads its own per tile from an opaque index: kept live across the loop it would cost the d = 40 build a
+//    register it does not have.  Built for the unfolded classes only (4 waves at d = 40, d = 80, d = 160); the 4-wave build
+//    serves the shapes the folded 8-wave one takes elsewhere.
+//    Fully masked LEADING tiles are legal here (a region that uses only the second reference masks the whole first tile), so
+//    "key 0 is finite" is replaced by "every region that occurs keeps one finite key somewhere", and the running maximum starts
+//    at a finite -2^100 log2 units instead of -inf: see the comment at m_run in the kernel text for why no (-inf) - (-inf) occurs,
+//    lane by lane (one wave holds queries of regions that start on different tiles).  For a region whose key 0 is finite every
+//    value of the lane's column is what attention_kbias_kernel computes from that row: alpha of the first tile is exp2(-huge) = 0
+//    there and exp2(-inf) = 0 here, and a rescale another lane of the wave asks for multiplies this lane by alpha = 1.
+// (the kernel text is attention2_kernel.inc, compiled once without the key logits, once with them and once with a row per region)
 #define ATTN2_KERNEL_NAME attention2_kernel
 #define ATTN2_PARAMS AttnParams
 #define ATTN2_KBIAS false
+#define ATTN2_RBIAS false
 #include "attention2_kernel.inc"
 #undef ATTN2_KERNEL_NAME
 #undef ATTN2_PARAMS
@@ -96,7 +111,15 @@ namespace {
 #include "attention2_kernel.inc"
 #undef ATTN2_KERNEL_NAME
 #undef ATTN2_PARAMS
+#undef ATTN2_RBIAS
+#define ATTN2_KERNEL_NAME attention_rbias_kernel
+#define ATTN2_PARAMS AttnParamsRB
+#define ATTN2_RBIAS true
+#include "attention2_kernel.inc"
+#undef ATTN2_KERNEL_NAME
+#undef ATTN2_PARAMS
 #undef ATTN2_KBIAS
+#undef ATTN2_RBIAS
 
 // ------------------------------------------------------------------------------------------------
 // d = 512, one head: the VAE mid-block attention (autokl_modules.py:186-197).  Same transposed formulation
@@ -351,6 +374,20 @@ int launch_kbias(const AttnParamsKB& p, hipStream_t s) {
   return pfd_check_launch("pfd_attention_kbias_f16");
 }
 
+// pfd_attention_rbias_f16: launch_kbias<D>'s rule without the folded 8-wave build (not compiled with a row per region): the
+// 4-wave d = 40 build takes those shapes too
+template <int D>
+int launch_rbias(const AttnParamsRB& p, hipStream_t s) {
+  const bool prof = pfd_prof_on();
+  if (prof)
+    pfd_prof_begin(8, 4.0 * p.B * p.H * (double)p.Nq * p.Nk * D,
+                   2.0 * p.B * p.H * D * (2.0 * p.Nq + 2.0 * p.Nk), s);
+  dim3 grid(((p.Nq + 127) / 128) * p.H * p.B);
+  hipLaunchKernelGGL((attention_rbias_kernel<D, 4, false>), grid, dim3(256), 0, s, p);
+  if (prof) pfd_prof_end(s);
+  return pfd_check_launch("pfd_attention_rbias_f16");
+}
+
 int check_desc(const PfdAttnDesc* d) {
   if (!d || !d->Q || !d->K || !d->Vt || !d->O) return PFD_EINVAL;
   if (d->B <= 0 || d->H <= 0 || d->Nq <= 0 || d->Nk <= 0) return PFD_EINVAL;
@@ -387,6 +424,36 @@ extern "C" int pfd_attention_kbias_f16(const PfdAttnDesc* d, const float* kbias,
     case 40: return launch_kbias<40>(p, s);
     case 80: return launch_kbias<80>(p, s);
     case 160: return launch_kbias<160>(p, s);
+    default: return PFD_ESHAPE;
+  }
+}
+
+extern "C" int pfd_attention_rbias_f16(const PfdAttnDesc* d, const float* rbias, int64_t rb_rs, int64_t rb_bs, int nr,
+                                       const uint8_t* qregion, int64_t qr_bs, pfd_stream_t stream) {
+  if (const int rc = check_desc(d)) return rc;
+  if (nr < 1 || nr > ATTN_MAX_REGIONS) return PFD_EINVAL;
+  if (!rbias || (reinterpret_cast<uintptr_t>(rbias) & 15) || (rb_rs & 3) || rb_rs < d->Nk) return PFD_EINVAL;
+  if ((rb_bs & 3) || (rb_bs != 0 && rb_bs < (int64_t)nr * rb_rs)) return PFD_EINVAL;   // 0: one table for the batch
+  if (!qregion || (qr_bs != 0 && qr_bs < d->Nq)) return PFD_EINVAL;
+  if (!(d->scale > 0.f)) return PFD_EINVAL;
+  AttnParamsRB p;
+  fill_params(d, p);
+  p.rbias = rbias;
+  p.rb_rs = rb_rs;
+  p.rb_bs = rb_bs;
+  p.qregion = qregion;
+  p.qr_bs = qr_bs;
+  p.nr = nr;
+  p.inv_scale_log2 = 1.0f / p.scale_log2;
+  p.m_start = -0x1p100f * p.inv_scale_log2;   // -2^100 log2 units as a raw score
+  // (the start value must be finite as a raw score, 2^100 / (scale log2 e) < 2^128, and far below every real score; the header
+  //  states the range it promises, 2^-28 < scale log2 e < 2^10 -- the head sizes served have scale = d^-1/2)
+  if (!(p.scale_log2 > 0x1p-28f) || !(p.scale_log2 < 0x1p10f)) return PFD_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  switch (d->D) {
+    case 40: return launch_rbias<40>(p, s);
+    case 80: return launch_rbias<80>(p, s);
+    case 160: return launch_rbias<160>(p, s);
     default: return PFD_ESHAPE;
   }
 }

@@ -1,10 +1,13 @@
-// The body of attention2_kernel (csrc/attention.hip holds its description), compiled twice from there:
-//   ATTN2_KERNEL_NAME = attention2_kernel,      ATTN2_PARAMS = AttnParams,   ATTN2_KBIAS = false   (pfd_attention_f16)
-//   ATTN2_KERNEL_NAME = attention_kbias_kernel, ATTN2_PARAMS = AttnParamsKB, ATTN2_KBIAS = true    (pfd_attention_kbias_f16)
+// The body of attention2_kernel (csrc/attention.hip holds its description), compiled three times from there:
+//   ATTN2_KERNEL_NAME = attention2_kernel,      ATTN2_PARAMS = AttnParams,   ATTN2_KBIAS = false                      (pfd_attention_f16)
+//   ATTN2_KERNEL_NAME = attention_kbias_kernel, ATTN2_PARAMS = AttnParamsKB, ATTN2_KBIAS = true                       (pfd_attention_kbias_f16)
+//   ATTN2_KERNEL_NAME = attention_rbias_kernel, ATTN2_PARAMS = AttnParamsRB, ATTN2_KBIAS = true, ATTN2_RBIAS = true   (pfd_attention_rbias_f16)
 // (why two __global__ templates from one text and not a fifth template parameter: DESIGN.md 3.20)
 template <int D, int NWAVES, bool PV16, bool FOLD = false>
 __global__ __launch_bounds__(NWAVES * 64, (D <= 40 ? 4 : 1)) void ATTN2_KERNEL_NAME(const ATTN2_PARAMS p) {
   constexpr bool KBIAS = ATTN2_KBIAS;
+  constexpr bool RBIAS = ATTN2_RBIAS;   // the logits of a key depend on the region of the query: KBIAS with a row per region
+  static_assert(!RBIAS || (KBIAS && !FOLD), "the regional build stages rows like KBIAS; no folded form of it is built");
   static_assert(!PV16 || D == 40, "the 16x16x32 PV path is laid out for d = 40 (48 padded rows, row 40 = ones)");
   static_assert(!FOLD || D == 40, "the folded maximum uses contraction slot 40 of the d = 40 build (DQK = 48)");
   constexpr int KV_TILE = 64, NU = 2;
@@ -25,8 +28,10 @@ __global__ __launch_bounds__(NWAVES * 64, (D <= 40 ? 4 : 1)) void ATTN2_KERNEL_N
   constexpr int V_PT = (V_CHUNKS + NTHR - 1) / NTHR;
   constexpr int K_TILE_HALFS = KV_TILE * K_LD;
   constexpr int V_TILE_HALFS = DV * VT_LD;
-  constexpr int KB_HALFS = KBIAS ? 2 * KV_TILE * 2 : 0;   // two stages of 64 fp32 key logits behind the V^T images
-  __shared__ __attribute__((aligned(16))) half_t lds[2 * K_TILE_HALFS + 2 * V_TILE_HALFS + KB_HALFS];
+  constexpr int KB_ROWS = RBIAS ? ATTN_MAX_REGIONS : 1;
+  constexpr int KB_HALFS = KBIAS ? 2 * KB_ROWS * KV_TILE * 2 : 0;   // two stages of (rows of) 64 fp32 key logits behind the V^T images
+  constexpr int RG_HALFS = RBIAS ? QB * 2 : 0;            // RBIAS: per query of the block, where its region's row starts in a stage
+  __shared__ __attribute__((aligned(16))) half_t lds[2 * K_TILE_HALFS + 2 * V_TILE_HALFS + KB_HALFS + RG_HALFS];
   half_t* const Ks = lds;
   half_t* const Vts = lds + 2 * K_TILE_HALFS;
 
@@ -39,6 +44,13 @@ __global__ __launch_bounds__(NWAVES * 64, (D <= 40 ? 4 : 1)) void ATTN2_KERNEL_N
   const int b = bh / p.H, h = bh - b * p.H;
   const int q_row = qb * QB + wave * 32 + l31;
 
+  if constexpr (RBIAS) {
+    // the region of each of the block's QB queries, once, as the float offset of its row inside a stage (ids are clamped to the
+    // rows that are staged: the host refuses others, and a wild byte must not read LDS nobody wrote).  Visible behind the barrier
+    // of the clear below; compute_tile re-reads its lane's entry per tile instead of keeping it live across the loop.
+    int* const Rg = reinterpret_cast<int*>(lds + 2 * K_TILE_HALFS + 2 * V_TILE_HALFS + KB_HALFS);
+    if (tid < QB) Rg[tid] = min((int)attn_qregion(p, b)[min(qb * QB + tid, p.Nq - 1)], attn_nr(p) - 1) * KV_TILE;
+  }
   static_assert((2 * K_TILE_HALFS + 2 * V_TILE_HALFS) % 8 == 0, "16-byte clears");
   for (int i = tid; i < (2 * K_TILE_HALFS + 2 * V_TILE_HALFS) / 8; i += NTHR)
     reinterpret_cast<uint4*>(lds)[i] = make_uint4(0, 0, 0, 0);
@@ -80,7 +92,11 @@ __global__ __launch_bounds__(NWAVES * 64, (D <= 40 ? 4 : 1)) void ATTN2_KERNEL_N
   for (int i = 0; i < (PV16 ? NDT : 1); ++i)
 #pragma unroll
     for (int q = 0; q < 2; ++q) o16[i][q] = (float4_t){0.f, 0.f, 0.f, 0.f};
-  float m_run = FOLD ? 0.f : -INFINITY, l_run = 0.f;
+  // RBIAS: a query whose region masks the leading key tiles meets mx = -inf there.  Its running maximum therefore starts at a
+  // large FINITE negative value (p.m_start, -2^100 log2 units) and is finite ever after: m_new = fmaxf(finite, .) is finite, a
+  // masked tile leaves it alone and gives p = exp2(fma(-inf, c, finite)) = 0, the first live tile rescales the (zero)
+  // accumulators by exp2(-huge) = 0 exactly as the start at -inf does.  No (-inf) - (-inf) can be formed, per lane.
+  float m_run = FOLD ? 0.f : (RBIAS ? attn_m_start(p) : -INFINITY), l_run = 0.f;
 
   const half_t* kbase = p.K + (long)b * p.k_bs + h * D;
   const half_t* vbase = p.Vt + (long)h * D * p.ldvt + (long)b * p.vt_bs;
@@ -142,7 +158,19 @@ __global__ __launch_bounds__(NWAVES * 64, (D <= 40 ? 4 : 1)) void ATTN2_KERNEL_N
   // (src = a wave-uniform base + a lane offset taken from an opaque value at every call: otherwise the loop carries a
   //  per-thread 64-bit pointer and a per-thread tile counter -- three registers the d = 40 build spills for)
   auto stage_kbias = [&](const float* base, int off_max, int kv0) __attribute__((always_inline)) {
-    if (__builtin_amdgcn_readfirstlane(wave) == 0) {
+    if constexpr (RBIAS) {   // row g of the table by wave g % NWAVES: one LDS-DMA dword load per row, into row g of the stage
+      int ln = tid;
+      asm volatile("" : "+v"(ln));
+      const int w0 = __builtin_amdgcn_readfirstlane(ln >> 6);
+#pragma unroll
+      for (int i = 0; i < (ATTN_MAX_REGIONS + NWAVES - 1) / NWAVES; ++i) {
+        const int g = w0 + i * NWAVES;
+        if (g < attn_nr(p))
+          __builtin_amdgcn_global_load_lds(
+              (const __attribute__((address_space(1))) void*)(base + (long)g * attn_rb_rs(p) + min(ln & 63, off_max)),
+              (__attribute__((address_space(3))) void*)(Kbs + (((kv0 >> 6) & 1) * KB_ROWS + g) * KV_TILE), 4, 0, 0);
+      }
+    } else if (__builtin_amdgcn_readfirstlane(wave) == 0) {
       int ln = tid;
       asm volatile("" : "+v"(ln));
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + min(ln & 63, off_max)),
@@ -226,13 +254,21 @@ __global__ __launch_bounds__(NWAVES * 64, (D <= 40 ? 4 : 1)) void ATTN2_KERNEL_N
     const half_t* Kt = Ks + stage * K_TILE_HALFS;
     const half_t* Vt = Vts + stage * V_TILE_HALFS;
     float16_t st[NU];
+    int roff = 0;             // RBIAS: the row of the lane's own region (the reads below are then no broadcasts)
+    if constexpr (RBIAS) {
+      int tq = tid;
+      asm volatile("" : "+v"(tq));
+      roff = reinterpret_cast<const int*>(Kbs + 2 * KB_ROWS * KV_TILE)[(tq >> 6) * 32 + (tq & 31)];
+    }
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
       if constexpr (KBIAS) {
         // the accumulator STARTS at the key's logit, in the units of the score: the QK^T MFMAs add it for nothing, and the
         // four broadcast 16-byte reads land in the registers that are the accumulator anyway (rows (r & 3) + 8 (r >> 2) + 4 hi
-        // are four runs of four consecutive keys)
-        const float* kb = Kbs + stage * KV_TILE + u * 32 + 4 * hi;
+        // are four runs of four consecutive keys).  RBIAS: the same four reads from the row of the lane's region -- a broadcast
+        // only among the lanes of one region; rows are 256 bytes apart, so lanes of different regions meet in the same banks
+        // and a read takes up to as many passes as there are regions in the half-wave (measured: profiles/regions.md)
+        const float* kb = Kbs + stage * (KB_ROWS * KV_TILE) + roff + u * 32 + 4 * hi;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const float4_t bv = *reinterpret_cast<const float4_t*>(kb + 8 * g);

@@ -66,6 +66,7 @@ SIGNATURES = {
     "pfd_gemm_geglu_group": (_i32, [_i32]),
     "pfd_attention_f16": (_i32, [C.POINTER(PfdAttnDesc), _vp]),
     "pfd_attention_kbias_f16": (_i32, [C.POINTER(PfdAttnDesc), _vp, _i64, _vp]),
+    "pfd_attention_rbias_f16": (_i32, [C.POINTER(PfdAttnDesc), _vp, _i64, _i64, _i32, _vp, _i64, _vp]),
     "pfd_swin_window_attention_f16": (_i32, [C.POINTER(PfdSwinAttnDesc), _vp]),
     "pfd_groupnorm_ws_bytes": (_sz, [_i32, _i32, _i32]),
     "pfd_groupnorm_table_f16": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _sz,

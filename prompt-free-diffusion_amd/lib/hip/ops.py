@@ -563,11 +563,52 @@ def _chk_kbias(kbias, kb_bs, B, Nk, device):
     return kb_bs
 
 
-def attention(q, k, vt, B, H, Nq, Nk, D, scale, *, ldq, ldk, ldvt, q_bs, k_bs, vt_bs, out=None, kbias=None, kb_bs=None):
+MAX_REGIONS = 8
+
+
+def _chk_rbias(rbias, qregion, B, Nq, Nk, device):
+    """the operands of pfd_attention_rbias_f16.  rbias: fp32 [B, NR, rb_rs] (or [1, NR, rb_rs]: one table for the batch) on
+    `device`, contiguous, 16-byte aligned, rb_rs % 4 == 0 and >= Nk, 1 <= NR <= 8.  qregion: uint8 [B, >= Nq] (a column slice
+    of a wider matrix is fine) or [>= Nq] (one map for the batch) on `device`; its values must be < NR, which the caller checks on the host where the map is
+    made (lib/regions.region_grid): nothing is read back here.  -> (rb_rs, rb_bs, NR, qr_bs)"""
+    if rbias is None or qregion is None:
+        raise ValueError("attention: rbias and qregion come together")
+    if not isinstance(rbias, torch.Tensor) or rbias.dtype != torch.float32:
+        raise TypeError(f"attention rbias: expected a float32 tensor, got {getattr(rbias, 'dtype', type(rbias).__name__)}")
+    if not isinstance(qregion, torch.Tensor) or qregion.dtype != torch.uint8:
+        raise TypeError(f"attention qregion: expected a uint8 tensor, got {getattr(qregion, 'dtype', type(qregion).__name__)}")
+    if not rbias.is_cuda or not qregion.is_cuda:
+        raise RuntimeError("attention rbias / qregion: tensor on the CPU (no CPU fallback)")
+    if rbias.device != device or qregion.device != device:
+        raise ValueError(f"attention rbias / qregion: on {rbias.device} / {qregion.device}, the operands are on {device}")
+    if not rbias.is_contiguous() or qregion.stride(-1) != 1 or (qregion.dim() == 1 and not qregion.is_contiguous()):
+        raise ValueError("attention rbias / qregion: rbias must be contiguous, the bytes of a map consecutive")
+    if rbias.dim() != 3 or rbias.shape[0] not in (1, B):
+        raise ValueError(f"attention rbias: expected [{B}, NR, rb_rs] or [1, NR, rb_rs], got {tuple(rbias.shape)}")
+    NR, rb_rs = int(rbias.shape[1]), int(rbias.shape[2])
+    if not 1 <= NR <= MAX_REGIONS:
+        raise ValueError(f"attention rbias: between 1 and {MAX_REGIONS} regions, got {NR}")
+    if rb_rs % 4 or rb_rs < Nk:
+        raise ValueError(f"attention rbias: row length {rb_rs} must be a multiple of 4 and at least Nk = {Nk}")
+    if rbias.data_ptr() % 16:
+        raise ValueError("attention rbias: must start on a 16-byte boundary")
+    if qregion.dim() not in (1, 2) or qregion.shape[-1] < Nq or (qregion.dim() == 2 and qregion.shape[0] not in (1, B)):
+        raise ValueError(f"attention qregion: expected [{B}, >= {Nq}] or [>= {Nq}], got {tuple(qregion.shape)}")
+    rb_bs = NR * rb_rs if rbias.shape[0] == B and B > 1 else 0
+    qr_bs = int(qregion.stride(0)) if qregion.dim() == 2 and qregion.shape[0] == B and B > 1 else 0   # (rows of a wider matrix are fine)
+    if qr_bs and qr_bs < Nq:
+        raise ValueError(f"attention qregion: rows {qr_bs} bytes apart hold no {Nq} queries")
+    return rb_rs, rb_bs, NR, qr_bs
+
+
+def attention(q, k, vt, B, H, Nq, Nk, D, scale, *, ldq, ldk, ldvt, q_bs, k_bs, vt_bs, out=None, kbias=None, kb_bs=None,
+              rbias=None, qregion=None):
     """Fused attention; see pfd_attention_f16.  q/k/vt may be views into wider buffers; out (optional): [>= B*Nq, >= H*D]
     rows of stride % 8 == 0 (a column slice of a wider matrix is fine), the first B*Nq rows and H*D columns are written.
     kbias (optional): fp32 per-key logits in log2 units, element (b, j) at kbias.view(-1)[b * kb_bs + j] (kb_bs defaults to the
-    row length of a [B, kb_bs] matrix); see pfd_attention_kbias_f16.  None is the plain entry point, exactly."""
+    row length of a [B, kb_bs] matrix); see pfd_attention_kbias_f16.  None is the plain entry point, exactly.
+    rbias, qregion (optional, together, not with kbias): fp32 [B, NR, rb_rs] logits per region and key and the uint8 region of every
+    query, [B, >= Nq] or [>= Nq]; see pfd_attention_rbias_f16 and _chk_rbias."""
     _chk16(q, "attention q")
     _chk16(k, "attention k")
     _chk16(vt, "attention vt")
@@ -575,6 +616,11 @@ def attention(q, k, vt, B, H, Nq, Nk, D, scale, *, ldq, ldk, ldvt, q_bs, k_bs, v
         kb_bs = _chk_kbias(kbias, kb_bs, B, Nk, q.device)
     elif kb_bs is not None:
         raise ValueError("attention: kb_bs without kbias")
+    rb = None
+    if rbias is not None or qregion is not None:
+        if kbias is not None:
+            raise ValueError("attention: kbias and rbias exclude each other (one region IS the per-key operand)")
+        rb = _chk_rbias(rbias, qregion, B, Nq, Nk, q.device)
     if out is None:
         out = torch.empty((B * Nq, H * D), dtype=torch.float16, device=q.device)
     else:
@@ -591,6 +637,11 @@ def attention(q, k, vt, B, H, Nq, Nk, D, scale, *, ldq, ldk, ldvt, q_bs, k_bs, v
     if kbias is not None:
         _b.check(_lib().pfd_attention_kbias_f16(_byref(d), kbias.data_ptr(), kb_bs, _stream()),
                  f"pfd_attention_kbias_f16 B{B} H{H} Nq{Nq} Nk{Nk} D{D}")
+        return out
+    if rb is not None:
+        rb_rs, rb_bs, NR, qr_bs = rb
+        _b.check(_lib().pfd_attention_rbias_f16(_byref(d), rbias.data_ptr(), rb_rs, rb_bs, NR, qregion.data_ptr(), qr_bs, _stream()),
+                 f"pfd_attention_rbias_f16 B{B} H{H} Nq{Nq} Nk{Nk} D{D} NR{NR}")
         return out
     _b.check(_lib().pfd_attention_f16(_byref(d), _stream()), f"pfd_attention_f16 B{B} H{H} Nq{Nq} Nk{Nk} D{D}")
     return out

@@ -43,9 +43,15 @@ class ContextKV:
     aligned (pfd_attention_f16 contract).
     bias (optional): fp32 [B, Nk] per-key logits in log2 units (lib/refmix.key_bias: several references mixed in one pass,
     -inf on keys that are padding); kept as [B, Nkp] with -inf next to the zero context rows and passed to every
-    cross-attention (pfd_attention_kbias_f16).  Key 0 of every sample must be finite, the context rows of -inf keys too."""
+    cross-attention (pfd_attention_kbias_f16).  Key 0 of every sample must be finite, the context rows of -inf keys too.
+    regions (optional, not with bias): (table, qmaps, sizes) -- regional mixing, lib/regions.py.  table: fp32 [B, NR, Nk]
+    logits per region and key (regions.region_bias), kept as [B, NR, Nkp] with -inf next to the zero context rows; qmaps: uint8
+    [B, sum(sizes)] on the device, the region of every query of every query-grid size side by side (regions.region_grid per
+    level, made on the host BEFORE any graph capture: nothing is built here or later); sizes: the token counts h * w of those
+    grids, distinct.  A cross-attention over N queries takes the map of size N (pfd_attention_rbias_f16); a size that is not
+    there is an error.  Every region that occurs keeps a finite key."""
 
-    def __init__(self, context, bias=None):
+    def __init__(self, context, bias=None, regions=None):
         L._require_gpu(context, "HIP path: context must be on the GPU (no CPU fallback)")
         B, Nk, Cd = context.shape
         self.B, self.Nk, self.Cd = B, Nk, Cd
@@ -56,6 +62,27 @@ class ContextKV:
                 raise ValueError(f"ContextKV: bias must be a float tensor [{B}, {Nk}], one logit per key")
             self.bias = torch.full((B, self.Nkp), float('-inf'), dtype=torch.float32, device=context.device)
             self.bias[:, :Nk] = bias.to(device=context.device, dtype=torch.float32)
+        self.rtable = self.qmaps = None
+        self.rsizes = {}
+        if regions is not None:
+            if bias is not None:
+                raise ValueError("ContextKV: a per-key bias and regions exclude each other (one region IS the per-key bias)")
+            table, qmaps, sizes = regions
+            if not torch.is_tensor(table) or table.dim() != 3 or table.shape[0] != B or table.shape[2] != Nk or \
+                    not 1 <= table.shape[1] <= 8 or not table.is_floating_point():
+                raise ValueError(f"ContextKV: the region table must be a float tensor [{B}, NR <= 8, {Nk}]")
+            sizes = [int(n) for n in sizes]
+            if not torch.is_tensor(qmaps) or qmaps.dtype != torch.uint8 or tuple(qmaps.shape) != (B, sum(sizes)) or \
+                    len(set(sizes)) != len(sizes) or qmaps.device != context.device or not qmaps.is_contiguous():
+                raise ValueError(f"ContextKV: the region maps must be uint8 [{B}, {sum(sizes)}] on {context.device}, one "
+                                 f"map per distinct grid size {sizes}")
+            self.rtable = torch.full((B, table.shape[1], self.Nkp), float('-inf'), dtype=torch.float32, device=context.device)
+            self.rtable[:, :, :Nk] = table.to(device=context.device, dtype=torch.float32)
+            self.qmaps = qmaps
+            off = 0
+            for n in sizes:
+                self.rsizes[n] = off
+                off += n
         ctx = torch.zeros((B, self.Nkp, Cd), dtype=torch.float16, device=context.device)
         ctx[:, :Nk] = context.to(torch.float16)
         self.ctx2d = ctx.view(B * self.Nkp, Cd)
@@ -65,6 +92,19 @@ class ContextKV:
         # returns exactly to_out.bias and the q / attention / out-projection work is skipped
         # (SURVEY 8a exact saving (i); verified bit-identical in tests/test_hip_parity.py)
         self.zero_lead = 0
+
+    def logit_args(self, N, z=0):
+        """the keyword arguments of ops.attention that carry the logits for a launch over samples z .. B - 1 with N queries
+        each: none, kbias (per key) or rbias + qregion (per region; the map of the grid with N cells)"""
+        if self.bias is not None:
+            return dict(kbias=self.bias[z:], kb_bs=self.Nkp)
+        if self.rtable is None:
+            return {}
+        off = self.rsizes.get(int(N))
+        if off is None:
+            raise ValueError(f"ContextKV: no region map for a grid of {N} queries (maps exist for {sorted(self.rsizes)}): all "
+                             f"maps are made with the context, none later")
+        return dict(rbias=self.rtable[z:], qregion=self.qmaps[z:, off:off + int(N)])
 
     def get(self, attn):
         ent = self._kv.get(id(attn))
@@ -92,7 +132,7 @@ class ContextMix:
 
     def mix(self, modules, h, emb):
         assert len(modules) == len(self.contexts)
-        if any(getattr(c, 'bias', None) is not None for c in self.contexts):
+        if any(getattr(c, 'bias', None) is not None or getattr(c, 'rtable', None) is not None for c in self.contexts):
             raise ValueError("ContextMix takes no per-key bias: it mixes transformer outputs, not keys")
         if self.mixing_type == 'layer':
             ni = npr.choice(len(modules), p=self.ratios)
@@ -104,18 +144,18 @@ class ContextMix:
         return out
 
 
-def as_context_kv(context, bias=None):
+def as_context_kv(context, bias=None, regions=None):
     if isinstance(context, ContextMix):
-        if bias is not None:
+        if bias is not None or regions is not None:
             raise ValueError("ContextMix takes no per-key bias")
         return context
     if context is None or isinstance(context, ContextKV):
-        if bias is not None:
+        if bias is not None or regions is not None:
             raise ValueError("a per-key bias goes with a context tensor, not with a prepared context")
         return context
     if isinstance(context, (list, tuple)):
         context = context[0]
-    return ContextKV(context, bias)
+    return ContextKV(context, bias) if regions is None else ContextKV(context, bias, regions)
 
 
 class GEGLU(nn.Module, L._Packed):
@@ -267,7 +307,8 @@ class CrossAttention(nn.Module, L._Packed):
             k, vt = context.get(self)
             # per-key logits (several references in one pass): sliced [z:] like K; the zero-context shortcut stays what it
             # is -- with K = V = 0 the weights of those samples cannot matter
-            kb = {} if context.bias is None else dict(kbias=context.bias[z:], kb_bs=context.Nkp)
+            # (regional mixing: the table and the map of this grid size the same way)
+            kb = context.logit_args(N, z)
             if single:
                 w_o, b_o = self.to_out[0]._pk()
                 out = torch.empty((B * N, res.shape[1]), dtype=torch.float16, device=res.device)

@@ -61,6 +61,14 @@ ControlNet attends with them (pfd_attention_kbias_f16).  Every solver, seeded no
 The bias is one more static graph input behind the others and the graph key gains a trailing element.  This is not the
 reference's context_mixing: the multi-context loop stays what it is and refuses a bias.  Without a bias every path, launch
 sequence and graph key is what it was.
+
+Regional mixing (opt-in, instead of key_bias): c_info['region_bias'], fp32 [bs, NR, Nk] -- a row of logits per region
+(lib/regions.region_bias) -- with c_info['region_map'], uint8 [Hm, Wm], [bs, Hm, Wm] or a list of bs maps, the region id of every pixel of a map
+of any size; optionally c_info['unconditional_region_bias'] [bs, NR, Nk], a missing one all zeros (every region reads the
+unconditional context alike).  The map is reduced on the host to every query grid of the UNet at the request's latent size
+(regions.level_maps: each level from the map itself) BEFORE the loop is captured; table and maps are two more static graph
+inputs, and the graph key gains a trailing element.  Every cross-attention of the UNet and of the ControlNet then starts a
+query's scores at the row of its region (pfd_attention_rbias_f16).  Entry points that refuse key_bias refuse these too.
 """
 import numpy as np
 import torch
@@ -151,7 +159,41 @@ def _guidance(c_info, bs, device):
 _BIAS_KEYS = ('key_bias', 'unconditional_key_bias')
 
 
+_REGION_KEYS = ('region_bias', 'region_map', 'unconditional_region_bias')
+
+
+def _regions(c_info, cond, cfg, latent_hw, n_levels, device):
+    """-> None, or (table fp32 [nb * bs, NR, Nk], qmaps uint8 [nb * bs, sum sizes], sizes) next to c_in (unconditional rows
+    first; both halves of a CFG pair share the sample's maps).  All host work -- the id check included -- happens here.
+    n_levels: a callable, asked only for a regional request (how many resolutions the UNet runs)."""
+    from .. import regions as _regions_spec
+    rb, rm, urb = (c_info.get(k, None) for k in _REGION_KEYS)
+    if rb is None and rm is None and urb is None:
+        return None
+    if rb is None or rm is None:
+        raise ValueError("c_info['region_bias'] and c_info['region_map'] come together")
+    if any(c_info.get(k, None) is not None for k in _BIAS_KEYS):
+        raise ValueError("c_info['key_bias'] and c_info['region_bias'] exclude each other (one region IS the per-key bias)")
+    bs, Nk = int(cond.shape[0]), int(cond.shape[1])
+    if not torch.is_tensor(rb) or rb.dim() != 3 or rb.shape[0] != bs or rb.shape[2] != Nk or not rb.is_floating_point() or \
+            not 1 <= rb.shape[1] <= _regions_spec.MAX_REGIONS:
+        raise ValueError(f"c_info['region_bias'] must be a float tensor [{bs}, NR <= {_regions_spec.MAX_REGIONS}, {Nk}]")
+    NR = int(rb.shape[1])
+    if urb is not None and (not torch.is_tensor(urb) or tuple(urb.shape) != tuple(rb.shape) or not urb.is_floating_point()):
+        raise ValueError(f"c_info['unconditional_region_bias'] must be a float tensor {list(rb.shape)}")
+    m = rm.detach().cpu().numpy() if torch.is_tensor(rm) else rm         # (a list: one map per sample, of any sizes)
+    maps, sizes = _regions_spec.level_maps(m, bs, latent_hw[0], latent_hw[1], n_levels(), NR)
+    rb = rb.to(device=device, dtype=torch.float32)
+    qmaps = torch.from_numpy(maps).to(device)
+    if cfg:
+        urb = torch.zeros_like(rb) if urb is None else urb.to(device=device, dtype=torch.float32)
+        rb, qmaps = torch.cat([urb, rb]), torch.cat([qmaps, qmaps])
+    return rb.contiguous(), qmaps.contiguous(), sizes
+
+
 def _refuse_bias(c_infos, what):
+    if any(ci.get(k, None) is not None for ci in c_infos for k in _REGION_KEYS):
+        raise ValueError(f"{what} takes no c_info['region_bias']: regional weights go with sample / ddim_sampling / p_sample_ddim")
     if any(ci.get(k, None) is not None for ci in c_infos for k in _BIAS_KEYS):
         raise ValueError(f"{what} takes no c_info['key_bias']: per-key weights go with sample / ddim_sampling / p_sample_ddim")
 
@@ -299,6 +341,7 @@ class DDIMSampler(object):
         c_in = torch.cat([uc, cond]) if cfg else cond   # uncond first, like ddim.py:147
         c_info['c'] = c_in
         kbias = _key_bias(c_info, cond, cfg, device)
+        regs = _regions(c_info, cond, cfg, tuple(x.shape[-2:]), lambda: self._n_levels(x_info['type']), device)
         # all-zero unconditional context (SeeCoder / SeeCoder-PA, app.py:236): its cross-attention is
         # exactly `x + to_out.bias`; one host sync per request decides
         zero_lead = bs if (cfg and self.zero_uncond_shortcut and not bool(uc.any())) else 0
@@ -326,10 +369,13 @@ class DDIMSampler(object):
             """the whole trajectory as a pure function of device tensors (capturable as one hipGraph), and its timestep table"""
             t_table = t_col.repeat(1, nb * bs)
 
-            def run_loop(x, c_in, hint, nkey, sps, mask=None, x0_keep=None, kkey=None, kbias=None):
+            def run_loop(x, c_in, hint, nkey, sps, mask=None, x0_keep=None, kkey=None, kbias=None, rtable=None, qmaps=None):
                 from .controlnet import PreparedHint
                 ps = {} if sps is None else {'scale': sps}
-                ctx = model.prepare_context(c_in) if kbias is None else model.prepare_context(c_in, kbias)
+                if rtable is not None:      # (the maps were made on the host, in front of the capture: views of a static input)
+                    ctx = model.prepare_context(c_in, None, (rtable, qmaps, regs[2]))
+                else:
+                    ctx = model.prepare_context(c_in) if kbias is None else model.prepare_context(c_in, kbias)
                 ctx.zero_lead = zero_lead
                 ctl = PreparedHint(hint) if hint is not None else None
                 # every ResBlock's time-embedding projection for ALL steps in one GEMM (t is the same for
@@ -375,10 +421,12 @@ class DDIMSampler(object):
             return run_loop, t_table
 
         inputs = (x, c_in, hint, nkey, sps)
-        if mask is not None or kbias is not None:
+        if mask is not None or kbias is not None or regs is not None:
             inputs = inputs + (mask, x0_keep, kkey)
-        if kbias is not None:
+        if kbias is not None or regs is not None:
             inputs = inputs + (kbias,)
+        if regs is not None:
+            inputs = inputs + (regs[0], regs[1])
         # a keyed schedule draws nothing from a generator: capturable whatever eta is
         if self.use_graph and (not stochastic or nkey is not None) and callback is None and x.is_cuda:
             # one hipGraph per (shape, schedule, weights version, flags); static input buffers, replayed per request.
@@ -394,6 +442,8 @@ class DDIMSampler(object):
                 key = key + (('mask', tuple(mask.shape)),)     # ... and so is every key without a mask
             if kbias is not None:
                 key = key + ('key_bias',)                      # ... and without a bias
+            if regs is not None:
+                key = key + (('regions', int(regs[0].shape[1]), tuple(regs[2])),)     # ... and without regions
             xf, ixt, ix0 = self._graph_for(key, lambda: self._capture(*make_loop(), inputs, coef)).replay(inputs)
         else:
             xf, ixt, ix0 = make_loop()[0](*inputs)
@@ -561,6 +611,14 @@ class DDIMSampler(object):
             outs = run_loop(*static)
         return _CapturedLoop(g, static, outs, (coef, t_table))
 
+    def _n_levels(self, x_type):
+        """how many resolutions the UNet (and the ControlNet, built like it) runs: the query grids regional maps are made for"""
+        try:
+            return len(self.model.diffuser[x_type].channel_mult)
+        except (AttributeError, KeyError, TypeError):
+            raise ValueError("regional mixing needs a UNet that states its resolutions (diffuser[x_type].channel_mult): the "
+                             "region maps are made for exactly the query grids it runs") from None
+
     def _graph_for(self, key, capture):
         """the captured loop of `key`, captured now if it is new; kept in order of use, the least recently used dropped at
         max_graphs (a server varies batch size and scale per request: keep the others)"""
@@ -592,7 +650,11 @@ class DDIMSampler(object):
         if cfg:
             x_info['x'] = torch.cat([x] * 2)
         kbias = _key_bias(c_info, c_info['conditioning'], cfg, x.device)
-        ctx = self.model.prepare_context(c_in) if kbias is None else self.model.prepare_context(c_in, kbias)
+        regs = _regions(c_info, c_info['conditioning'], cfg, tuple(x.shape[-2:]), lambda: self._n_levels(x_info['type']), x.device)
+        if regs is not None:
+            ctx = self.model.prepare_context(c_in, None, regs)
+        else:
+            ctx = self.model.prepare_context(c_in) if kbias is None else self.model.prepare_context(c_in, kbias)
         xf = x.to(torch.float32).contiguous()
         eps = self.model.apply_model_nhwc(x_info['type'], ops.to_nhwc(xf, rep=nb), t_in, c_info['type'], ctx,
                                           control=c_info.get('control', None))

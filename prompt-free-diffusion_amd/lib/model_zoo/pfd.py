@@ -156,11 +156,12 @@ class PromptFreeDiffusion(nn.Module):
 
     ctx_encode_trainable = ctx_encode
 
-    def prepare_context(self, c, bias=None):
+    def prepare_context(self, c, bias=None, regions=None):
         """Wrap a context tensor so the 16 cross-attention K/V^T projections are computed once per
         request instead of once per step; `apply_model` accepts either form in c_info['c'].
-        bias: fp32 [B, Nk] per-key logits (lib/refmix.py), or None."""
-        return as_context_kv(c, bias)
+        bias: fp32 [B, Nk] per-key logits (lib/refmix.py), or None.
+        regions: (table fp32 [B, NR, Nk], qmaps uint8 [B, sum(sizes)], sizes) of lib/regions.py (ContextKV), or None."""
+        return as_context_kv(c, bias) if regions is None else as_context_kv(c, bias, regions)
 
     def _control_residuals(self, x_nhwc, timesteps, context, control, cfg_pair=False):
         return None

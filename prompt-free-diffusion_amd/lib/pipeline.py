@@ -14,10 +14,12 @@ all-gather of the decoded images after the loop (`gather=True`).
 """
 import os
 
+import numpy as np
 import torch
 
 from . import image_io
 from . import refmix
+from . import regions as region_lib
 from .hip import ops
 from .hip.ops import serialised
 
@@ -204,6 +206,35 @@ def check_references(image, image_weights):
     return [image[i] for i in keep], w
 
 
+def check_regions(image, regions, region_weights, image_weights):
+    """the regional arguments of a request, checked on the host before anything touches the device.
+    -> (image, image_weights, None) where the request is no regional one after all -- none given; one region, which IS the
+    image_weights request of its row; one reference left after the all-zero columns are dropped, which IS the plain request
+    of that picture -- else (references kept, None, (uint8 map [Hm, Wm] as numpy, float64 weights [NR, R]))."""
+    if regions is None and region_weights is None:
+        return image, image_weights, None
+    if regions is None or region_weights is None:
+        raise ValueError("a regional request gives regions=<uint8 map [Hm, Wm]> together with region_weights=[[w00, w01, ...], ...]")
+    if image_weights is not None:
+        raise ValueError("region_weights and image_weights exclude each other: one region is the image_weights request")
+    if not isinstance(image, (list, tuple)):
+        raise ValueError("a regional request gives its references as image=[ref0, ref1, ...]")
+    w = region_lib.check_region_weights(region_weights)
+    if w.shape[1] != len(image):
+        raise ValueError(f"{len(image)} reference pictures but rows of {w.shape[1]} region_weights")
+    m = regions.detach().cpu().numpy() if torch.is_tensor(regions) else np.asarray(regions)
+    if m.ndim != 2:
+        raise ValueError(f"regions must be a uint8 map [Hm, Wm], got shape {m.shape}")
+    region_lib.region_grid(m, 1, 1, nr=w.shape[0])          # dtype, shape and ids, on the host
+    if w.shape[0] == 1:
+        return image, [float(x) for x in w[0]], None
+    keep, w = region_lib.drop_zero_columns(w)
+    if len(keep) == 1:
+        return image[keep[0]], None, None
+    check_references([image[i] for i in keep], [1.0] * len(keep))      # the pictures themselves
+    return [image[i] for i in keep], None, (np.ascontiguousarray(m), w)
+
+
 class PromptFreePipeline:
     """One rank's view of a (possibly multi-GPU) request: shard -> encode -> DDIM loop -> decode -> gather.
     `sampler` is injectable (the gloo CPU tests drive this very code with a stand-in for the GPU compute)."""
@@ -238,6 +269,29 @@ class PromptFreePipeline:
 
     @serialised
     @torch.no_grad()
+    def encode_reference_tokens(self, images, n):
+        """the tokens of several references side by side: images, a list of uint8 HWC pictures / float [1,3,H,W] tensors
+        -> (cond [n, R*Nk, C], zeros like it, Nk = tokens per reference).  SeeCoder runs once per reference (through the
+        graphed stage when graphs are on)."""
+        dev = self.net.device
+        toks = []
+        for ref in images:
+            img = self.ingest(ref) if image_io.wants_ingest(ref) else ref.to(dev)
+            toks.append(self._ctx_stage(img) if self._ctx_stage is not None else self.net.ctx_encode(img, 'image'))
+        cond = torch.cat(toks, 1).repeat(n, 1, 1)
+        return cond, torch.zeros_like(cond), int(toks[0].shape[1])
+
+    @serialised
+    @torch.no_grad()
+    def encode_regions(self, images, region_weights, n):
+        """regional mixing (lib/regions.py): the references' tokens and a row of logits per region
+        -> (cond [n, R*Nk, C], zeros like it, table fp32 [n, NR, R*Nk])"""
+        cond, zeros, nk = self.encode_reference_tokens(images, n)
+        tab = torch.from_numpy(region_lib.region_bias(region_weights, nk, int(cond.shape[1])))
+        return cond, zeros, tab.to(self.net.device)[None].repeat(n, 1, 1)
+
+    @serialised
+    @torch.no_grad()
     def encode_references(self, images, weights, n):
         """several references mixed in one UNet pass (lib/refmix.py): images, a list of uint8 HWC pictures / float [1,3,H,W]
         tensors, with one weight > 0 each -> (cond [n, R*Nk, C], zeros like it, bias fp32 [n, R*Nk]).  SeeCoder runs once
@@ -246,15 +300,9 @@ class PromptFreePipeline:
         w = refmix.check_weights(weights)
         if len(images) != w.size:
             raise ValueError(f"{len(images)} references but {w.size} weights")
-        dev = self.net.device
-        toks = []
-        for ref in images:
-            img = self.ingest(ref) if image_io.wants_ingest(ref) else ref.to(dev)
-            toks.append(self._ctx_stage(img) if self._ctx_stage is not None else self.net.ctx_encode(img, 'image'))
-        nk = int(toks[0].shape[1])
-        cond = torch.cat(toks, 1).repeat(n, 1, 1)
-        bias = torch.from_numpy(refmix.key_bias(w, nk, len(toks) * nk)).to(dev)[None].repeat(n, 1)
-        return cond, torch.zeros_like(cond), bias
+        cond, zeros, nk = self.encode_reference_tokens(images, n)
+        bias = torch.from_numpy(refmix.key_bias(w, nk, int(cond.shape[1]))).to(self.net.device)[None].repeat(n, 1)
+        return cond, zeros, bias
 
     @staticmethod
     def pad_context(ctx, bias, nk):
@@ -387,7 +435,8 @@ class PromptFreePipeline:
     def generate(self, image, n_global, height, width, steps=50, scale=2.0, eta=0.0, seed=20, control=None,
                  uncond=None, decode=True, gather=False, verbose=False, timings=None, as_uint8=False,
                  device_noise=False, solver='ddim', control_preprocess=None, control_thresholds=(100, 200), init=None,
-                 strength=0.75, init_posterior='sample', mask=None, composite=False, image_weights=None):
+                 strength=0.75, init_posterior='sample', mask=None, composite=False, image_weights=None, regions=None,
+                 region_weights=None):
         """returns (images, latents [n_local,4,h,w]); images = [n_local | n_global (gather), 3, H, W] in [0,1]
         in the model dtype, or -- as_uint8 -- packed uint8 [n, H, W, 3] (the bytes ToPILImage would produce,
         app.py:273-275; 4x fewer bytes through the all-gather); decode=False returns the latents twice.
@@ -424,14 +473,21 @@ class PromptFreePipeline:
         `encode_references`; pfd_attention_kbias_f16).  Only the ratios matter.  A reference of weight 0 is dropped before it
         is encoded; with one reference left the request IS the plain request of that picture.  An `uncond` with fewer tokens
         than the mix is padded with zero tokens that carry weight 0.  Works with every other argument; draws nothing, so the
-        result does not depend on the world size.  Not the reference's context_mixing (sample_multicontext)."""
+        result does not depend on the world size.  Not the reference's context_mixing (sample_multicontext).
+        regions, region_weights (instead of image_weights): regional mixing, lib/regions.py -- regions is a uint8 map [Hm, Wm]
+        of any size whose pixel value is a region id, region_weights[g][r] >= 0 the weight of reference r in region g (up to
+        8 regions; every row with a weight > 0).  A query of a cross-attention listens to the references at the weights of the
+        region under the centre of its cell (regions.region_grid, every UNet level from the map itself;
+        pfd_attention_rbias_f16).  One region IS the image_weights request of its row, a reference no region uses is dropped,
+        one reference left IS the plain request.  Works with every other argument; draws nothing."""
         from .model_zoo.ddim import is_per_sample
         from .solver import solver_order
         if solver_order(solver) is not None and (eta != 0. or device_noise):     # an unknown name raises here too
             raise ValueError(f"solver {solver!r} is deterministic: eta must be 0 and device_noise off")
         P, r = self.world_size, self.rank
         dev = self.net.device
-        refs = check_references(image, image_weights)     # checked before anything touches the device
+        image, image_weights, regional = check_regions(image, regions, region_weights, image_weights)
+        refs = check_references(image, image_weights if regional is None else [1.0] * len(image))     # checked before anything touches the device
         if refs is not None and len(refs[0]) == 1:
             image, refs = refs[0][0], None                # one reference left: the plain request
         if is_per_sample(scale):     # checked before anything touches the device
@@ -466,7 +522,10 @@ class PromptFreePipeline:
         kbias = None
         if u8_image:
             image = self.ingest(image)
-        if refs is not None:
+        rtable = None
+        if regional is not None:          # the tokens of the references side by side; a row of logits per region
+            cond, zeros, rtable = self.encode_regions(refs[0], regional[1], n)
+        elif refs is not None:
             cond, zeros, kbias = self.encode_references(refs[0], refs[1], n)
         elif image.shape[0] > 1:
             # one reference image PER SAMPLE (the "+737 GFLOP/img" variant): SeeCoder is run once per image
@@ -480,8 +539,8 @@ class PromptFreePipeline:
         ukb = None
         if uncond is None:
             uncond = zeros
-        elif kbias is not None and uncond.shape[1] != cond.shape[1]:
-            uncond, ukb = self.pad_uncond(uncond.to(dev).to(cond.dtype), kbias)
+        elif (kbias is not None or rtable is not None) and uncond.shape[1] != cond.shape[1]:
+            uncond, ukb = self.pad_uncond(uncond.to(dev).to(cond.dtype), cond[:, :, 0])
             if uncond.shape[0] == 1 and n > 1:
                 uncond, ukb = uncond.expand(n, -1, -1), ukb.expand(n, -1)
         if mk:
@@ -505,7 +564,11 @@ class PromptFreePipeline:
             x_info['noise_key'] = shard_noise_keys(n_global, seed, r, P).to(dev)
         c_info = {'type': 'image', 'conditioning': cond, 'unconditional_conditioning': uncond,
                   'unconditional_guidance_scale': scale}
-        if kbias is not None:
+        if regional is not None:
+            c_info['region_bias'], c_info['region_map'] = rtable, regional[0]
+            if ukb is not None:
+                c_info['unconditional_region_bias'] = ukb[:, None].expand(-1, rtable.shape[1], -1)
+        elif kbias is not None:
             c_info['key_bias'] = kbias
             if ukb is not None:
                 c_info['unconditional_key_bias'] = ukb

@@ -27,14 +27,14 @@ from concurrent.futures import Future
 import torch
 
 from . import image_io
-from .pipeline import PromptFreePipeline, check_references, shard_noise_keys, shard_xT
+from .pipeline import PromptFreePipeline, check_references, check_regions, shard_noise_keys, shard_xT
 from .solver import solver_order
 
 
 class _Request:
     __slots__ = ("image", "n", "height", "width", "steps", "scale", "eta", "seed", "control", "uncond", "as_uint8",
                  "device_noise", "future", "mixed", "solver", "control_preprocess", "control_thresholds", "init", "strength",
-                 "init_k", "mask", "composite", "weights")
+                 "init_k", "mask", "composite", "weights", "regional")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -47,7 +47,9 @@ class _Request:
             how = how + (('init', int(self.init_k)),)
         if self.mask is not None:     # inpainting: masked requests share batches with each other only; every other key is unchanged
             how = how + (('mask', bool(self.composite)),)
-        if self.weights is not None:  # several references: with each other only, whatever their number; every other key is unchanged
+        if self.regional is not None:  # regional mixing: with regional requests of the same number of regions and references only
+            how = how + (('regions',) + tuple(self.regional[1].shape),)
+        elif self.weights is not None:  # several references: with each other only, whatever their number; every other key is unchanged
             how = how + ('refmix',)
         if self.mixed:
             return (self.height, self.width, self.steps, float(self.scale) == 1.0, float(self.eta),
@@ -82,7 +84,8 @@ class PromptFreeServer:
     # ---- client side (any thread) -------------------------------------------------------------------
     def submit(self, image, n_samples=1, height=512, width=512, steps=50, scale=2.0, eta=0.0, seed=20,
                control=None, uncond=None, as_uint8=True, device_noise=False, solver='ddim', control_preprocess=None,
-               control_thresholds=(100, 200), init=None, strength=0.75, mask=None, composite=False, image_weights=None):
+               control_thresholds=(100, 200), init=None, strength=0.75, mask=None, composite=False, image_weights=None,
+               regions=None, region_weights=None):
         """image [1,3,h,w] in [0,1] (any size); control [1,3,H,W] or None; uncond [1,148,768] or None (zeros).
         image and control may each be a uint8 HWC picture [h,w,3] (torch or numpy, any size; the reference picture
         at least 32 a side) instead: the request carries the bytes and the worker converts them on the device
@@ -109,6 +112,11 @@ class PromptFreeServer:
         the other key fields) whatever their numbers of references: contexts are padded to the longest of the batch with
         zero tokens of weight 0, each sample with its own row of logits.  A request without image_weights never shares a
         batch with one that has them.  One reference left after dropping zero weights is the plain request.
+        regions, region_weights: regional mixing (PromptFreePipeline.generate, lib/regions.py) -- a uint8 map [Hm, Wm] of region
+        ids and a row of weights per region, instead of image_weights.  Regional requests share a batch only with regional
+        requests of the same output size, number of regions and number of references (equal in the other key fields), each
+        sample with its own map (of its own size) and table; never with plain or image_weights requests.  One region is the
+        image_weights request, one reference left the plain request.  An uncond is not taken with regions here.
         -> Future of uint8 [n,H,W,3] (as_uint8) or float [n,3,H,W] images"""
         if self._stop:
             raise RuntimeError("server is closed")
@@ -122,7 +130,10 @@ class PromptFreeServer:
             raise ValueError("steps must be >= 1")
         if solver_order(solver) is not None and (float(eta) != 0.0 or device_noise):     # an unknown name raises here too
             raise ValueError(f"solver {solver!r} is deterministic: eta must be 0 and device_noise off")
-        refs = check_references(image, image_weights)
+        image, image_weights, regional = check_regions(image, regions, region_weights, image_weights)
+        if regional is not None and uncond is not None:
+            raise ValueError("a regional request takes no uncond on the server (PromptFreePipeline.generate does)")
+        refs = check_references(image, image_weights if regional is None else [1.0] * len(image))
         weights = None
         if refs is not None:
             for ref in refs[0]:
@@ -153,7 +164,7 @@ class PromptFreeServer:
                      strength=strength, init_k=init_k, mask=mask, composite=bool(composite) if mask is not None else None,
                      scale=scale, eta=eta, seed=int(seed), control=control, uncond=uncond, as_uint8=as_uint8,
                      device_noise=bool(device_noise), future=Future(), mixed=self.mixed_batches or None, solver=solver,
-                     control_preprocess=control_preprocess, control_thresholds=thresholds, weights=weights)
+                     control_preprocess=control_preprocess, control_thresholds=thresholds, weights=weights, regional=regional)
         self._q.put(r)
         return r.future
 
@@ -252,9 +263,13 @@ class PromptFreeServer:
         with DEVICE_LOCK:
             if float(r0.eta) != 0.0 and not r0.device_noise:   # runs alone (shareable()): its noise stream is a function
                 torch.manual_seed(r0.seed)                      # of ITS seed only
-            conds, xts, unconds, keys, masks, x0s, biases, ubiases = [], [], [], [], [], [], [], []
+            conds, xts, unconds, keys, masks, x0s, biases, ubiases, tables, rmaps = [], [], [], [], [], [], [], [], [], []
             for r in batch:
-                if r.weights is not None:           # several references: ITS tokens and ITS row of logits
+                if r.regional is not None:          # regional: ITS tokens, ITS table and ITS map (of its own size) per sample
+                    c, z, tab = self.pipe.encode_regions(r.image, r.regional[1], r.n)
+                    tables.append(tab)
+                    rmaps.extend([r.regional[0]] * r.n)
+                elif r.weights is not None:           # several references: ITS tokens and ITS row of logits
                     c, z, kb = self.pipe.encode_references(r.image, r.weights, r.n)
                     biases.append(kb)
                 else:
@@ -272,7 +287,7 @@ class PromptFreeServer:
                     xts.append(x_t)
                     x0s.append(x0)
                     masks.append(self.pipe.mask_grid(r.mask, r.height, r.width)[:1].expand(r.n, -1, -1))
-            if r0.weights is not None:
+            if r0.weights is not None and r0.regional is None:
                 # contexts of different lengths: padded to the longest of the batch with zero tokens at -inf
                 nk = max(int(t.shape[1]) for t in conds + unconds)      # (an uncond longer than every mix is padded to as well)
                 for i, (c, u, kb) in enumerate(zip(conds, unconds, biases)):
@@ -283,7 +298,9 @@ class PromptFreeServer:
             cond, uncond, xT = torch.cat(conds), torch.cat(unconds), torch.cat(xts).to(dev)
             c_info = {'type': 'image', 'conditioning': cond, 'unconditional_conditioning': uncond,
                       'unconditional_guidance_scale': r0.scale}
-            if r0.weights is not None:
+            if r0.regional is not None:             # (equal numbers of references: the key says so, nothing to pad)
+                c_info['region_bias'], c_info['region_map'] = torch.cat(tables), rmaps
+            elif r0.weights is not None:
                 c_info['key_bias'] = torch.cat(biases)
                 if any(r.uncond is not None for r in batch):
                     c_info['unconditional_key_bias'] = torch.cat(ubiases)
