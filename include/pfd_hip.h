@@ -528,6 +528,16 @@ int pfd_composite_u8(const void* decoded, const void* init, int32_t Bi, const vo
                      int32_t H, int32_t W, int32_t C, pfd_stream_t stream);
 /* y = a + b (f16, fp32 add), n elements; b may be NULL (copy). */
 int pfd_add_f16(const void* a, const void* b, void* y, int64_t n, pfd_stream_t stream);
+/* ControlNet strength (added under ABI 10): y[b, e] = (f16) fmaf(scale[b * scale_stride], (float) r[b, e], (float) x[b, e])
+ * on dense f16 [B, n_per_sample] -- the add of a ControlNet residual r into the UNet's activation x with one fp32
+ * scale per sample, a column of the request's [B, 13] strength table (scale_stride = 13).  It replaces the plain
+ * `h = h + control.pop()` / `torch.cat([h, hs.pop() + control.pop()], dim=1)` of the reference (pfd.py:515-521, whose
+ * `control_scales` are never applied, pfd.py:463) where a request scales its control.  y may be x or r (in place).  A
+ * sample whose scale is exactly 0 receives x's bits and r is not read for it; at scale 1.0f the result is bit for bit
+ * pfd_add_f16's.  NULL pointers, B < 1, scale_stride < 1 or n_per_sample < 1 is PFD_EINVAL; n_per_sample % 8 != 0, a
+ * pointer x / r / y that is not 16-byte aligned or B > 65535 is PFD_ESHAPE. */
+int pfd_add_scaled_rows_f16(const void* x, const void* r, const float* scale, int64_t scale_stride, void* y, int32_t B,
+                            int64_t n_per_sample, pfd_stream_t stream);
 /* y = alpha*a + beta*b (f16 storage, fp32 math), n elements; b may be NULL (y = alpha*a).  The
  * ratio-weighted sum of the per-context SpatialTransformer outputs of multi-context sampling
  * (pfd.py:375-380 `h = h + module(x, emb, c) * r`). */

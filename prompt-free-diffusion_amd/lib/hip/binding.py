@@ -96,6 +96,7 @@ SIGNATURES = {
     "pfd_mask_grid_u8": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "pfd_composite_u8": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pfd_add_f16": (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    "pfd_add_scaled_rows_f16": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _i64, _vp]),
     "pfd_axpby_f16": (_i32, [_vp, _f32, _vp, _f32, _vp, _i64, _vp]),
     "pfd_add_rowvec_f16": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp]),
     "pfd_add_rowvec_lnstats_f16": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),

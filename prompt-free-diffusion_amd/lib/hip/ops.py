@@ -1179,6 +1179,32 @@ def add(a, b, out=None):
     return _written(out)
 
 
+def add_scaled_rows(x, r, scale, out=None):
+    """out[b] = x[b] + scale[b] * r[b] (fp32 fma, one f16 rounding): the add of a ControlNet residual with one strength per
+    sample (lib/control.py).  x, r: dense f16 [B, ...] of equal sizes; scale: an fp32 [B] view on the device, any stride
+    -- a column of the request's [B, 13] table; out: x, r or another dense f16 tensor of that size.  A sample of scale 0
+    receives x's bits and r is not read for it; at scale 1 the result is add(x, r) bit for bit.  Reads nothing back."""
+    _chk16(x, "add_scaled_rows x")
+    _chk16(r, "add_scaled_rows r")
+    if not (x.is_contiguous() and r.is_contiguous()) or (out is not None and not out.is_contiguous()):
+        raise ValueError("add_scaled_rows: dense tensors expected")
+    if x.dim() < 2 or x.numel() != r.numel() or x.shape[0] != r.shape[0] or (out is not None and out.numel() != x.numel()):
+        raise ValueError(f"add_scaled_rows: operand sizes differ ({tuple(x.shape)} vs {tuple(r.shape)}); no broadcasting")
+    B = int(x.shape[0])
+    if not torch.is_tensor(scale) or scale.dtype != torch.float32 or not scale.is_cuda or tuple(scale.shape) != (B,):
+        raise ValueError(f"add_scaled_rows: scale must be a float32 [{B}] tensor on the device (a column of the strength table)")
+    stride = int(scale.stride(0)) if B > 1 else 1
+    if stride < 1:
+        raise ValueError("add_scaled_rows: scale must have a positive stride")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _chk16(out, "add_scaled_rows out")
+    _b.check(_lib().pfd_add_scaled_rows_f16(x.data_ptr(), r.data_ptr(), scale.data_ptr(), stride, out.data_ptr(), B,
+                                            x.numel() // B, _stream()), "pfd_add_scaled_rows_f16")
+    return _written(out)
+
+
 def axpby(a, alpha, b=None, beta=0.0, out=None):
     """out = alpha*a + beta*b (b optional)"""
     _chk16(a, "axpby a")

@@ -69,6 +69,14 @@ unconditional context alike).  The map is reduced on the host to every query gri
 (regions.level_maps: each level from the map itself) BEFORE the loop is captured; table and maps are two more static graph
 inputs, and the graph key gains a trailing element.  Every cross-attention of the UNet and of the ControlNet then starts a
 query's scores at the row of its region (pfd_attention_rbias_f16).  Entry points that refuse key_bias refuse these too.
+
+ControlNet strength (opt-in, with c_info['control']): c_info['control_scale'], fp32 [nb * bs, 13] -- lib/control.scale_table,
+rows in the order of the CFG batch, column i the strength of ControlNet residual i -- and c_info['control_steps'] = (lo, hi),
+run indices (lib/control.window_steps; without it every step).  A step i outside lo <= i < hi calls the model with
+control=None: it IS the uncontrolled step, the ControlNet is not evaluated.  A step inside passes the hint and the table
+(pfd_add_scaled_rows_f16 in place of the 13 plain adds).  The table is one more static graph input behind the others --
+another strength replays the same graph -- and the graph key gains a trailing ('control', lo, hi).  The multi-context loop
+and the single-step entry points refuse both keys.  Without them every path, launch sequence and graph key is what it was.
 """
 import numpy as np
 import torch
@@ -196,6 +204,39 @@ def _refuse_bias(c_infos, what):
         raise ValueError(f"{what} takes no c_info['region_bias']: regional weights go with sample / ddim_sampling / p_sample_ddim")
     if any(ci.get(k, None) is not None for ci in c_infos for k in _BIAS_KEYS):
         raise ValueError(f"{what} takes no c_info['key_bias']: per-key weights go with sample / ddim_sampling / p_sample_ddim")
+
+
+_CONTROL_KEYS = ('control_scale', 'control_steps')
+
+
+def _refuse_control(c_infos, what):
+    if any(ci.get(k, None) is not None for ci in c_infos for k in _CONTROL_KEYS):
+        raise ValueError(f"{what} takes no c_info['control_scale'] / ['control_steps']: a scaled or windowed control goes with "
+                         "sample / ddim_sampling")
+
+
+def _control_strength(c_info, has_hint, rows, total_steps, device):
+    """-> (None, None), or (table fp32 [rows, 13] on the device, (lo, hi) run indices) of a scaled / windowed control"""
+    tab, steps = (c_info.get(k, None) for k in _CONTROL_KEYS)
+    if tab is None and steps is None:
+        return None, None
+    if not has_hint:
+        raise ValueError("c_info['control_scale'] / ['control_steps'] need c_info['control'] on a model with a ControlNet")
+    if tab is None:
+        raise ValueError("c_info['control_steps'] comes with c_info['control_scale'] (lib/control.scale_table; ones: the plain adds)")
+    if not torch.is_tensor(tab) or tab.dtype != torch.float32 or tuple(tab.shape) != (rows, 13):
+        raise ValueError(f"c_info['control_scale'] must be a float32 tensor [{rows}, 13]: a row per sample of the CFG batch, "
+                         "a column per ControlNet residual")
+    if steps is None:
+        steps = (0, total_steps)
+    try:
+        lo, hi = (int(v) for v in steps)
+        ok = lo == steps[0] and hi == steps[1] and 0 <= lo <= hi <= total_steps
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"c_info['control_steps'] must be (lo, hi) with 0 <= lo <= hi <= {total_steps} (run indices), got {steps!r}")
+    return tab.to(device).contiguous(), (lo, hi)
 
 
 def _key_bias(c_info, cond, cfg, device):
@@ -364,12 +405,14 @@ class DDIMSampler(object):
                                  "global generator: leave the key out)")
             nkey = ops.noise_key_rows(nkey, bs, device)
         mask, x0_keep, kkey = _masked_inputs(x_info, x, nkey, stochastic)
+        ctab, csteps = _control_strength(c_info, hint is not None, nb * bs, total_steps, device)
 
         def make_loop():
             """the whole trajectory as a pure function of device tensors (capturable as one hipGraph), and its timestep table"""
             t_table = t_col.repeat(1, nb * bs)
 
-            def run_loop(x, c_in, hint, nkey, sps, mask=None, x0_keep=None, kkey=None, kbias=None, rtable=None, qmaps=None):
+            def run_loop(x, c_in, hint, nkey, sps, mask=None, x0_keep=None, kkey=None, kbias=None, rtable=None, qmaps=None,
+                         ctab=None):
                 from .controlnet import PreparedHint
                 ps = {} if sps is None else {'scale': sps}
                 if rtable is not None:      # (the maps were made on the host, in front of the capture: views of a static input)
@@ -391,8 +434,14 @@ class DDIMSampler(object):
                 x0_last = None
                 for i in range(total_steps):
                     index = total_steps - i - 1
-                    eps = model.apply_model_nhwc(x_type, xin, t_table[i], c_type, ctx, control=ctl,
-                                                 emb_table=emb_all[i:i + 1], cfg_pair=pair)
+                    ctl_i, how = ctl, {}
+                    if csteps is not None:      # a scaled / windowed control: outside the window the uncontrolled step itself
+                        if csteps[0] <= i < csteps[1]:
+                            how = {'control_scale': ctab}
+                        else:
+                            ctl_i = None
+                    eps = model.apply_model_nhwc(x_type, xin, t_table[i], c_type, ctx, control=ctl_i,
+                                                 emb_table=emb_all[i:i + 1], cfg_pair=pair, **how)
                     if mask is not None:
                         # masked regeneration: the same step, blended with the init picture's own trajectory outside the mask
                         ksq, ks = _inpaint.step_constants(self.ddim_alphas_prev[index], index)
@@ -427,6 +476,8 @@ class DDIMSampler(object):
             inputs = inputs + (kbias,)
         if regs is not None:
             inputs = inputs + (regs[0], regs[1])
+        if ctab is not None:                  # behind every other static input, absent ones as None
+            inputs = inputs + (None,) * (11 - len(inputs)) + (ctab,)
         # a keyed schedule draws nothing from a generator: capturable whatever eta is
         if self.use_graph and (not stochastic or nkey is not None) and callback is None and x.is_cuda:
             # one hipGraph per (shape, schedule, weights version, flags); static input buffers, replayed per request.
@@ -444,6 +495,8 @@ class DDIMSampler(object):
                 key = key + ('key_bias',)                      # ... and without a bias
             if regs is not None:
                 key = key + (('regions', int(regs[0].shape[1]), tuple(regs[2])),)     # ... and without regions
+            if csteps is not None:
+                key = key + (('control', csteps[0], csteps[1]),)     # ... and without a scaled / windowed control
             xf, ixt, ix0 = self._graph_for(key, lambda: self._capture(*make_loop(), inputs, coef)).replay(inputs)
         else:
             xf, ixt, ix0 = make_loop()[0](*inputs)
@@ -497,6 +550,7 @@ class DDIMSampler(object):
             raise ValueError(f"solver {solver!r} is not available for multi-context sampling: use 'ddim'")
         _refuse_mask(x_info, "sample_multicontext")
         _refuse_bias(c_info_list, "sample_multicontext")
+        _refuse_control(c_info_list, "sample_multicontext")
         self.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=verbose)
         if verbose:
             print(f'Data shape for DDIM sampling is {shape}, eta {eta}')
@@ -510,6 +564,7 @@ class DDIMSampler(object):
         model = self.model
         scale = None
         _refuse_bias(c_info_list, "multi-context sampling")
+        _refuse_control(c_info_list, "multi-context sampling")
         for ci in c_info_list:
             if is_per_sample(ci['unconditional_guidance_scale']):
                 raise ValueError("a per-sample guidance scale is out of scope for multi-context sampling: give one "
@@ -639,6 +694,7 @@ class DDIMSampler(object):
         (x_prev, pred_x0) in x.dtype); the loop above uses the same kernels without the
         per-step layout conversions."""
         _refuse_mask(x_info, "p_sample_ddim")
+        _refuse_control([c_info], "p_sample_ddim")
         x = x_info['x']
         sps, scale, uc, cfg, nb = _guidance(c_info, x.shape[0], x.device)
         if cfg:

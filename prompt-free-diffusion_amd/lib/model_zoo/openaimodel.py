@@ -399,9 +399,13 @@ class UNetModel2D_Next(nn.Module, L._Packed):
         w, bias, cols = self._emb_pack()
         return ops.gemm(self.silu_time_embedding(timesteps), w, bias=bias), cols
 
-    def hip(self, x, timesteps, context, control=None, context_net=None, emb_table=None, cfg_pair=False):
+    def hip(self, x, timesteps, context, control=None, context_net=None, emb_table=None, cfg_pair=False,
+            control_scale=None):
         """The forward that pfd.apply_model defines (pfd.py:314-365, :466-528), NHWC fp16 in/out.
         control: list of 13 NHWC residuals from ControlNet (popped from the end) or None.
+        control_scale: None -- the residuals are added as they are --, or an fp32 [B, 13] table on the device (lib/control.py):
+        residual i is added with the strength of column i for each sample of the full batch, in place into the residual
+        (ops.add_scaled_rows; the residual is dead afterwards).
         context_net: the UNet that owns the context blocks (defaults to self).
         emb_table: optional [1, sum Cout] row of `emb_projections` valid for EVERY sample of the
         batch (the sampler precomputes all steps at once); otherwise computed here per sample.
@@ -430,6 +434,18 @@ class UNetModel2D_Next(nn.Module, L._Packed):
                 p, pair[0] = pair[0], False
                 return next(c_iter).hip(hh, semb, context, cfg_pair=p)
         ccs = list(control) if control is not None else None
+        if control_scale is not None:
+            if ccs is None:
+                raise ValueError("control_scale without control")
+            if not torch.is_tensor(control_scale) or control_scale.dim() != 2 or control_scale.shape[1] != len(ccs):
+                raise ValueError(f"control_scale must be a float32 [B, {len(ccs)}] table, one column per ControlNet residual")
+
+            def add_control(t):
+                r = ccs.pop()                      # residual len(ccs) of ControlNet.hip's list: the column of that index
+                return ops.add_scaled_rows(t, r, control_scale[:, len(ccs)], out=r)
+        else:
+            def add_control(t):
+                return ops.add(t, ccs.pop())
         hs = []
         h = x
         nn_of = self._next_norms(cnet, control is not None) if not isinstance(context, ContextMix) else {}
@@ -451,13 +467,13 @@ class UNetModel2D_Next(nn.Module, L._Packed):
             h = data_layer(h) if ltype == 'd' else ctx_layer(h)
             step[0] += 1
         if ccs is not None:
-            h = ops.add(h, ccs.pop())
+            h = add_control(h)
         skip = None
         for ltype in self.o_order:
             if ltype == 'load_hidden_feature':
                 skip = hs.pop()
                 if ccs is not None:
-                    skip = ops.add(skip, ccs.pop())
+                    skip = add_control(skip)
             elif ltype == 'd':
                 h, skip = data_layer(h, x2=skip), None
             else:

@@ -169,9 +169,10 @@ class PromptFreeDiffusion(nn.Module):
     @ops.serialised
     @torch.no_grad()
     def apply_model_nhwc(self, x_type, x_nhwc, timesteps, c_type, context, control=None, emb_table=None,
-                         cfg_pair=False):
+                         cfg_pair=False, control_scale=None):
         """x_nhwc fp16 [B,h,w,C]; context ContextKV; -> eps NHWC fp16.
-        cfg_pair: x_nhwc is one copy [B/2,...] of a CFG batch [x | x] (see UNetModel2D_Next.hip)"""
+        cfg_pair: x_nhwc is one copy [B/2,...] of a CFG batch [x | x] (see UNetModel2D_Next.hip)
+        control_scale: the fp32 [B, 13] strength table of a scaled control (lib/control.py), or None: the plain adds"""
         unet = self.diffuser[x_type]
         gnet = unet if self.global_layer_ptr is None else self.diffuser[self.global_layer_ptr]
         if gnet is not unet:
@@ -188,13 +189,18 @@ class PromptFreeDiffusion(nn.Module):
             if emb_table is None and (not timesteps.is_cuda or not torch.cuda.is_current_stream_capturing()) and \
                     not bool((timesteps[:nb] == timesteps[nb:]).all()):
                 raise ValueError("cfg_pair: the two halves of the pair carry different timesteps")
+        if control_scale is not None and control is None:
+            raise ValueError("control_scale without control")
         if isinstance(context, ContextMix):
             if control is not None:
                 raise NotImplementedError("ControlNet with multi-context mixing (the reference has no such path)")
             return unet.hip(x_nhwc, timesteps, context, emb_table=emb_table)
         ccs = self._control_residuals(x_nhwc, timesteps, context, control, cfg_pair)
+        if control_scale is not None and ccs is None:
+            raise ValueError("control_scale on a model without a ControlNet")
+        how = {} if control_scale is None else {'control_scale': control_scale}     # the default call is what it was
         return unet.hip(x_nhwc, timesteps, context, control=ccs, context_net=self.diffuser[c_type],
-                        emb_table=emb_table, cfg_pair=cfg_pair)
+                        emb_table=emb_table, cfg_pair=cfg_pair, **how)
 
     def prepare_context_mix(self, c_info_list, mixing_type='attention'):
         """[{'type', 'c', 'ratio'}] -> ContextMix with every context's K / V^T hoisted (pfd.py:366-386)"""
@@ -237,7 +243,7 @@ class PromptFreeDiffusion_with_control(PromptFreeDiffusion):
         ctl_cfg = kwargs.pop('ctl_cfg')
         super().__init__(*args, **kwargs)
         self.ctl = get_model()(ctl_cfg)
-        self.control_scales = [1.0] * 13  # never applied by the reference either (pfd.py:463)
+        self.control_scales = [1.0] * 13  # never applied by the reference either (pfd.py:463); a request's strength is lib/control.py
         self.parameter_group['ctl'] = [self.ctl]
 
     def _control_residuals(self, x_nhwc, timesteps, context, control, cfg_pair=False):

@@ -235,6 +235,36 @@ def check_regions(image, regions, region_weights, image_weights):
     return [image[i] for i in keep], None, (np.ascontiguousarray(m), w)
 
 
+def schedule_length(steps, num_timesteps):
+    """how many timesteps the sampler's schedule has for a request of `steps` steps (len(ddim_timesteps))"""
+    from .model_zoo.diffusion_utils import make_ddim_timesteps
+    return int(len(make_ddim_timesteps("uniform", int(steps), int(num_timesteps), verbose=False)))
+
+
+def check_control_strength(control, control_scale, control_layer_scales, control_window, control_cond_only, n, nb, total_k,
+                           first=0, n_local=None):
+    """the four strength arguments of a control request (lib/control.py), checked on the host before anything touches the
+    device.  n: the samples control_scale speaks of (the global batch; a request's own on the server), of which this caller
+    runs n_local from `first` on; nb: 2 with CFG, else 1; total_k: a callable -> (schedule length, steps the run evaluates),
+    asked only when an argument is off its default.
+    -> None: the plain request (with or without control); 'off': drop the control, the request is the uncontrolled one;
+    else (table float32 [nb * n_local, 13], (lo, hi)) for c_info['control_scale'] / ['control_steps']."""
+    from . import control as control_lib
+    plain = (control_layer_scales is None and not control_cond_only and isinstance(control_scale, (int, float)) and
+             not isinstance(control_scale, bool) and control_scale == 1 and isinstance(control_window, (tuple, list)) and
+             tuple(control_window) == (0.0, 1.0))
+    if plain:
+        return None
+    scales = control_lib.sample_scales(control_scale.detach().cpu().numpy() if torch.is_tensor(control_scale) else control_scale, n)
+    n_local = int(n) if n_local is None else int(n_local)
+    total, k = total_k()
+    out = control_lib.normalise(scales[first:first + n_local], control_layer_scales, control_window, bool(control_cond_only),
+                                n_local, total, k, nb)
+    if control is None and out is not None:
+        raise ValueError("control_scale / control_layer_scales / control_window / control_cond_only need a control picture")
+    return out
+
+
 class PromptFreePipeline:
     """One rank's view of a (possibly multi-GPU) request: shard -> encode -> DDIM loop -> decode -> gather.
     `sampler` is injectable (the gloo CPU tests drive this very code with a stand-in for the GPU compute)."""
@@ -436,7 +466,8 @@ class PromptFreePipeline:
                  uncond=None, decode=True, gather=False, verbose=False, timings=None, as_uint8=False,
                  device_noise=False, solver='ddim', control_preprocess=None, control_thresholds=(100, 200), init=None,
                  strength=0.75, init_posterior='sample', mask=None, composite=False, image_weights=None, regions=None,
-                 region_weights=None):
+                 region_weights=None, control_scale=1.0, control_layer_scales=None, control_window=(0.0, 1.0),
+                 control_cond_only=False):
         """returns (images, latents [n_local,4,h,w]); images = [n_local | n_global (gather), 3, H, W] in [0,1]
         in the model dtype, or -- as_uint8 -- packed uint8 [n, H, W, 3] (the bytes ToPILImage would produce,
         app.py:273-275; 4x fewer bytes through the all-gather); decode=False returns the latents twice.
@@ -479,7 +510,16 @@ class PromptFreePipeline:
         8 regions; every row with a weight > 0).  A query of a cross-attention listens to the references at the weights of the
         region under the centre of its cell (regions.region_grid, every UNet level from the map itself;
         pfd_attention_rbias_f16).  One region IS the image_weights request of its row, a reference no region uses is dropped,
-        one reference left IS the plain request.  Works with every other argument; draws nothing."""
+        one reference left IS the plain request.  Works with every other argument; draws nothing.
+        control_scale, control_layer_scales, control_window, control_cond_only (with control; lib/control.py): how strongly,
+        in which layers and on which steps the hint binds.  control_scale: one number >= 0 or one per sample of the GLOBAL
+        batch.  control_layer_scales: None, 'soft' (0.825 ** (12 - i): the deep layers bind, the shallow ones give way to the
+        reference picture) or 13 numbers >= 0, one per ControlNet residual.  control_window = (start, end) in [0, 1]: the
+        part of the FULL schedule that is controlled, 0 the first (noisiest) step -- the same noise levels whatever
+        `strength` is; a step outside it is the uncontrolled step and does not run the ControlNet.  control_cond_only: the
+        unconditional half of the CFG batch gets no control.  All at their defaults: the plain control request, its path,
+        graph and bits.  Nothing left of the control (scale 0, an empty window): the request without `control`, bit for bit.
+        Works with every other argument; draws nothing."""
         from .model_zoo.ddim import is_per_sample
         from .solver import solver_order
         if solver_order(solver) is not None and (eta != 0. or device_noise):     # an unknown name raises here too
@@ -514,6 +554,14 @@ class PromptFreePipeline:
                              "the global generator")
         if composite and not decode:
             raise ValueError("composite=True needs decode=True")
+        ctl_strength = check_control_strength(
+            control, control_scale, control_layer_scales, control_window, control_cond_only, n_global,
+            2 if (is_per_sample(scale) or scale != 1.) else 1,
+            lambda: (schedule_length(steps, self.net.num_timesteps),) * 2 if init is None else
+            (schedule_length(steps, self.net.num_timesteps), image_io.check_img2img(init, height, width, steps, strength, init_posterior)),
+            first=r * (n_global // P), n_local=n_global // P)
+        if ctl_strength == 'off':
+            control, ctl_strength = None, None        # nothing left of the control: the uncontrolled request, before a hint is made
         mk = _Marks(torch.device(dev).type == 'cuda') if timings is not None else None
         if mk:
             mk.mark()
@@ -574,6 +622,9 @@ class PromptFreePipeline:
                 c_info['unconditional_key_bias'] = ukb
         if control is not None:
             c_info['control'] = self.control_hint(control, height, width, control_preprocess, control_thresholds)
+            if ctl_strength is not None:
+                c_info['control_scale'] = torch.from_numpy(ctl_strength[0]).to(dev)
+                c_info['control_steps'] = ctl_strength[1]
         how = {} if solver == 'ddim' else {'solver': solver}     # the default call is what it was
         x, _ = self.sampler.sample(steps=steps, shape=shape, x_info=x_info, c_info=c_info, eta=eta,
                                    verbose=verbose, **how)

@@ -19,6 +19,11 @@ model with no lock and one request = one `sampler.sample` of `n_sample_image` sa
 among themselves), every other batch runs with a scale vector and one captured graph per shape whatever the scales
 are.  ControlNet requests share a batch with other ControlNet requests, each sample with its own hint.  Still per
 batch: output size, steps, eta, noise kind, output kind, with / without control, unconditional-context kind.
+
+ControlNet strength (submit(control_scale=, control_layer_scales=, control_window=, control_cond_only=), lib/control.py): a
+request whose arguments are off their defaults shares a batch only with requests that have them too, with equal layer
+weights, equal controlled steps and equal cond_only; the strengths may differ, each sample has its own rows of the table.
+A request with nothing left of its control (scale 0, an empty window) IS the uncontrolled request and batches as one.
 """
 import queue
 import threading
@@ -27,14 +32,15 @@ from concurrent.futures import Future
 import torch
 
 from . import image_io
-from .pipeline import PromptFreePipeline, check_references, check_regions, shard_noise_keys, shard_xT
+from .pipeline import (PromptFreePipeline, check_control_strength, check_references, check_regions, schedule_length,
+                       shard_noise_keys, shard_xT)
 from .solver import solver_order
 
 
 class _Request:
     __slots__ = ("image", "n", "height", "width", "steps", "scale", "eta", "seed", "control", "uncond", "as_uint8",
                  "device_noise", "future", "mixed", "solver", "control_preprocess", "control_thresholds", "init", "strength",
-                 "init_k", "mask", "composite", "weights", "regional")
+                 "init_k", "mask", "composite", "weights", "regional", "ctl")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -51,6 +57,8 @@ class _Request:
             how = how + (('regions',) + tuple(self.regional[1].shape),)
         elif self.weights is not None:  # several references: with each other only, whatever their number; every other key is unchanged
             how = how + ('refmix',)
+        if self.ctl is not None:      # a scaled / windowed control: equal layers, steps and cond_only; the strengths may differ
+            how = how + (('control',) + tuple(self.ctl[1:]),)
         if self.mixed:
             return (self.height, self.width, self.steps, float(self.scale) == 1.0, float(self.eta),
                     self.control is None, self.uncond is None, bool(self.as_uint8), bool(self.device_noise)) + how
@@ -85,7 +93,8 @@ class PromptFreeServer:
     def submit(self, image, n_samples=1, height=512, width=512, steps=50, scale=2.0, eta=0.0, seed=20,
                control=None, uncond=None, as_uint8=True, device_noise=False, solver='ddim', control_preprocess=None,
                control_thresholds=(100, 200), init=None, strength=0.75, mask=None, composite=False, image_weights=None,
-               regions=None, region_weights=None):
+               regions=None, region_weights=None, control_scale=1.0, control_layer_scales=None, control_window=(0.0, 1.0),
+               control_cond_only=False):
         """image [1,3,h,w] in [0,1] (any size); control [1,3,H,W] or None; uncond [1,148,768] or None (zeros).
         image and control may each be a uint8 HWC picture [h,w,3] (torch or numpy, any size; the reference picture
         at least 32 a side) instead: the request carries the bytes and the worker converts them on the device
@@ -117,6 +126,10 @@ class PromptFreeServer:
         requests of the same output size, number of regions and number of references (equal in the other key fields), each
         sample with its own map (of its own size) and table; never with plain or image_weights requests.  One region is the
         image_weights request, one reference left the plain request.  An uncond is not taken with regions here.
+        control_scale, control_layer_scales, control_window, control_cond_only (with control; PromptFreePipeline.generate,
+        lib/control.py): control_scale is one number or n_samples numbers.  Off their defaults, the request shares a batch
+        only with requests that have them too and agree in layer weights, controlled steps and cond_only -- the strengths
+        may differ.  Nothing left of the control: the request is served as the one without `control`.
         -> Future of uint8 [n,H,W,3] (as_uint8) or float [n,3,H,W] images"""
         if self._stop:
             raise RuntimeError("server is closed")
@@ -160,7 +173,19 @@ class PromptFreeServer:
         image_io.check_mask(mask, init, int(height), int(width), composite, as_uint8, n=1)
         if mask is not None and float(eta) != 0.0 and not device_noise:
             raise ValueError("a masked request with eta > 0 needs device_noise=True")
-        r = _Request(image=image, n=int(n_samples), height=int(height), width=int(width), steps=int(steps), init=init,
+        from . import control as control_lib
+        ctl = check_control_strength(
+            control, control_scale, control_layer_scales, control_window, control_cond_only, int(n_samples),
+            1 if float(scale) == 1.0 else 2,
+            lambda: (schedule_length(steps, getattr(self.net, 'num_timesteps', 1000)),) * 2 if init_k is None else
+            (schedule_length(steps, getattr(self.net, 'num_timesteps', 1000)), int(init_k)))
+        if ctl == 'off':
+            control, ctl = None, None
+        elif ctl is not None:        # (strengths float64 [n], layer weights, controlled steps, cond_only): the last three are the key
+            ctl = (control_lib.sample_scales(control_scale.tolist() if torch.is_tensor(control_scale) else control_scale, n_samples),
+                   tuple(float(v) for v in control_lib.layer_scales(control_layer_scales)), ctl[1],
+                   bool(control_cond_only) and float(scale) != 1.0)
+        r = _Request(image=image, ctl=ctl, n=int(n_samples), height=int(height), width=int(width), steps=int(steps), init=init,
                      strength=strength, init_k=init_k, mask=mask, composite=bool(composite) if mask is not None else None,
                      scale=scale, eta=eta, seed=int(seed), control=control, uncond=uncond, as_uint8=as_uint8,
                      device_noise=bool(device_noise), future=Future(), mixed=self.mixed_batches or None, solver=solver,
@@ -315,6 +340,12 @@ class PromptFreeServer:
                 c_info['control'] = torch.cat(hints)
             elif r0.control is not None:
                 c_info['control'] = self._hint(r0)
+            if r0.ctl is not None:      # each sample its own rows of the table, batch order (layers, steps, cond_only: the key)
+                from . import control as control_lib
+                strengths = [float(v) for r in batch for v in r.ctl[0]]
+                tab = control_lib.scale_table(strengths, r0.ctl[1], len(strengths), 2 if per_sample or float(r0.scale) != 1.0 else 1,
+                                              r0.ctl[3])
+                c_info['control_scale'], c_info['control_steps'] = torch.from_numpy(tab).to(dev), r0.ctl[2]
             x_info = {'type': 'image', 'xt': xT}
             if r0.init is not None:
                 x_info['xt_steps'] = r0.init_k       # equal over the batch: part of the key
