@@ -514,6 +514,34 @@ int pfd_cfg_step_masked(const void* eps, int32_t nb, const float* x, int32_t sol
                         const float* x0_keep, const float* mask, int32_t Bm, float ksq, float ks, float* x_out,
                         float* pred_x0, void* xin_next, int32_t rep, int32_t B, int32_t C, int32_t h, int32_t w,
                         pfd_stream_t stream);
+/* Guidance rescale (added under ABI 10): Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed",
+ * section 3.4 -- what diffusers' rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale) does after the CFG combine,
+ * per sample and without leaving the one-launch step.  eps: f16 NHWC [2B, h, w, C], the unconditional half first, n = C*h*w
+ * elements per sample and half.  For sample b, with s = scale[b * scale_stride] and phi_b = phi[b * phi_stride] (a stride of 0:
+ * one number for all, e.g. the guidance scale of a coefficient row):
+ *   g      = fl32(fma(s, fl32(ec - eu), eu))                 the guided eps as every pfd_cfg_* entry point rounds it
+ *   mul[b] = phi_b * std(ec) / std(g) + (1 - phi_b)          std over the n elements, mean removed (n or n - 1 cancels)
+ * std(g) == 0 gives 1.0f; phi_b == 0 gives 1.0f and nothing of that sample's eps is read.  One launch of one block per
+ * sample, no workspace, no atomics, nothing read back: capturable.  The bits of mul[b] are a function of the sample's data,
+ * s, phi_b and n alone -- not of B, nor of the alignment of eps (a base that is not 16-byte aligned, or n % 8 != 0, takes
+ * scalar loads over the same order of summation).  phi outside [0, 1] is the host's to refuse.  NULL pointers, B <= 0,
+ * n <= 0 or a negative stride is PFD_EINVAL. */
+int pfd_guidance_rescale_f32(const void* eps, const float* scale, int32_t scale_stride, const float* phi, int32_t phi_stride,
+                             float* mul, int32_t B, int64_t n, pfd_stream_t stream);
+/* Any of the five step entry points above with a factor per sample on the guided eps (added under ABI 10):
+ *   e = fl32(eps_mul[b] * g),   g the guided eps; e then stands where g stood, for pred_x0 and for the update alike.
+ * eps_mul: device fp32 [B], the output of pfd_guidance_rescale_f32.  The arguments are the union of the five signatures, NULL
+ * (0 for Bm, ksq, ks, step) where the entry point stood for has none, and decide which one that is: a mask ->
+ * pfd_cfg_step_masked; else solver 1 -> pfd_cfg_dpmpp_step; else a scale -> pfd_cfg_ddim_step_ps, a key ->
+ * pfd_cfg_ddim_step_rng, neither -> pfd_cfg_ddim_step.  That entry point's rules, checks and codes apply (a noise tensor
+ * with a mask or with solver 1, a key with unmasked solver 1 and x0_keep without a mask are PFD_EINVAL too), and its kernel
+ * is launched: with eps_mul all 1.0f the results are its results bit for bit.  nb != 2 -- there is no rescale without an
+ * unconditional half -- or a NULL eps_mul is PFD_EINVAL. */
+int pfd_cfg_step_mul(const void* eps, int32_t nb, const float* x, int32_t solver, const float* noise, const float* x0_prev,
+                     const int64_t* key, int32_t step, float noise_mul, const float* coef, const float* scale,
+                     const float* eps_mul, const float* x0_keep, const float* mask, int32_t Bm, float ksq, float ks,
+                     float* x_out, float* pred_x0, void* xin_next, int32_t rep, int32_t B, int32_t C, int32_t h, int32_t w,
+                     pfd_stream_t stream);
 /* uint8 mask(s) [Bm, Hm, Wm] -> the binary grid [Bm, gh, gw], fp32 0.0 / 1.0 (out_f32 != 0) or uint8 0 / 1.  Cell y
  * covers mask rows lo = (y*Hm)/gh up to hi = max(lo + 1, ceil((y+1)*Hm/gh)) in integer arithmetic, columns alike; a cell
  * is set if any pixel of its footprint is >= 128.  Footprints are never empty and together cover the mask: the rule

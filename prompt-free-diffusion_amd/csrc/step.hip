@@ -1,6 +1,8 @@
 // The fused CFG combine + sampler step: ONE kernel behind the five entry points pfd_cfg_ddim_step,
-// pfd_cfg_ddim_step_rng, pfd_cfg_ddim_step_ps, pfd_cfg_dpmpp_step and pfd_cfg_step_masked, one launch per step.  Per element:
-//   e      = the guided eps (nb = 2: eu + scale (ec - eu); nb = 1: eu scale), scale the row's or scale_ps[b]
+// pfd_cfg_ddim_step_rng, pfd_cfg_ddim_step_ps, pfd_cfg_dpmpp_step and pfd_cfg_step_masked -- and pfd_cfg_step_mul, any of the
+// five with a per-sample factor on the guided eps (guidance rescale) --, one launch per step.  Per element:
+//   e      = the guided eps (nb = 2: eu + scale (ec - eu); nb = 1: eu scale), scale the row's or scale_ps[b]; times
+//            eps_mul[b] where the entry point has one
 //   pred   = (x - sqrt(1-a_t) e) / sqrt(a_t)
 //   xp     = DDIM: sqrt(a_prev) pred + dir e [+ sigma noise], the noise a tensor or the seeded stream-0 normal times noise_mul
 //            DPM-Solver++(2M): c_x x + c_d D, D = pred or w_cur pred + w_prev x0_prev
@@ -31,6 +33,7 @@ struct StepArgs {
   const int64_t* key;      // KEYED: [B][2] (seed, sample_id)
   const float* coef;       // DDIM {a_t, a_prev, sigma, sqrt(1-a_t), scale}; DPM {a_t, sqrt(1-a_t), c_x, c_d, w_cur, w_prev, scale, 0}
   const float* scale_ps;   // [B] per-sample guidance scales in place of the row's, or NULL
+  const float* eps_mul;    // [B] guidance rescale: the guided eps of sample b times eps_mul[b] (guidance.hip), or NULL
   const float* x0_keep;    // MASKED
   const float* mask;       // MASKED: [1 | B, h, w]
   float* x_out;
@@ -190,7 +193,8 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const StepArgs a) {
     for (int j = 0; j < 4; ++j) {
       xo4[j] = p04[j] = 0.f;
       if (!VEC && e0 + j >= ns) continue;
-      const float e = guided_eps(eu[j], ec[j], a.nb, scale);
+      float e = guided_eps(eu[j], ec[j], a.nb, scale);
+      if (a.eps_mul) e = a.eps_mul[b] * e;   // a rounded product, for pred_x0 and the update alike; uniform over the launch
       const float p0 = pred_x0_of(xv[j], e, s1mat, isq_at);
       float xp;
       if (SOLVER == kSolverDdim) {
@@ -359,4 +363,39 @@ extern "C" int pfd_cfg_step_masked(const void* eps, int32_t nb, const float* x, 
     case kTooLarge: return refuse(PFD_ESHAPE, "pfd_cfg_step_masked: more than 2^34 elements per sample");
   }
   return launch_step(a, solver, true, stream, "pfd_cfg_step_masked");
+}
+
+// Any of the five above with the guidance-rescale factor eps_mul [B] (pfd_guidance_rescale_f32) on the guided eps.  The
+// arguments are the union of the five signatures, NULL where the entry point stood for has none; which one that is follows
+// from them: a mask -> pfd_cfg_step_masked; else solver 1 -> pfd_cfg_dpmpp_step; else a scale -> pfd_cfg_ddim_step_ps, a key
+// -> pfd_cfg_ddim_step_rng, neither -> pfd_cfg_ddim_step.  Its rules for which pointers go together, its check_step and its
+// instantiation apply, so eps_mul of ones gives that entry point's bits.  There is no rescale without an unconditional half.
+extern "C" int pfd_cfg_step_mul(const void* eps, int32_t nb, const float* x, int32_t solver, const float* noise,
+                                const float* x0_prev, const int64_t* key, int32_t step, float noise_mul, const float* coef,
+                                const float* scale, const float* eps_mul, const float* x0_keep, const float* mask, int32_t Bm,
+                                float ksq, float ks, float* x_out, float* pred_x0, void* xin_next, int32_t rep, int32_t B,
+                                int32_t C, int32_t h, int32_t w, pfd_stream_t stream) {
+  if (!eps_mul) return refuse(PFD_EINVAL, "pfd_cfg_step_mul: eps_mul must not be NULL (without it, call the entry point itself)");
+  if (nb != 2) return refuse(PFD_EINVAL, "pfd_cfg_step_mul: nb must be 2: there is no rescale without an unconditional half");
+  StepArgs a = step_args(eps, nb, x, coef, scale, x_out, pred_x0, xin_next, rep, B, C, h, w);
+  a.eps_mul = eps_mul;
+  const bool masked = mask != nullptr;
+  StepFault f;
+  if (masked) {
+    if (noise) return refuse(PFD_EINVAL, "pfd_cfg_step_mul: the masked step has no form with a noise tensor");
+    a.x0_prev = x0_prev; a.key = key; a.step = step; a.noise_mul = noise_mul; a.x0_keep = x0_keep; a.mask = mask;
+    a.mask_bcast = Bm == 1 && B > 1 ? 1 : 0; a.ksq = ksq; a.ks = ks;
+    f = check_step(a, key && x0_keep, solver, true, Bm, true);
+  } else if (x0_keep) {
+    return refuse(PFD_EINVAL, "pfd_cfg_step_mul: x0_keep comes with a mask");
+  } else if (solver == kSolverDpmpp) {
+    if (noise || key) return refuse(PFD_EINVAL, "pfd_cfg_step_mul: DPM-Solver++ is deterministic: no noise tensor, no key");
+    a.x0_prev = x0_prev;
+    f = check_step(a, true, kSolverDpmpp, false, 0, true);
+  } else {
+    a.noise = noise; a.key = key; a.step = step; a.noise_mul = noise_mul; a.x0_prev = x0_prev;   // (a history: refused below)
+    f = check_step(a, !(noise && key), solver, false, 0, key != nullptr);
+  }
+  if (f != kStepOk) return refuse(f == kTooLarge ? PFD_ESHAPE : PFD_EINVAL, "pfd_cfg_step_mul: arguments the entry point it stands for refuses");
+  return launch_step(a, solver, masked, stream, "pfd_cfg_step_mul");
 }

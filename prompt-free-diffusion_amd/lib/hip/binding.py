@@ -93,6 +93,9 @@ SIGNATURES = {
     "pfd_latent_start": (_i32, [_vp, _i32, _vp, _f32, _f32, _f32, _f32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pfd_cfg_step_masked": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _vp, _vp,
                                    _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "pfd_guidance_rescale_f32": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i64, _vp]),
+    "pfd_cfg_step_mul": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32,
+                                _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "pfd_mask_grid_u8": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "pfd_composite_u8": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pfd_add_f16": (_i32, [_vp, _vp, _vp, _i64, _vp]),

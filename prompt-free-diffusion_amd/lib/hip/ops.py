@@ -979,6 +979,62 @@ def guidance_scale_rows(scale, B, device):
     return scale
 
 
+def guidance_phi_rows(phi, B, device):
+    """the per-sample guidance-rescale factors phi, checked like guidance_scale_rows: a contiguous float32 [B] next to x.
+    Their range, [0, 1], is the sampler's to check (DDIMSampler moves the vector once per request)"""
+    if not (torch.is_tensor(phi) and phi.dtype == torch.float32 and tuple(phi.shape) == (B,) and phi.is_contiguous()):
+        raise ValueError(f"the guidance-rescale factors must be a contiguous float32 tensor [{B}]")
+    if not phi.is_cuda or phi.device != torch.device(device):
+        raise ValueError(f"the guidance-rescale factors must live on {device}, next to eps")
+    return phi
+
+
+def guidance_rescale(eps, scale_or_rows, phi_rows):
+    """The per-sample factor of guidance rescale (pfd_guidance_rescale_f32; lib/guidance.py is the same function in fp64):
+    mul[b] = phi[b] * std(ec_b) / std(g_b) + (1 - phi[b]), g the guided eps as the step kernel rounds it.  eps: f16 NHWC
+    [2B, h, w, C], unconditional half first; scale_or_rows: a float32 tensor [B] (per-sample scales) or a float32 tensor
+    of one element on the device (one scale for all, e.g. coef[index][4] -- a view, nothing is copied); phi_rows: float32
+    [B] on the device.  Returns mul, float32 [B], for the eps_mul= of the step ops.  One launch; reads nothing back."""
+    if not (torch.is_tensor(eps) and eps.dtype == torch.float16 and eps.dim() == 4 and eps.shape[0] % 2 == 0 and
+            eps.shape[0] > 0 and eps.is_contiguous()):
+        raise ValueError("guidance_rescale: eps must be a contiguous f16 NHWC tensor [2B, h, w, C], unconditional half first")
+    if not eps.is_cuda:
+        raise RuntimeError("guidance_rescale: eps must live on the GPU; the HIP path has no CPU fallback")
+    B = int(eps.shape[0]) // 2
+    n = eps[0].numel()
+    phi_rows = guidance_phi_rows(phi_rows, B, eps.device)
+    sc = scale_or_rows
+    if not (torch.is_tensor(sc) and sc.dtype == torch.float32 and sc.is_cuda and sc.device == eps.device):
+        raise ValueError("guidance_rescale: the scale must be a float32 tensor next to eps (one element, or one per sample)")
+    if sc.numel() == 1:
+        s_stride = 0
+    elif tuple(sc.shape) == (B,) and sc.stride(0) >= 0:
+        s_stride = int(sc.stride(0))
+    else:
+        raise ValueError(f"guidance_rescale: the scale must have one element or the shape [{B}], got {tuple(sc.shape)}")
+    mul = torch.empty((B,), dtype=torch.float32, device=eps.device)
+    rc = _lib().pfd_guidance_rescale_f32(eps.data_ptr(), sc.data_ptr(), s_stride, phi_rows.data_ptr(), 1, mul.data_ptr(), B,
+                                         n, _stream())
+    _b.check(rc, "pfd_guidance_rescale_f32")
+    return mul
+
+
+def _step_mul(eps, nb, x, solver, coef, eps_mul, outs, *, noise=None, x0_prev=None, key=None, step=None, noise_mul=1.0,
+              scale=None, x0_keep=None, mask=None, ksq=0.0, ks=0.0):
+    """the step ops with eps_mul=: pfd_cfg_step_mul, the entry point the op would have called plus the factor per sample"""
+    B = x.shape[0]
+    if nb != 2:
+        raise ValueError("eps_mul (guidance rescale) needs the unconditional half: nb must be 2")
+    if not (torch.is_tensor(eps_mul) and eps_mul.dtype == torch.float32 and tuple(eps_mul.shape) == (B,) and
+            eps_mul.is_contiguous() and eps_mul.device == x.device):
+        raise ValueError(f"eps_mul must be a contiguous float32 tensor [{B}] next to x (ops.guidance_rescale)")
+    rc = _lib().pfd_cfg_step_mul(eps.data_ptr(), nb, x.data_ptr(), solver, _ptr(noise), _ptr(x0_prev), _ptr(key),
+                                 0 if step is None else int(step), float(noise_mul), coef.data_ptr(), _ptr(scale),
+                                 eps_mul.data_ptr(), _ptr(x0_keep), _ptr(mask), 0 if mask is None else int(mask.shape[0]),
+                                 float(ksq), float(ks), *outs)
+    _b.check(rc, "pfd_cfg_step_mul")
+
+
 def _step_outputs(x, rep, want_next):
     """(x_prev | x_next, pred_x0) fp32 like x, and the next UNet input f16 NHWC [rep*B, h, w, C] or None"""
     B, Cc, h, w = x.shape
@@ -987,14 +1043,16 @@ def _step_outputs(x, rep, want_next):
 
 
 def cfg_ddim_step(eps, nb, x, coef, *, noise=None, want_next=True, rep=None, noise_key=None, step=None, noise_mul=1.0,
-                  scale=None):
+                  scale=None, eps_mul=None):
     """Fused CFG combine + DDIM update.  eps NHWC f16 [nb*B,h,w,C]; x NCHW fp32 [B,C,h,w];
     coef fp32[5] device.  Returns (x_prev fp32 NCHW, pred_x0 fp32 NCHW, xin_next f16 NHWC|None);
     xin_next holds `rep` copies of the batch (default nb: the CFG-doubled UNet input).
     noise: fp32 NCHW tensor added as sigma * noise, or -- noise_key int64 [B,2] (seed, sample_id), step, noise_mul --
     the seeded noise sigma * noise_mul * z(key[b], step, element) evaluated inside the kernel (philox_normal).
     scale: fp32 [B] tensor, the guidance scale of sample b in place of coef[4] (pfd_cfg_ddim_step_ps; with noise,
-    noise_key or neither).  None: coef[4] for the whole batch."""
+    noise_key or neither).  None: coef[4] for the whole batch.
+    eps_mul: fp32 [B] tensor (guidance_rescale), the guided eps of sample b times eps_mul[b] (pfd_cfg_step_mul: the same
+    kernel; ones give the bits of the call without it).  None: the call is what it was."""
     B, Cc, h, w = x.shape
     rep = nb if rep is None else rep
     if noise_key is not None:
@@ -1007,6 +1065,9 @@ def cfg_ddim_step(eps, nb, x, coef, *, noise=None, want_next=True, rep=None, noi
         scale = guidance_scale_rows(scale, B, x.device)
     x_prev, pred_x0, xin = _step_outputs(x, rep, want_next)
     outs = (x_prev.data_ptr(), pred_x0.data_ptr(), _ptr(xin), rep, B, Cc, h, w, _stream())
+    if eps_mul is not None:
+        _step_mul(eps, nb, x, 0, coef, eps_mul, outs, noise=noise, key=noise_key, step=step, noise_mul=noise_mul, scale=scale)
+        return x_prev, pred_x0, xin
     if scale is not None:
         name = "pfd_cfg_ddim_step_ps"
         args = (_ptr(noise), _ptr(noise_key), 0 if step is None else int(step), float(noise_mul), coef.data_ptr(),
@@ -1019,11 +1080,12 @@ def cfg_ddim_step(eps, nb, x, coef, *, noise=None, want_next=True, rep=None, noi
     return x_prev, pred_x0, xin
 
 
-def cfg_dpmpp_step(eps, nb, x, coef, x0_prev=None, want_next=False, rep=None, scale=None):
+def cfg_dpmpp_step(eps, nb, x, coef, x0_prev=None, want_next=False, rep=None, scale=None, eps_mul=None):
     """Fused CFG combine + one DPM-Solver++(2M) step (pfd_cfg_dpmpp_step).  eps NHWC f16 [nb*B,h,w,C]; x NCHW fp32
     [B,C,h,w]; coef fp32[8] device, one row of lib/solver.py::dpmpp_2m_table.  x0_prev: the pred_x0 of the step before
     (fp32 NCHW, like x), or None for a first-order step (= DDIM at eta 0; the weights of the row are not read).
     scale: fp32 [B] tensor, the guidance scale of sample b in place of coef[6]; None: coef[6] for the whole batch.
+    eps_mul: as in cfg_ddim_step.
     Returns (x_next fp32 NCHW, pred_x0 fp32 NCHW, xin_next f16 NHWC|None) like cfg_ddim_step."""
     B, Cc, h, w = x.shape
     rep = nb if rep is None else rep
@@ -1035,6 +1097,10 @@ def cfg_dpmpp_step(eps, nb, x, coef, x0_prev=None, want_next=False, rep=None, sc
     if scale is not None:
         scale = guidance_scale_rows(scale, B, x.device)
     x_next, pred_x0, xin = _step_outputs(x, rep, want_next)
+    if eps_mul is not None:
+        _step_mul(eps, nb, x, 1, coef, eps_mul, (x_next.data_ptr(), pred_x0.data_ptr(), _ptr(xin), rep, B, Cc, h, w, _stream()),
+                  x0_prev=x0_prev, scale=scale)
+        return x_next, pred_x0, xin
     rc = _lib().pfd_cfg_dpmpp_step(eps.data_ptr(), nb, x.data_ptr(), _ptr(x0_prev), coef.data_ptr(), _ptr(scale),
                                    x_next.data_ptr(), pred_x0.data_ptr(), _ptr(xin), rep, B, Cc, h, w, _stream())
     _b.check(rc, "pfd_cfg_dpmpp_step")
@@ -1058,14 +1124,14 @@ def mask_rows(mask, B, h, w):
 
 
 def cfg_step_masked(eps, nb, x, coef, *, solver='ddim', x0_prev=None, keep_key=None, step=None, x0_keep=None, mask=None,
-                    ksq=None, ks=None, noise_mul=1.0, scale=None, want_next=True, rep=None):
+                    ksq=None, ks=None, noise_mul=1.0, scale=None, want_next=True, rep=None, eps_mul=None):
     """The masked (inpainting) form of cfg_ddim_step (solver='ddim') / cfg_dpmpp_step (solver='dpmpp') in one launch
     (pfd_cfg_step_masked; lib/inpaint.py is the same function on the host): x_out = m * xp + (1 - m) * known with xp the
     unmasked update and known = ksq * x0_keep + ks * z_keep, z_keep the stream-3 normal of (keep_key[b], step, element).
     keep_key: int64 [B, 2] rows (seed, sample_id), required: a DDIM row with sigma != 0 draws its step noise from the same
     rows (stream 0, times noise_mul) -- there is no form with a noise tensor.  x0_keep: fp32 NCHW like x, the clean latent
     of the init picture (latent_start(..., want_x0=True)); mask: fp32 [1 | B, h, w] in [0, 1], 1 = regenerate; ksq, ks:
-    lib/inpaint.py::step_constants of the row stepped to.  coef, x0_prev, scale, want_next, rep: as in the unmasked ops.
+    lib/inpaint.py::step_constants of the row stepped to.  coef, x0_prev, scale, eps_mul, want_next, rep: as in the unmasked ops.
     The mask's values are the caller's (reading them back would synchronise a loop that is captured): outside [0, 1] the
     blend extrapolates, nothing is read or written out of bounds.
     Returns (x_out fp32 NCHW, pred_x0 fp32 NCHW -- the unmasked one --, xin_next f16 NHWC | None)."""
@@ -1110,6 +1176,11 @@ def cfg_step_masked(eps, nb, x, coef, *, solver='ddim', x0_prev=None, keep_key=N
     if scale is not None:
         scale = guidance_scale_rows(scale, B, x.device)
     x_out, pred_x0, xin = _step_outputs(x, rep, want_next)
+    if eps_mul is not None:
+        _step_mul(eps, nb, x, MASKED_SOLVERS[solver], coef, eps_mul,
+                  (x_out.data_ptr(), pred_x0.data_ptr(), _ptr(xin), rep, B, Cc, h, w, _stream()), x0_prev=x0_prev, key=keep_key,
+                  step=step, noise_mul=noise_mul, scale=scale, x0_keep=x0_keep, mask=mask, ksq=ksq, ks=ks)
+        return x_out, pred_x0, xin
     rc = _lib().pfd_cfg_step_masked(eps.data_ptr(), nb, x.data_ptr(), MASKED_SOLVERS[solver], _ptr(x0_prev),
                                     keep_key.data_ptr(), int(step), float(noise_mul), coef.data_ptr(), _ptr(scale),
                                     x0_keep.data_ptr(), mask.data_ptr(), int(mask.shape[0]), float(ksq), float(ks),

@@ -77,10 +77,20 @@ control=None: it IS the uncontrolled step, the ControlNet is not evaluated.  A s
 (pfd_add_scaled_rows_f16 in place of the 13 plain adds).  The table is one more static graph input behind the others --
 another strength replays the same graph -- and the graph key gains a trailing ('control', lo, hi).  The multi-context loop
 and the single-step entry points refuse both keys.  Without them every path, launch sequence and graph key is what it was.
+
+Guidance rescale (opt-in): c_info['guidance_rescale'] = phi, one number or `bs` numbers in [0, 1] (lib/guidance.py; Lin et al.
+2023, section 3.4; diffusers' `guidance_rescale`).  Each step is then two launches: ops.guidance_rescale turns the UNet's eps,
+the scale and phi into one factor per sample -- phi std(eps_cond) / std(eps_guided) + 1 - phi --, and the step kernel
+multiplies its guided eps by it (eps_mul=, pfd_cfg_step_mul: the same kernel instantiation as without).  Every solver,
+seeded noise, per-sample scale, img2img start, mask, bias, regions and control; p_sample_ddim too.  The phi vector is one more
+static graph input behind the others -- another phi replays the same graph -- and the graph key gains a trailing
+('rescale',).  Absent, all zero, or without an unconditional half (scale 1) it IS the plain request: same path, same graph
+key, same bits.  The multi-context entry points refuse it.
 """
 import numpy as np
 import torch
 
+from .. import guidance as _guidance_spec
 from .. import inpaint as _inpaint
 from .. import solver as _solver
 from ..hip import ops
@@ -239,6 +249,32 @@ def _control_strength(c_info, has_hint, rows, total_steps, device):
     return tab.to(device).contiguous(), (lo, hi)
 
 
+def _refuse_rescale(c_infos, what):
+    if any(ci.get('guidance_rescale', None) is not None for ci in c_infos):
+        raise ValueError(f"{what} takes no c_info['guidance_rescale']: guidance rescale goes with sample / ddim_sampling / "
+                         "p_sample_ddim")
+
+
+def _rescale(c_info, bs, nb, device):
+    """-> None (the plain request: absent, all zero, or no unconditional half), or the fp32 [bs] vector of phi on the device;
+    c_info['guidance_rescale'] is one number or bs numbers, finite and in [0, 1], checked whatever the outcome"""
+    phi = c_info.get('guidance_rescale', None)
+    if phi is None:
+        return None
+    if torch.is_tensor(phi):
+        phi = phi.detach().cpu().numpy()
+    v = _guidance_spec.normalise(phi, bs, nb)
+    return None if v is None else torch.from_numpy(v).to(device).contiguous()
+
+
+def _rescale_args(eps, sps, coef_row, scale_at, phi):
+    """the extra keyword of a step op for a rescaled request ({} for a plain one: the call is what it was): the statistics
+    launch on this step's eps, with the per-sample scales or the row's"""
+    if phi is None:
+        return {}
+    return {'eps_mul': ops.guidance_rescale(eps, sps if sps is not None else coef_row[scale_at:scale_at + 1], phi)}
+
+
 def _key_bias(c_info, cond, cfg, device):
     """-> None, or the fp32 [nb * bs, Nk] logits next to c_in (unconditional rows first): c_info['key_bias'] /
     ['unconditional_key_bias'], a missing one all zeros"""
@@ -277,7 +313,8 @@ def _step_noise(x, sigma, index, nkey, temperature, noise_dropout, repeat_noise=
 
 class _CapturedLoop:
     """one captured trajectory: the hipGraph, its static inputs in the order (x, c_in, hint, nkey, sps) -- None where the
-    request has none --, behind them (mask, x0_keep, keep_key) of a masked request, its static outputs and what must live as long as the graph"""
+    request has none --, behind them (mask, x0_keep, keep_key) of a masked request, then the bias, the regional table and maps,
+    the control table and the guidance-rescale phi, each at its fixed position, its static outputs and what must live as long as the graph"""
 
     def __init__(self, graph, inputs, outs, keep):
         self.graph, self.inputs, self.outs, self.keep = graph, inputs, outs, keep
@@ -406,13 +443,14 @@ class DDIMSampler(object):
             nkey = ops.noise_key_rows(nkey, bs, device)
         mask, x0_keep, kkey = _masked_inputs(x_info, x, nkey, stochastic)
         ctab, csteps = _control_strength(c_info, hint is not None, nb * bs, total_steps, device)
+        phi = _rescale(c_info, bs, nb, device)
 
         def make_loop():
             """the whole trajectory as a pure function of device tensors (capturable as one hipGraph), and its timestep table"""
             t_table = t_col.repeat(1, nb * bs)
 
             def run_loop(x, c_in, hint, nkey, sps, mask=None, x0_keep=None, kkey=None, kbias=None, rtable=None, qmaps=None,
-                         ctab=None):
+                         ctab=None, phi=None):
                 from .controlnet import PreparedHint
                 ps = {} if sps is None else {'scale': sps}
                 if rtable is not None:      # (the maps were made on the host, in front of the capture: views of a static input)
@@ -442,6 +480,7 @@ class DDIMSampler(object):
                             ctl_i = None
                     eps = model.apply_model_nhwc(x_type, xin, t_table[i], c_type, ctx, control=ctl_i,
                                                  emb_table=emb_all[i:i + 1], cfg_pair=pair, **how)
+                    rs = _rescale_args(eps, sps, coef[index], 4 if order is None else 6, phi)
                     if mask is not None:
                         # masked regeneration: the same step, blended with the init picture's own trajectory outside the mask
                         ksq, ks = _inpaint.step_constants(self.ddim_alphas_prev[index], index)
@@ -449,18 +488,18 @@ class DDIMSampler(object):
                         x, pred_x0, xin = ops.cfg_step_masked(
                             eps, nb, x, coef[index], solver='ddim' if order is None else 'dpmpp',
                             x0_prev=None if first_order else x0_last, keep_key=kkey, step=index, x0_keep=x0_keep, mask=mask,
-                            ksq=float(ksq), ks=float(ks), noise_mul=temperature, want_next=True, rep=rep, **ps)
+                            ksq=float(ksq), ks=float(ks), noise_mul=temperature, want_next=True, rep=rep, **ps, **rs)
                         x0_last = pred_x0
                     elif order is not None:
                         # multistep: this step's pred_x0 is the next step's history; none on the first step of a run
                         # (an img2img start included) nor on the last, nor at order 1
                         first_order = order == 1 or i == 0 or index == 0
                         x, pred_x0, xin = ops.cfg_dpmpp_step(eps, nb, x, coef[index], None if first_order else x0_last,
-                                                             want_next=True, rep=rep, **ps)
+                                                             want_next=True, rep=rep, **ps, **rs)
                         x0_last = pred_x0
                     else:
                         noise = _step_noise(x, self.ddim_sigmas[index], index, nkey, temperature, noise_dropout)
-                        x, pred_x0, xin = ops.cfg_ddim_step(eps, nb, x, coef[index], want_next=True, rep=rep, **ps, **noise)
+                        x, pred_x0, xin = ops.cfg_ddim_step(eps, nb, x, coef[index], want_next=True, rep=rep, **ps, **noise, **rs)
                     if index % log_every_t == 0 or index == total_steps - 1:
                         inter_xt.append(x)
                         inter_x0.append(pred_x0)
@@ -478,6 +517,8 @@ class DDIMSampler(object):
             inputs = inputs + (regs[0], regs[1])
         if ctab is not None:                  # behind every other static input, absent ones as None
             inputs = inputs + (None,) * (11 - len(inputs)) + (ctab,)
+        if phi is not None:                   # ... and phi behind the table
+            inputs = inputs + (None,) * (12 - len(inputs)) + (phi,)
         # a keyed schedule draws nothing from a generator: capturable whatever eta is
         if self.use_graph and (not stochastic or nkey is not None) and callback is None and x.is_cuda:
             # one hipGraph per (shape, schedule, weights version, flags); static input buffers, replayed per request.
@@ -497,6 +538,8 @@ class DDIMSampler(object):
                 key = key + (('regions', int(regs[0].shape[1]), tuple(regs[2])),)     # ... and without regions
             if csteps is not None:
                 key = key + (('control', csteps[0], csteps[1]),)     # ... and without a scaled / windowed control
+            if phi is not None:
+                key = key + (('rescale',),)                          # ... and without guidance rescale; phi is an input, not a key
             xf, ixt, ix0 = self._graph_for(key, lambda: self._capture(*make_loop(), inputs, coef)).replay(inputs)
         else:
             xf, ixt, ix0 = make_loop()[0](*inputs)
@@ -529,7 +572,7 @@ class DDIMSampler(object):
         return x.contiguous(), timesteps
 
     def _single_step(self, x_info, eps, nb, xf, dtype, scale, sps, index, repeat_noise, use_original_steps,
-                     noise_dropout, temperature):
+                     noise_dropout, temperature, phi=None):
         """the tail of p_sample_ddim and p_sample_ddim_multicontext: coefficient row, noise, the step -> (x_prev, pred_x0)"""
         coef = self._coef_table(scale, use_original_steps)[index]
         sig = (self.ddim_sigmas_for_original_num_steps if use_original_steps else self.ddim_sigmas)[index]
@@ -538,7 +581,8 @@ class DDIMSampler(object):
             raise ValueError("noise_dropout > 0 is not available with x_info['noise_key']")
         ps = {} if sps is None else {'scale': sps}
         noise = _step_noise(xf, sig, index, nkey, temperature, noise_dropout, repeat_noise)
-        x_prev, pred_x0, _ = ops.cfg_ddim_step(eps, nb, xf, coef, want_next=False, **ps, **noise)
+        rs = _rescale_args(eps, sps, coef, 4, phi)
+        x_prev, pred_x0, _ = ops.cfg_ddim_step(eps, nb, xf, coef, want_next=False, **ps, **noise, **rs)
         return x_prev.to(dtype), pred_x0.to(dtype)
 
     # ---- multi-context sampling (ddim.py:174-299) ------------------------------------------------
@@ -551,6 +595,7 @@ class DDIMSampler(object):
         _refuse_mask(x_info, "sample_multicontext")
         _refuse_bias(c_info_list, "sample_multicontext")
         _refuse_control(c_info_list, "sample_multicontext")
+        _refuse_rescale(c_info_list, "sample_multicontext")
         self.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=verbose)
         if verbose:
             print(f'Data shape for DDIM sampling is {shape}, eta {eta}')
@@ -565,6 +610,7 @@ class DDIMSampler(object):
         scale = None
         _refuse_bias(c_info_list, "multi-context sampling")
         _refuse_control(c_info_list, "multi-context sampling")
+        _refuse_rescale(c_info_list, "multi-context sampling")
         for ci in c_info_list:
             if is_per_sample(ci['unconditional_guidance_scale']):
                 raise ValueError("a per-sample guidance scale is out of scope for multi-context sampling: give one "
@@ -697,6 +743,7 @@ class DDIMSampler(object):
         _refuse_control([c_info], "p_sample_ddim")
         x = x_info['x']
         sps, scale, uc, cfg, nb = _guidance(c_info, x.shape[0], x.device)
+        phi = _rescale(c_info, x.shape[0], nb, x.device)      # checked before the model runs
         if cfg:
             c_in = torch.cat([uc, c_info['conditioning']])
             t_in = torch.cat([t] * 2)
@@ -714,5 +761,6 @@ class DDIMSampler(object):
         xf = x.to(torch.float32).contiguous()
         eps = self.model.apply_model_nhwc(x_info['type'], ops.to_nhwc(xf, rep=nb), t_in, c_info['type'], ctx,
                                           control=c_info.get('control', None))
+        rs = {} if phi is None else {'phi': phi}      # (the plain call is what it was)
         return self._single_step(x_info, eps, nb, xf, x.dtype, scale, sps, index, repeat_noise, use_original_steps,
-                                 noise_dropout, temperature)
+                                 noise_dropout, temperature, **rs)

@@ -81,6 +81,21 @@ def shard_scales(scales, rank, world_size):
     return v[rank * n:(rank + 1) * n].clone()
 
 
+def shard_rescale(guidance_rescale, n_global, rank, world_size):
+    """generate's guidance_rescale for this rank: checked for the GLOBAL batch (one number or n_global numbers in [0, 1],
+    lib/guidance.check_phi), cut like shard_scales -- sample j keeps its phi whatever P is.  -> None when nothing of it is
+    left on this rank's samples (all zero: the plain request), else float32 [n_local] on the CPU"""
+    from . import guidance as guidance_lib
+    if torch.is_tensor(guidance_rescale):
+        guidance_rescale = guidance_rescale.detach().cpu().numpy()
+    v = guidance_lib.check_phi(guidance_rescale, n_global)
+    if n_global % world_size:
+        raise ValueError(f"{n_global} guidance-rescale factors do not divide over {world_size} ranks")
+    n = n_global // world_size
+    local = guidance_lib.normalise(v[rank * n:(rank + 1) * n], n)
+    return None if local is None else torch.from_numpy(local)
+
+
 def force_collective():
     """PFD_FORCE_COLLECTIVE=1 with an initialised process group: the collectives run even at world size 1 -- the
     one-GPU RCCL smoke (tests/test_hip_parity.py::test_rccl_one_rank_collectives, `bench.py --gpus 1` under that
@@ -467,7 +482,7 @@ class PromptFreePipeline:
                  device_noise=False, solver='ddim', control_preprocess=None, control_thresholds=(100, 200), init=None,
                  strength=0.75, init_posterior='sample', mask=None, composite=False, image_weights=None, regions=None,
                  region_weights=None, control_scale=1.0, control_layer_scales=None, control_window=(0.0, 1.0),
-                 control_cond_only=False):
+                 control_cond_only=False, guidance_rescale=0.0):
         """returns (images, latents [n_local,4,h,w]); images = [n_local | n_global (gather), 3, H, W] in [0,1]
         in the model dtype, or -- as_uint8 -- packed uint8 [n, H, W, 3] (the bytes ToPILImage would produce,
         app.py:273-275; 4x fewer bytes through the all-gather); decode=False returns the latents twice.
@@ -519,7 +534,13 @@ class PromptFreePipeline:
         `strength` is; a step outside it is the uncontrolled step and does not run the ControlNet.  control_cond_only: the
         unconditional half of the CFG batch gets no control.  All at their defaults: the plain control request, its path,
         graph and bits.  Nothing left of the control (scale 0, an empty window): the request without `control`, bit for bit.
-        Works with every other argument; draws nothing."""
+        Works with every other argument; draws nothing.
+        guidance_rescale: phi in [0, 1], one number or one per sample of the GLOBAL batch (lib/guidance.py; Lin et al. 2023,
+        section 3.4; diffusers' `guidance_rescale`): the guided eps of every step is brought back to the standard deviation
+        of the sample's conditional eps and blended by phi, which keeps pictures from burning out at the scales used with a
+        reference (0.7 is the paper's value).  One small launch in front of the step kernel (pfd_guidance_rescale_f32); a
+        sample's result does not depend on its company nor on the world size.  0 (or all zero, or scale 1): the plain
+        request, its path, graph and bits.  Works with every other argument; draws nothing."""
         from .model_zoo.ddim import is_per_sample
         from .solver import solver_order
         if solver_order(solver) is not None and (eta != 0. or device_noise):     # an unknown name raises here too
@@ -534,6 +555,7 @@ class PromptFreePipeline:
             if tuple(torch.as_tensor(scale).shape) != (n_global,):
                 raise ValueError(f"scale must be one number or {n_global} numbers, one per sample of the global batch")
             scale = shard_scales(scale, r, P)
+        phi = shard_rescale(guidance_rescale, n_global, r, P)     # checked before anything touches the device
         if torch.is_tensor(control) and control.dim() == 4 and control.shape[0] not in (1, n_global // P):
             raise ValueError(f"control must be [1, 3, H, W] (shared) or [{n_global // P}, 3, H, W] (one hint per local "
                              f"sample): got {control.shape[0]} hints")
@@ -625,6 +647,8 @@ class PromptFreePipeline:
             if ctl_strength is not None:
                 c_info['control_scale'] = torch.from_numpy(ctl_strength[0]).to(dev)
                 c_info['control_steps'] = ctl_strength[1]
+        if phi is not None and (is_per_sample(scale) or scale != 1.):     # (scale 1: no unconditional half, nothing to rescale)
+            c_info['guidance_rescale'] = phi
         how = {} if solver == 'ddim' else {'solver': solver}     # the default call is what it was
         x, _ = self.sampler.sample(steps=steps, shape=shape, x_info=x_info, c_info=c_info, eta=eta,
                                    verbose=verbose, **how)

@@ -24,6 +24,10 @@ ControlNet strength (submit(control_scale=, control_layer_scales=, control_windo
 request whose arguments are off their defaults shares a batch only with requests that have them too, with equal layer
 weights, equal controlled steps and equal cond_only; the strengths may differ, each sample has its own rows of the table.
 A request with nothing left of its control (scale 0, an empty window) IS the uncontrolled request and batches as one.
+
+Guidance rescale (submit(guidance_rescale=), lib/guidance.py): the key gains "has rescale", not the values -- requests with
+it share a batch whatever their phi, each sample with its own (the vector is a static input of one captured graph); a
+request without it (0, or scale 1) never shares a batch with one that has it, so it keeps its graph and its bits.
 """
 import queue
 import threading
@@ -40,7 +44,7 @@ from .solver import solver_order
 class _Request:
     __slots__ = ("image", "n", "height", "width", "steps", "scale", "eta", "seed", "control", "uncond", "as_uint8",
                  "device_noise", "future", "mixed", "solver", "control_preprocess", "control_thresholds", "init", "strength",
-                 "init_k", "mask", "composite", "weights", "regional", "ctl")
+                 "init_k", "mask", "composite", "weights", "regional", "ctl", "rescale")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -59,6 +63,8 @@ class _Request:
             how = how + ('refmix',)
         if self.ctl is not None:      # a scaled / windowed control: equal layers, steps and cond_only; the strengths may differ
             how = how + (('control',) + tuple(self.ctl[1:]),)
+        if self.rescale is not None:  # guidance rescale: with each other only, whatever their phi; every other key is unchanged
+            how = how + ('rescale',)
         if self.mixed:
             return (self.height, self.width, self.steps, float(self.scale) == 1.0, float(self.eta),
                     self.control is None, self.uncond is None, bool(self.as_uint8), bool(self.device_noise)) + how
@@ -94,7 +100,7 @@ class PromptFreeServer:
                control=None, uncond=None, as_uint8=True, device_noise=False, solver='ddim', control_preprocess=None,
                control_thresholds=(100, 200), init=None, strength=0.75, mask=None, composite=False, image_weights=None,
                regions=None, region_weights=None, control_scale=1.0, control_layer_scales=None, control_window=(0.0, 1.0),
-               control_cond_only=False):
+               control_cond_only=False, guidance_rescale=0.0):
         """image [1,3,h,w] in [0,1] (any size); control [1,3,H,W] or None; uncond [1,148,768] or None (zeros).
         image and control may each be a uint8 HWC picture [h,w,3] (torch or numpy, any size; the reference picture
         at least 32 a side) instead: the request carries the bytes and the worker converts them on the device
@@ -130,6 +136,9 @@ class PromptFreeServer:
         lib/control.py): control_scale is one number or n_samples numbers.  Off their defaults, the request shares a batch
         only with requests that have them too and agree in layer weights, controlled steps and cond_only -- the strengths
         may differ.  Nothing left of the control: the request is served as the one without `control`.
+        guidance_rescale: phi in [0, 1], one number or n_samples numbers (PromptFreePipeline.generate, lib/guidance.py).
+        Requests with it share a batch whatever their phi, never with requests without it; 0, or scale 1, is the request
+        without it.
         -> Future of uint8 [n,H,W,3] (as_uint8) or float [n,3,H,W] images"""
         if self._stop:
             raise RuntimeError("server is closed")
@@ -185,7 +194,10 @@ class PromptFreeServer:
             ctl = (control_lib.sample_scales(control_scale.tolist() if torch.is_tensor(control_scale) else control_scale, n_samples),
                    tuple(float(v) for v in control_lib.layer_scales(control_layer_scales)), ctl[1],
                    bool(control_cond_only) and float(scale) != 1.0)
-        r = _Request(image=image, ctl=ctl, n=int(n_samples), height=int(height), width=int(width), steps=int(steps), init=init,
+        from . import guidance as guidance_lib
+        rescale = guidance_lib.normalise(guidance_rescale.tolist() if torch.is_tensor(guidance_rescale) else guidance_rescale,
+                                         int(n_samples), 1 if float(scale) == 1.0 else 2)
+        r = _Request(image=image, ctl=ctl, rescale=rescale, n=int(n_samples), height=int(height), width=int(width), steps=int(steps), init=init,
                      strength=strength, init_k=init_k, mask=mask, composite=bool(composite) if mask is not None else None,
                      scale=scale, eta=eta, seed=int(seed), control=control, uncond=uncond, as_uint8=as_uint8,
                      device_noise=bool(device_noise), future=Future(), mixed=self.mixed_batches or None, solver=solver,
@@ -346,6 +358,9 @@ class PromptFreeServer:
                 tab = control_lib.scale_table(strengths, r0.ctl[1], len(strengths), 2 if per_sample or float(r0.scale) != 1.0 else 1,
                                               r0.ctl[3])
                 c_info['control_scale'], c_info['control_steps'] = torch.from_numpy(tab).to(dev), r0.ctl[2]
+            if r0.rescale is not None:  # each sample its own phi, batch order ("has rescale" is the key)
+                import numpy as np
+                c_info['guidance_rescale'] = torch.from_numpy(np.concatenate([r.rescale for r in batch]))
             x_info = {'type': 'image', 'xt': xT}
             if r0.init is not None:
                 x_info['xt_steps'] = r0.init_k       # equal over the batch: part of the key

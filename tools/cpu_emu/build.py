@@ -1,10 +1,10 @@
 #!/usr/bin/env python
-"""Build the CPU emulation of csrc/gemm_glds.hip, csrc/norm.hip, csrc/attention.hip, csrc/image.hip, csrc/canny.hip, csrc/latent.hip, csrc/inpaint.hip, csrc/step.hip and csrc/control.hip (tools/cpu_emu/emu_*.cpp): write
+"""Build the CPU emulation of csrc/gemm_glds.hip, csrc/norm.hip, csrc/attention.hip, csrc/image.hip, csrc/canny.hip, csrc/latent.hip, csrc/inpaint.hip, csrc/step.hip, csrc/control.hip and csrc/guidance.hip (tools/cpu_emu/emu_*.cpp): write
 <file>_emu.inc = the kernel file with its gfx950 inline-asm statements replaced by their C meaning, then compile the
 drivers for the host with clang++.
 (emu_attn drives pfd_attention_f16 and, with --kbias, pfd_attention_kbias_f16: the LDS-DMA load of the key logits is the shim's
 __builtin_amdgcn_global_load_lds, the opaque register pins of its KBIAS builds fall under the first substitution below.)
-usage: [EMU_DEFINES="-DPFD_FAST_PROLOGUE ..."] build.py [outdir]   (default /tmp/pfd_cpu_emu)  -> <outdir>/emu_gemm, <outdir>/emu_norm, <outdir>/emu_attn, <outdir>/emu_image, <outdir>/emu_canny, <outdir>/emu_latent, <outdir>/emu_inpaint, <outdir>/emu_step, <outdir>/emu_control"""
+usage: [EMU_DEFINES="-DPFD_FAST_PROLOGUE ..."] build.py [outdir]   (default /tmp/pfd_cpu_emu)  -> <outdir>/emu_gemm, <outdir>/emu_norm, <outdir>/emu_attn, <outdir>/emu_image, <outdir>/emu_canny, <outdir>/emu_latent, <outdir>/emu_inpaint, <outdir>/emu_step, <outdir>/emu_control, <outdir>/emu_guidance"""
 import os
 import re
 import subprocess
@@ -50,7 +50,7 @@ def main():
     only = os.environ.get("EMU_ONLY", "").split()     # e.g. EMU_ONLY=emu_gemm: just that driver
     for name, driver in (("gemm_glds", "emu_gemm"), ("norm", "emu_norm"), ("attention", "emu_attn"), ("image", "emu_image"),
                          ("canny", "emu_canny"), ("latent", "emu_latent"), ("inpaint", "emu_inpaint"), ("step", "emu_step"),
-                         ("control", "emu_control")):
+                         ("control", "emu_control"), ("guidance", "emu_guidance")):
         if only and driver not in only:
             continue
         preprocess(name, out)
@@ -58,6 +58,9 @@ def main():
             preprocess("attention2_kernel", out, ext=".inc", outname="attention2_kernel.inc")
         if name == "control":       # its driver also runs pfd_add_f16 (elementwise.hip), the launch the scaled add stands in for
             preprocess("elementwise", out)
+        if name == "guidance" and "emu_step" not in [os.path.basename(e) for e, _, _ in procs]:
+            # its driver also runs pfd_cfg_step_mul (step.hip); emu_step's compile, if it runs, is reading that file already
+            preprocess("step", out)
         exe = os.path.join(out, driver)
         cmd = [CXX, "-std=c++17", os.environ.get("EMU_OPT", "-O0"), "-pthread", "-w", f"-I{HERE}", f"-I{out}", f"-I{REPO}/include", f"-I{CSRC}",
                os.path.join(HERE, driver + ".cpp"), "-o", exe] + os.environ.get("EMU_DEFINES", "").split()
