@@ -554,7 +554,8 @@ int pfd_mask_grid_u8(const void* mask, int32_t Bm, int32_t Hm, int32_t Wm, void*
  * C > 4 is PFD_ESHAPE. */
 int pfd_composite_u8(const void* decoded, const void* init, int32_t Bi, const void* sel, int32_t Bs, void* out, int32_t n,
                      int32_t H, int32_t W, int32_t C, pfd_stream_t stream);
-/* y = a + b (f16, fp32 add), n elements; b may be NULL (copy). */
+/* y = a + b (f16, fp32 add), n elements; b may be NULL (copy).  y may be a or b (in place, element for element).
+ * NULL a / y or n <= 0 is PFD_EINVAL, so is a pointer that is not 16-byte aligned. */
 int pfd_add_f16(const void* a, const void* b, void* y, int64_t n, pfd_stream_t stream);
 /* ControlNet strength (added under ABI 10): y[b, e] = (f16) fmaf(scale[b * scale_stride], (float) r[b, e], (float) x[b, e])
  * on dense f16 [B, n_per_sample] -- the add of a ControlNet residual r into the UNet's activation x with one fp32
@@ -568,17 +569,22 @@ int pfd_add_scaled_rows_f16(const void* x, const void* r, const float* scale, in
                             int64_t n_per_sample, pfd_stream_t stream);
 /* y = alpha*a + beta*b (f16 storage, fp32 math), n elements; b may be NULL (y = alpha*a).  The
  * ratio-weighted sum of the per-context SpatialTransformer outputs of multi-context sampling
- * (pfd.py:375-380 `h = h + module(x, emb, c) * r`). */
+ * (pfd.py:375-380 `h = h + module(x, emb, c) * r`).  y may be a or b (in place, element for element).  NULL a / y or
+ * n <= 0 is PFD_EINVAL, so is a pointer that is not 16-byte aligned. */
 int pfd_axpby_f16(const void* a, float alpha, const void* b, float beta, void* y, int64_t n,
                   pfd_stream_t stream);
 /* y[r, c] = x[r, c] + v[c] for a [R, C] f16 matrix (level/positional embeddings,
- * seecoder.py:402,515). */
+ * seecoder.py:402,515).  y may be x (in place: the same rows, ldy == ldx); v must not overlap y.  NULL pointers, R <= 0,
+ * C <= 0, C % 8 != 0, ldx % 8 != 0, ldy % 8 != 0 or a pointer x / v / y that is not 16-byte aligned is PFD_EINVAL. */
 int pfd_add_rowvec_f16(const void* x, int64_t ldx, const void* v, void* y, int64_t ldy, int32_t R,
                        int32_t C, pfd_stream_t stream);
 
 /* The same with the partial row sums of y in the layout PfdGemmDesc.ln_stats takes (f32 [R][C / 160][2]; C % 160 == 0,
  * C <= 1280), in the summation order of pfd_ln_rowstats_f16 / the statistics-emitting GEMM epilogue: the `x + to_out.bias`
- * rows of the zero-context cross-attention shortcut feed the next folded LayerNorm without another pass. */
+ * rows of the zero-context cross-attention shortcut feed the next folded LayerNorm without another pass.  y may be x (in
+ * place: the same rows, ldy == ldx); v and stats must not overlap y.  NULL pointers, R <= 0, C <= 0, ldx % 8 != 0,
+ * ldy % 8 != 0, x / v / y not 16-byte aligned or stats not 8-byte aligned is PFD_EINVAL; C % 160 != 0 or C > 1280 is
+ * PFD_ESHAPE. */
 int pfd_add_rowvec_lnstats_f16(const void* x, int64_t ldx, const void* v, void* y, int64_t ldy, int32_t R, int32_t C,
                                void* stats, pfd_stream_t stream);
 
@@ -587,7 +593,11 @@ int pfd_add_rowvec_lnstats_f16(const void* x, int64_t ldx, const void* v, void* 
  * AutoencoderKL.decode's (x+1)/2 + clamp (autokl.py:47,53) followed by torchvision's ToPILImage, i.e.
  * `pic.mul(255).byte()` (app.py:273-275).  f16_image != 0: the image tensor is fp16 (fp16 model, app.py
  * default): v and the product v*255 are each rounded to f16 first, as on that tensor; 0: fp32 image.
- * The request front-end hands the bytes to the client without a float image ever leaving the device. */
+ * The request front-end hands the bytes to the client without a float image ever leaving the device.
+ * x must be 16-byte aligned and y 8-byte aligned (any n: the last n % 8 values are converted one by one); NULL x / y,
+ * n <= 0 or a misaligned pointer is PFD_EINVAL.  The bit-for-bit promise covers every input that is not a NaN, the
+ * infinities included, for (mul, add) whose product x * mul is exact ((0.5, 0.5), (1, 0)); the byte a NaN input gives is
+ * unspecified (the reference's `.byte()` of a NaN is undefined), only that the launch completes and is deterministic. */
 int pfd_image_u8_f16(const void* x, void* y, int64_t n, float mul, float add, int32_t f16_image,
                      pfd_stream_t stream);
 
@@ -663,7 +673,12 @@ int pfd_canny_u8(const void* src, int32_t B, int32_t H, int32_t W, int32_t C, in
 
 /* y = act(x) elementwise (act in NONE|GELU|RELU|SILU), n f16 elements.  The SiLU in front
  * of every ResBlock emb_layers Linear (openaimodel.py:217-218) applied once to the shared
- * time embedding, and nonlinearity() on its own (autokl_modules.py:33-35). */
+ * time embedding, and nonlinearity() on its own (autokl_modules.py:33-35).  y may be x (in place).
+ * Accuracy, per element against the exact function of the f16 input, hu = half an f16 ulp of the result (the one rounding
+ * of the store): NONE returns the input's bits; RELU the input's bits or +0 (-0 may give either zero); SILU is within
+ * hu + 2^-20 |result|; GELU (exact-erf form) within hu + 5e-7 -- held on all 63 488 finite f16 inputs by
+ * tests/test_boundary_kernels_gpu.py.  +-inf give what IEEE arithmetic gives (gelu / silu of -inf are NaN, as in torch).
+ * NULL pointers, n <= 0, an act outside the four or a pointer that is not 16-byte aligned is PFD_EINVAL. */
 int pfd_act_f16(const void* x, void* y, int64_t n, int32_t act, pfd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------

@@ -113,8 +113,8 @@ __global__ void philox_normal_kernel(const int64_t* __restrict__ key, int step, 
   }
 }
 
-__global__ void add_kernel(const half_t* __restrict__ a, const half_t* __restrict__ b, half_t* __restrict__ y,
-                           long n) {
+// (no __restrict__ on the pointers pfd_hip.h allows to alias: y may be a or b here, x below)
+__global__ void add_kernel(const half_t* a, const half_t* b, half_t* y, long n) {
   const long nv = n / 8;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
     Pack16 p, q, o;
@@ -134,8 +134,7 @@ __global__ void add_kernel(const half_t* __restrict__ a, const half_t* __restric
   }
 }
 
-__global__ void axpby_kernel(const half_t* __restrict__ a, float alpha, const half_t* __restrict__ b, float beta,
-                             half_t* __restrict__ y, long n) {
+__global__ void axpby_kernel(const half_t* a, float alpha, const half_t* b, float beta, half_t* y, long n) {
   const long nv = n / 8;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
     Pack16 p, q, o;
@@ -152,8 +151,8 @@ __global__ void axpby_kernel(const half_t* __restrict__ a, float alpha, const ha
   }
 }
 
-__global__ void add_rowvec_kernel(const half_t* __restrict__ x, long ldx, const half_t* __restrict__ v,
-                                  half_t* __restrict__ y, long ldy, int R, int C) {
+__global__ void add_rowvec_kernel(const half_t* x, long ldx, const half_t* __restrict__ v, half_t* y, long ldy, int R,
+                                  int C) {
   const int nvec = C / 8;
   const long n = (long)R * nvec;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -167,7 +166,7 @@ __global__ void add_rowvec_kernel(const half_t* __restrict__ x, long ldx, const 
   }
 }
 
-__global__ void act_kernel(const half_t* __restrict__ x, half_t* __restrict__ y, long n, int act) {
+__global__ void act_kernel(const half_t* x, half_t* y, long n, int act) {
   const long nv = n / 8;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
     Pack16 p, o;
@@ -312,9 +311,9 @@ extern "C" int pfd_axpby_f16(const void* a, float alpha, const void* b, float be
 // (row, 160-column slice), lane k takes chunks k, k + 4, ..., k + 16 -- the summation order of ln_rowstats_kernel
 // (norm.hip) and of the statistics-emitting GEMM epilogue, so the `x + bias` rows of the zero-context shortcut carry
 // bit-for-bit the statistics the full out-projection would have written.
-__global__ __launch_bounds__(256) void add_rowvec_lnstats_kernel(const half_t* __restrict__ x, long ldx,
-                                                                 const half_t* __restrict__ v, half_t* __restrict__ y,
-                                                                 long ldy, int R, int P, float2* __restrict__ st) {
+__global__ __launch_bounds__(256) void add_rowvec_lnstats_kernel(const half_t* x, long ldx, const half_t* __restrict__ v,
+                                                                 half_t* y, long ldy, int R, int P,
+                                                                 float2* __restrict__ st) {
   const long grp = ((long)blockIdx.x * 256 + threadIdx.x) >> 2;
   const int k = threadIdx.x & 3;
   const long ngrp = (long)R * P;
@@ -368,6 +367,8 @@ extern "C" int pfd_add_rowvec_f16(const void* x, int64_t ldx, const void* v, voi
                                   int32_t C, pfd_stream_t stream) {
   if (!x || !v || !y || R <= 0 || C <= 0) return PFD_EINVAL;
   if ((C & 7) || (ldx & 7) || (ldy & 7)) return PFD_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(v) & 15) || (reinterpret_cast<uintptr_t>(y) & 15))
+    return PFD_EINVAL;
   const long n = (long)R * (C / 8);
   PfdProfScope prof_scope(15, 0.0, 0.0, (hipStream_t)stream);
   hipLaunchKernelGGL(add_rowvec_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,

@@ -1237,15 +1237,27 @@ def composite_u8(decoded, init, sel):
     return out
 
 
+def _chk_dense_out(out, n, what):
+    """a caller's `out` of a dense element-wise launch: float16, on the device, dense, n elements (it may be an input)"""
+    _chk16(out, what)
+    if not out.is_contiguous():
+        raise ValueError(f"{what}: dense tensor expected")
+    if out.numel() != n:
+        raise ValueError(f"{what}: {out.numel()} elements for a result of {n}")
+
+
 def add(a, b, out=None):
+    """out = a + b; out may be a or b"""
     _chk16(a, "add a")
     _chk16(b, "add b")
     if not (a.is_contiguous() and b.is_contiguous()):
         raise ValueError("add: dense tensors expected")
-    if a.numel() != b.numel() or (out is not None and out.numel() != a.numel()):
+    if a.numel() != b.numel():
         raise ValueError(f"add: operand sizes differ ({tuple(a.shape)} vs {tuple(b.shape)}); no broadcasting")
     if out is None:
         out = torch.empty_like(a)
+    else:
+        _chk_dense_out(out, a.numel(), "add out")
     _b.check(_lib().pfd_add_f16(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), _stream()), "pfd_add_f16")
     return _written(out)
 
@@ -1277,14 +1289,18 @@ def add_scaled_rows(x, r, scale, out=None):
 
 
 def axpby(a, alpha, b=None, beta=0.0, out=None):
-    """out = alpha*a + beta*b (b optional)"""
+    """out = alpha*a + beta*b (b optional); out may be a or b"""
     _chk16(a, "axpby a")
+    if b is not None:
+        _chk16(b, "axpby b")
     if not a.is_contiguous() or (b is not None and not b.is_contiguous()):
         raise ValueError("axpby: dense tensors expected")
-    if (b is not None and b.numel() != a.numel()) or (out is not None and out.numel() != a.numel()):
+    if b is not None and b.numel() != a.numel():
         raise ValueError("axpby: operand sizes differ; no broadcasting")
     if out is None:
         out = torch.empty_like(a)
+    else:
+        _chk_dense_out(out, a.numel(), "axpby out")
     _b.check(_lib().pfd_axpby_f16(a.data_ptr(), float(alpha), _ptr(b), float(beta), out.data_ptr(), a.numel(),
                                   _stream()), "pfd_axpby_f16")
     return _written(out)
@@ -1292,11 +1308,18 @@ def axpby(a, alpha, b=None, beta=0.0, out=None):
 
 def add_rowvec(x, v, out=None, ln_out=None):
     """out = x + v[None, :]; ln_out: a float32 [R, C/160, 2] tensor that receives the partial row sums of `out` in the
-    same launch (the layout gemm(ln=...) takes)"""
+    same launch (the layout gemm(ln=...) takes).  x and out: strided [R, C] matrices (out may be x); v: dense [C]"""
     _chk16(x, "add_rowvec x")
     R, Cc, ldx = _rows(x)
+    _chk16(v, "add_rowvec v")
+    if v.numel() != Cc or not v.is_contiguous():
+        raise ValueError(f"add_rowvec: v of shape {tuple(v.shape)} strides {v.stride()} is not a dense vector of {Cc} elements")
     if out is None:
         out = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+    else:
+        _chk16(out, "add_rowvec out")
+        if _rows(out)[:2] != (R, Cc):
+            raise ValueError(f"add_rowvec: out of shape {tuple(out.shape)} for a [{R}, {Cc}] result")
     if ln_out is not None:
         ln_out = _row_stats("add_rowvec: ln_out", "R, C/160, 2", R, Cc, x.device, ln_out)
         _b.check(_lib().pfd_add_rowvec_lnstats_f16(x.data_ptr(), ldx, v.data_ptr(), out.data_ptr(), _rows(out)[2], R, Cc,
@@ -1308,10 +1331,13 @@ def add_rowvec(x, v, out=None, ln_out=None):
 
 
 def activation(x, act, out=None):
+    """out = act(x); out may be x"""
     _chk16(x, "activation x")
     if not x.is_contiguous():
         raise ValueError("activation: dense tensor expected")
     if out is None:
         out = torch.empty_like(x)
+    else:
+        _chk_dense_out(out, x.numel(), "activation out")
     _b.check(_lib().pfd_act_f16(x.data_ptr(), out.data_ptr(), x.numel(), act, _stream()), "pfd_act_f16")
     return _written(out)

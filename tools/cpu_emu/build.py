@@ -1,10 +1,10 @@
 #!/usr/bin/env python
-"""Build the CPU emulation of csrc/gemm_glds.hip, csrc/norm.hip, csrc/attention.hip, csrc/image.hip, csrc/canny.hip, csrc/latent.hip, csrc/inpaint.hip, csrc/step.hip, csrc/control.hip and csrc/guidance.hip (tools/cpu_emu/emu_*.cpp): write
+"""Build the CPU emulation of csrc/gemm_glds.hip, csrc/norm.hip, csrc/attention.hip, csrc/image.hip, csrc/canny.hip, csrc/latent.hip, csrc/inpaint.hip, csrc/step.hip, csrc/control.hip, csrc/guidance.hip and csrc/elementwise.hip (tools/cpu_emu/emu_*.cpp): write
 <file>_emu.inc = the kernel file with its gfx950 inline-asm statements replaced by their C meaning, then compile the
 drivers for the host with clang++.
 (emu_attn drives pfd_attention_f16 and, with --kbias, pfd_attention_kbias_f16: the LDS-DMA load of the key logits is the shim's
 __builtin_amdgcn_global_load_lds, the opaque register pins of its KBIAS builds fall under the first substitution below.)
-usage: [EMU_DEFINES="-DPFD_FAST_PROLOGUE ..."] build.py [outdir]   (default /tmp/pfd_cpu_emu)  -> <outdir>/emu_gemm, <outdir>/emu_norm, <outdir>/emu_attn, <outdir>/emu_image, <outdir>/emu_canny, <outdir>/emu_latent, <outdir>/emu_inpaint, <outdir>/emu_step, <outdir>/emu_control, <outdir>/emu_guidance"""
+usage: [EMU_DEFINES="-DPFD_FAST_PROLOGUE ..."] build.py [outdir]   (default /tmp/pfd_cpu_emu)  -> <outdir>/emu_gemm, <outdir>/emu_norm, <outdir>/emu_attn, <outdir>/emu_image, <outdir>/emu_canny, <outdir>/emu_latent, <outdir>/emu_inpaint, <outdir>/emu_step, <outdir>/emu_control, <outdir>/emu_guidance, <outdir>/emu_elementwise"""
 import os
 import re
 import subprocess
@@ -50,13 +50,15 @@ def main():
     only = os.environ.get("EMU_ONLY", "").split()     # e.g. EMU_ONLY=emu_gemm: just that driver
     for name, driver in (("gemm_glds", "emu_gemm"), ("norm", "emu_norm"), ("attention", "emu_attn"), ("image", "emu_image"),
                          ("canny", "emu_canny"), ("latent", "emu_latent"), ("inpaint", "emu_inpaint"), ("step", "emu_step"),
-                         ("control", "emu_control"), ("guidance", "emu_guidance")):
+                         ("elementwise", "emu_elementwise"), ("control", "emu_control"), ("guidance", "emu_guidance")):
         if only and driver not in only:
             continue
         preprocess(name, out)
         if name == "attention":     # the kernel text attention.hip includes twice (with and without the key logits), under its own name
             preprocess("attention2_kernel", out, ext=".inc", outname="attention2_kernel.inc")
-        if name == "control":       # its driver also runs pfd_add_f16 (elementwise.hip), the launch the scaled add stands in for
+        if name == "control" and "emu_elementwise" not in [os.path.basename(e) for e, _, _ in procs]:
+            # its driver also runs pfd_add_f16 (elementwise.hip), the launch the scaled add stands in for; emu_elementwise's
+            # compile, if it runs, is reading that file already
             preprocess("elementwise", out)
         if name == "guidance" and "emu_step" not in [os.path.basename(e) for e, _, _ in procs]:
             # its driver also runs pfd_cfg_step_mul (step.hip); emu_step's compile, if it runs, is reading that file already
