@@ -75,7 +75,10 @@ const char* pfd_last_error(void);
  *                Rounding: the contraction and the activation are fp32.  Without a residual the result is rounded to f16
  *                once.  With one, the wide-tile kernels stage act(...) as f16 (the LDS image of the output tile) and their
  *                store pass adds R in fp32 and rounds again: two roundings, at most 2^-11 |act(...)| more than one.  The
- *                register-staged kernel and the split-K reductions add R in fp32 and round once.
+ *                register-staged kernel and the split-K reductions add R in fp32 and round once.  The staged act(...)
+ *                overflows like an f16 result BEFORE R is added: where |act(...)| > 65504 the unsplit wide-tile kernels
+ *                (only they) store +-inf even if act(...) + R is an ordinary f16 value, which the register-staged kernel
+ *                and a split launch of the same operands store.
  *
  * Replaces: nn.Linear / 1x1 nn.Conv2d everywhere on the path (attention.py:169-176,
  * 47-51, 60-67, 329-347; swin.py:88-90,171-173,322; seecoder.py:74-77,216-218,358;
@@ -117,7 +120,12 @@ typedef struct PfdGemmDesc {
    * keeps in it is private: since round 6 the K-range partial sums are stored rounded to f16 and summed in fp32, in
    * slab order, by the reduction launch (deterministic; the same freedom the reference's default
    * torch.backends.cuda.matmul.allow_fp16_reduced_precision_reduction = True gives its own split-K GEMMs); a
-   * partial sum beyond +-65504 becomes +-inf exactly as an f16 result of that magnitude would. */
+   * partial sum beyond +-65504 becomes +-inf exactly as an f16 result of that magnitude would, and the sum goes on in IEEE
+   * arithmetic: +inf and -inf slabs give NaN, relu (fmaxf) of -inf or NaN is 0, silu / gelu of -inf are NaN.  One exception: the
+   * reductions read the slabs four at a time and fill a last group up with copies of the LAST slab weighted by 0, so with a
+   * slab count that is no multiple of four an element whose last slab is +-inf is NaN (inf * 0), whatever the other slabs hold.
+   * The unsplit launch of the same operands is finite wherever its own result is (tests/test_gemm_range_gpu.py holds all of
+   * this; profiles/gemm_kernel_tests.md, "Operand kinds", has the sizes). */
   void* ws;
   size_t ws_bytes;
   /* optional transposed tail (ABI 3): with Ct != NULL the output columns n >= n_split are not

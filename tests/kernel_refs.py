@@ -1,10 +1,11 @@
 """Plain fp64 references of single kernels of the library, and the seeded operands the kernel-level tests run them on: the
 SeeCoder side (tests/test_encoder_kernels_cpu.py pins the references to the oracle, tests/test_encoder_kernels_gpu.py
 compares the HIP kernels with them), the fused attention family (tests/test_attention_kernels_{cpu,gpu}.py), the GEMM /
-convolution kernels (tests/test_gemm_kernels_{cpu,gpu}.py) and the stand-alone GroupNorm kernels
+convolution kernels (tests/test_gemm_kernels_{cpu,gpu}.py, tests/test_gemm_range_{cpu,gpu}.py) and the stand-alone GroupNorm kernels
 (tests/test_norm_kernels_{cpu,gpu}.py, the last section).  Everything here is torch on whatever device the operands live on; nothing imports the
 native library.  A plain module, not a conftest: the two test files import it by name."""
 import functools
+import math
 import re
 import zlib
 
@@ -486,6 +487,9 @@ GEMM_MUTANTS = ("last_k_dropped", "pad_tap_reads_edge", "pad_before_normalise", 
                 "residual_no_wrap", "residual_wrap_off_by_one", "zero_rows_rounded_to_tile", "bias_after_act",
                 "geglu_halves_swapped", "ups_gather_ceil", "k_split_second_source_offset", "ln_mean_of_first_part",
                 "tail_transposed_without_bias")
+# wrong variants of the documented ARITHMETIC (not of the formula): they act on gemm_ref(..., slabs=, staged=), the model of what
+# include/pfd_hip.h says a launch computes, and are qualified by tests/test_gemm_range_cpu.py
+GEMM_ARITH_MUTANTS = ("slab_round_toward_zero", "slab_saturates", "residual_added_before_staging")
 GEMM_CLASSES = ("lin160", "lin128", "geglu", "reg", "abi", "conv", "patch", "narrow")
 # the Lipschitz constants of the activations: max |gelu'| = 1.1290 (at x = 1.4142...), max |silu'| = 1.0998 (at x = 2.3994)
 _ACT_LIP = {ACT_NONE: 1.0, ACT_GELU: 1.13, ACT_RELU: 1.0, ACT_SILU: 1.10, ACT_GEGLU: 1.13}
@@ -546,6 +550,36 @@ def gemm_slab_ranges(nk, splits):
     kt = ceil(nk / splits); slabs that would start at or beyond nk do not exist (real_splits < splits)"""
     kt = -(-nk // splits)
     return [(s * kt, min(nk, (s + 1) * kt)) for s in range(-(-nk // kt))]
+
+
+def gemm_slab_columns(c, splits):
+    """the K indices of every slab of a launch with `splits` slabs requested: K-tile ranges (gemm_slab_ranges), for the patch
+    kernels the 64-channel blocks over all nine taps"""
+    if c["cls"] == "patch":
+        Cin = c["K"] // 9
+        return [torch.cat([torch.arange(t * Cin + lo * 64, t * Cin + hi * 64) for t in range(9)])
+                for lo, hi in gemm_slab_ranges(Cin // 64, splits)]
+    return [torch.arange(lo * 64, hi * 64) for lo, hi in gemm_slab_ranges(c["K"] // 64, splits)]
+
+
+F16_MAX, F16_OVERFLOW = 65504.0, 65520.0       # the largest f16; the smallest magnitude that rounds to inf (half an ulp above it)
+
+
+def _slab_sum(X, W, slabs, mutant):
+    """include/pfd_hip.h, PfdGemmDesc.ws: "the K-range partial sums are stored rounded to f16 and summed in fp32, in slab
+    order ... a partial sum beyond +-65504 becomes +-inf" -- sum_s f16(P_s) in X's dtype"""
+    tot = None
+    for i in slabs:
+        P = X[:, i] @ W[:, i].t()
+        h = P.half()
+        if mutant == "slab_round_toward_zero":
+            h = torch.where(h.to(P.dtype).abs() > P.abs(), torch.nextafter(h, torch.zeros_like(h)), h)
+        elif mutant == "slab_saturates":
+            h = P.clamp(-F16_MAX, F16_MAX).half()
+        tot = h.to(X.dtype) if tot is None else tot + h.to(X.dtype)
+    if len(slabs) % 4:                  # the reductions read four slabs at a time; a last group is filled up with copies of the
+        tot = tot + h.to(X.dtype) * 0.0     # LAST slab weighted by 0: nothing, unless that slab is +-inf (inf * 0 = NaN)
+    return tot
 
 
 def ln_out_ref(stored):
@@ -616,14 +650,17 @@ def _gemm_operand(p, mutant, dtype, want_abs=False):
     return X, E
 
 
-def gemm_ref(p, mutant=None, dtype=torch.float64, parts=False):
+def gemm_ref(p, mutant=None, dtype=torch.float64, parts=False, slabs=None, staged=False, maxnum_relu=False):
     """one formula, from the header text of PfdGemmDesc, on the fp16 operands of gemm_problem(case), on their device:
         C[m, n] = act(sum_k X[m, k] W[n, k] + bias[n or m] + rowvec[m / rows_per_rv, n]) + R[m (- res_rows), n]
     X the linear operand ([A | A2] with k_split, zero rows in front with zero_rows), the implicit-convolution gather or the
     GroupNorm-prologue image; GEGLU x * gelu(gate) of the two logical halves; the LayerNorm fold as ((x - mean) rstd) W'^T + b'
     with the statistics of x in `dtype`; columns >= n_split transposed (+ bias only).  Returns dict(out=[M, N_out]) plus out_t
-    ([N - n_split, M]) with a transposed tail; parts=True adds what gemm_allowance needs.  mutant: one of GEMM_MUTANTS."""
-    assert mutant is None or mutant in GEMM_MUTANTS
+    ([N - n_split, M]) with a transposed tail; parts=True adds what gemm_allowance needs.  mutant: one of GEMM_MUTANTS.
+    slabs / staged turn the formula into the ARITHMETIC the header documents (gemm_kernel_model): slabs = the K index sets whose
+    partial sums pass through f16 (of the raw x W'^T under the LayerNorm fold), staged = act(...) rounded to f16 in front of R;
+    mutant may then be one of GEMM_ARITH_MUTANTS."""
+    assert mutant is None or mutant in GEMM_MUTANTS or ((slabs is not None or staged) and mutant in GEMM_ARITH_MUTANTS)
     c = p["case"]
     M, N, act = c["M"], c["N"], c["act"]
     X, _ = _gemm_operand(p, mutant, dtype)
@@ -632,8 +669,13 @@ def gemm_ref(p, mutant=None, dtype=torch.float64, parts=False):
         xs = X[:, :160] if mutant == "ln_mean_of_first_part" else X
         mean = xs.mean(1, keepdim=True)
         rstd = 1.0 / torch.sqrt((xs * xs).mean(1, keepdim=True) - mean * mean + c["ln_eps"])
-        X = (X - mean) * rstd
-    acc = X @ W.t()
+        if slabs is None:
+            X = (X - mean) * rstd
+            acc = X @ W.t()
+        else:
+            acc = rstd * (_slab_sum(X, W, slabs, mutant) - mean * W.sum(1)[None])
+    else:
+        acc = X @ W.t() if slabs is None else _slab_sum(X, W, slabs, mutant)
     m = torch.arange(M, device=acc.device)
     bias = None if p["bias"] is None else (p["bias"].to(dtype)[:, None] if c["bias_per_row"] else p["bias"].to(dtype)[None, :])
     rv = None
@@ -652,10 +694,14 @@ def gemm_ref(p, mutant=None, dtype=torch.float64, parts=False):
         post = px * F.gelu(pg)
     else:
         post = activation_ref(pre, act, dtype)
+        if maxnum_relu and act == ACT_RELU:                                # fmaxf(v, 0): a NaN gives 0 (torch.relu keeps it)
+            post = torch.fmax(pre, torch.zeros_like(pre))
     if bias is not None and mutant == "bias_after_act":
         post = post + (bias[:, :N // 2] if act == ACT_GEGLU else bias)
     out = post
     if p["R"] is not None:
+        if staged and mutant != "residual_added_before_staging":
+            post = post.half().to(dtype)
         r = p["R"].to(dtype)
         rr = c["res_rows"]
         if rr and rr != M:
@@ -743,12 +789,7 @@ def gemm_allowance(p, splits=1, wide=True):
         S_b = S_b + p["rowvec"].double().abs()[torch.arange(M) // c["rows_per_rv"]]
     a_pre = a_acc + ACC_C * K * _U * S_b + extra
     if splits > 1:
-        if c["cls"] == "patch":
-            Cin = c["K"] // 9
-            cols = lambda lo, hi: torch.cat([torch.arange(t * Cin + lo * 64, t * Cin + hi * 64) for t in range(9)])
-            rng = [cols(lo, hi) for lo, hi in gemm_slab_ranges(Cin // 64, splits)]
-        else:
-            rng = [torch.arange(lo * 64, hi * 64) for lo, hi in gemm_slab_ranges(K // 64, splits)]
+        rng = gemm_slab_columns(c, splits)
         # (the slabs hold partial sums of x W'^T: the LayerNorm fold is applied behind the reduction, which scales them by rstd)
         a_pre = a_pre + sum(2.0 ** -11 * (Xraw[:, i] @ W[:, i].t()).abs() for i in rng) * rstd
     res = {}
@@ -769,6 +810,79 @@ def gemm_allowance(p, splits=1, wide=True):
     if wide and splits == 1 and p["R"] is not None:
         a = a + 2.0 ** -11 * (r["post"].abs() + a)                        # the staged value (see above)
     res["out"] = a[:, :ns] if ns else a
+    return res
+
+
+def gemm_kernel_model(p, splits=1, wide=True, mutant=None, dtype=torch.float32):
+    """the ARITHMETIC include/pfd_hip.h documents for a launch with `splits` slabs, evaluated by torch in fp32 on the CPU and
+    rounded to f16: epi(sum_s f16(P_s)) with per-range fp32 contractions, the slabs summed in order, the epilogue in fp32, act(...)
+    staged as f16 in front of a residual on the unsplit wide-tile kernels.  IEEE all the way: a slab beyond +-65504 is +-inf,
+    inf - inf NaN, silu / gelu of -inf NaN, and a last slab of +-inf gives NaN whenever the slab count is no multiple of four (the
+    zero-weighted copies of _slab_sum; FINDING of the range tests, stated in the header now).  RELU is fmaxf(v, 0) -- IEEE maxNum, the instruction the kernels use: relu(-inf) = 0
+    and relu(NaN) = 0, where torch.relu keeps the NaN.  mutant: one of GEMM_ARITH_MUTANTS."""
+    c = p["case"]
+    r = gemm_ref(p, mutant=mutant, dtype=dtype, slabs=gemm_slab_columns(c, splits) if splits > 1 else None,
+                 staged=wide and splits == 1, maxnum_relu=True)
+    return {k: r[k].half() for k in ("out", "out_t") if k in r}
+
+
+def gemm_slab_partials(p, splits):
+    """[(P_s, d_s)] in fp64 for every slab of a launch with `splits` slabs (one entry, the whole K, unsplit): the partial sum
+    of the raw operand and its own accumulation allowance ACC_C K_s u sum_k |x_k| |w_k| over the slab"""
+    c = p["case"]
+    X, _ = _gemm_operand(p, None, torch.float64)
+    W = p["W"].double()
+    cols = gemm_slab_columns(c, splits) if splits > 1 else [torch.arange(c["K"])]
+    return [(X[:, i] @ W[:, i].t(), ACC_C * len(i) * _U * (X[:, i].abs() @ W[:, i].abs().t())) for i in cols]
+
+
+def gemm_range_classes(p, splits, wide):
+    """per element of the main output, from the fp64 reference alone: 0 `finite` -- every quantity the header says passes
+    through f16 (the slab partials; act(...) on an unsplit wide-tile launch with a residual) lies below 65520 - d, d its own
+    accumulation allowance; 1 `nonfinite` -- some quantity lies beyond 65520 + d and none in between; 2 `band` -- otherwise (which
+    way such a quantity rounds is not determined by the reference: left out)"""
+    c = p["case"]
+    q = gemm_slab_partials(p, splits) if splits > 1 else []
+    if wide and splits == 1 and p["R"] is not None:
+        a = gemm_allowance(p, 1, False)["out"]
+        q.append((gemm_ref(p, parts=True)["post"], a))
+    cls = torch.zeros((c["M"], c["N"]), dtype=torch.int64)
+    for P, d in q:
+        cls = torch.maximum(cls, torch.where(P.abs() > F16_OVERFLOW + d, 1, torch.where(P.abs() < F16_OVERFLOW - d, 0, 2)))
+    n_out = c["n_split"] or (c["N"] // 2 if c["act"] == ACT_GEGLU else c["N"])
+    assert n_out == c["N"]
+    return cls
+
+
+def half_pipeline(p):
+    """the same operation the way the model this library ports computes it in fp16 (torch modules on f16 tensors): each GEMM
+    accumulates the WHOLE K in fp32 and rounds its result (+ bias) to f16 once, and every op around it -- LayerNorm / GroupNorm
+    in front, the row-vector add, the activation, the GEGLU product, the residual add -- is a separate op that reads f16 and
+    rounds to f16.  Not a bound on anything: the yardstick the f16-slab loss is recorded against."""
+    c = p["case"]
+    M, N, act = c["M"], c["N"], c["act"]
+    h = lambda t: t.half().float()
+    X, _ = _gemm_operand(p, None, torch.float32)
+    if c["ln"] is not None:
+        X = h(F.layer_norm(X, (c["K"],), None, None, c["ln_eps"]))
+    y = X @ p["W"].float().t()
+    if p["bias"] is not None:
+        y = y + (p["bias"].float()[:, None] if c["bias_per_row"] else p["bias"].float()[None])
+    y = h(y)
+    res = {}
+    if c["n_split"]:
+        res["out_t"] = y[:, c["n_split"]:].t().contiguous().half()
+    if p["rowvec"] is not None:
+        y = h(y + p["rowvec"].float()[torch.arange(M) // c["rows_per_rv"]])
+    if act == ACT_GEGLU:
+        y = h(y[:, :N // 2] * h(F.gelu(y[:, N // 2:])))
+    else:
+        y = h(activation_ref(y, act, torch.float32))
+    if p["R"] is not None:
+        r, rr = p["R"].float(), c["res_rows"]
+        m = torch.arange(M)
+        y = h(y + (r[torch.where(m >= rr, m - rr, m)] if rr and rr != M else r))
+    res["out"] = (y[:, :c["n_split"]] if c["n_split"] else y).half()
     return res
 
 
@@ -806,12 +920,15 @@ def wide_kernel_name(v, conv, nt):
 
 _GEMM_DEFAULTS = dict(kind="lin", act=ACT_NONE, bias=False, rowvec=False, rows_per_rv=1, res=False, bias_per_row=False, geom=None,
                       image=None, k_split=0, zero_rows=0, res_rows=0, n_split=0, ln=None, ln_eps=1e-5, ln_out=False, gn_out=False,
-                      w_tiled=False, gn_pro=None, gnf=None, splits=1, reduce=None, tile=0, base_kernel=None, ldc_pad=16)
+                      w_tiled=False, gn_pro=None, gnf=None, splits=1, reduce=None, tile=0, base_kernel=None, ldc_pad=16,
+                      operands="unit")
 EPI_NONE = dict()
 EPI_FULL = dict(bias=True, act=ACT_SILU, rowvec=True, rows_per_rv=100, res=True)
 EPI_GELU = dict(bias=True, act=ACT_GELU)
 EPI_RELU = dict(act=ACT_RELU)
-_EPI_NAMES = ((EPI_NONE, "plain"), (EPI_FULL, "silu-rv-res"), (EPI_GELU, "gelu"), (EPI_RELU, "relu"))
+EPI_RES = dict(res=True)
+EPI_RV_RES = dict(bias=True, rowvec=True, rows_per_rv=100, res=True)
+_EPI_NAMES = ((EPI_NONE, "plain"), (EPI_FULL, "silu-rv-res"), (EPI_GELU, "gelu"), (EPI_RELU, "relu"), (EPI_RES, "res"), (EPI_RV_RES, "rv-res"))
 
 
 def _epi_name(e):
@@ -956,11 +1073,83 @@ def _build_gemm_cases():
             geo, M, K, hw = _conv_geom(B, H, W, 64)
             cs.append(_mk(f"narrow-n{N}-{B}x{H}x{W}", "narrow", "conv3x3_narrow_kernel", M, N, K, bias=True, rows_per_rv=hw, **geo))
     assert len({c["id"] for c in cs}) == len(cs)
+    return cs + _operand_kind_cases({c["id"]: c for c in cs})
+
+
+def _kinded(c, kind):
+    """the same launch on other operands (field `operands`: the case field `kind` already says linear / convolution): the kind
+    is part of the id, hence of gemm_problem_key -- the variants and split counts of one problem still share their operands"""
+    return dict(c, id=f"{c['id']}-k{kind}", operands=kind)
+
+
+def _operand_kind_cases(base):
+    """the launches of the table that also run on trained magnitudes (`act`), on partial sums that cancel between the slabs of
+    split count S (`cancelS`) and on the same construction from small integers (`exactS`); see gemm_problem for the recipes.
+    Shapes, variants and split counts are those of the unit cases (the 24-integer records do not change with the kind)."""
+    H41 = "gemm160_kernel<4, 1, false, 2, 5>"
+    cs = []
+    lin = "300x320x320"
+    for s in (0, 2, 4, 8):
+        sp = f"-split{s}" if s else ""
+        for v, e in ((44, EPI_FULL), (41, EPI_NONE), (25, EPI_FULL), (0, EPI_GELU)):
+            b = base[f"lin160-v{v}{sp}-{lin}-{_epi_name(e)}"]
+            cs +=[_kinded(b, "act"), _kinded(b, "cancel2")]
+        for v, e in ((41, EPI_NONE), (44, EPI_RES), (0, EPI_RELU)):
+            b = base.get(f"lin160-v{v}{sp}-{lin}-{_epi_name(e)}") or \
+                _wide(f"lin160-v{v}{sp}-{lin}-{_epi_name(e)}", "lin160", v, s, 300, 320, 320, kernel=H41 if v == 0 else None, **e)
+            cs.append(_kinded(b, "exact2"))
+    for b in (_wide("lin128-v22-300x256x512-gelu", "lin128", 22, 0, 300, 256, 512, **EPI_GELU), base["lin128-v22-split2-300x256x512-gelu"]):
+        cs += [_kinded(b, "act"), _kinded(b, "cancel2")]
+    act_only = ["geglu-v84-300x640x320", "geglu-v44-300x640x320", "geglu-v0-300x640x320", "geglu-reg-300x256x320",
+                "reg-t22-301x200x192-silu-rv-res", "reg-t11-301x200x192-silu-rv-res", "reg-t11-301x200x192-silu-rv-res-ldc212",
+                "abi-ln640-v0-plain", "abi-ln640-split2", "abi-ln320-rowstats"]
+    act_only += [f"abi-{o}-128x{N}x320-split{s}" for N in (320, 640) for s in (0, 2) for o in ("ln_out", "gn_out")]
+    for g in ("s1p1-9x7", "s2p1-10x8"):      # 18 K tiles: v0 and v22 split four ways (5 + 5 + 5 + 3), v44 does not
+        for v in (0, 22, 44):
+            cs += [_kinded(base[f"conv-v{v}-c128-{g}"], "act"), _kinded(base[f"conv-v{v}-c128-{g}"], "cancel4")]
+    for v in (96, 0):
+        for img in ("2x16x16", "1x8x32"):
+            for sp in ("", "-split2"):
+                cs += [_kinded(base[f"patch-v{v}-c192-{img}{sp}"], "act"), _kinded(base[f"patch-v{v}-c192-{img}{sp}"], "cancel2")]
+    act_only += [f"patch-prologue-{a}{b}" for a in ("128", "64+64") for b in ("", "-silu")]
+    act_only += ["patch-gnf-raw-kept", "patch-gnf-raw-skipped", "narrow-n4-2x9x7"]
+    cs += [_kinded(base[i], "act") for i in act_only]
+    assert len({c["id"] for c in cs}) == len(cs)
+    return cs
+
+
+def _build_gemm_range_cases():
+    """beyond the f16 range (tests/test_gemm_range_cpu.py / _gpu.py; the runner of GEMM_CASES asserts finiteness, so these have
+    a table of their own): `overflowS` = the cancelS operands times 2 -- some slab partials leave the range while the result
+    stays O(1e3) -- split and, beside it, unsplit; `staged` = a large bias + row vector against a residual of the opposite
+    sign -- act(...) leaves the range, the result does not"""
+    cs = []
+    for e in (EPI_NONE, EPI_FULL, EPI_RELU):
+        cs.append(_wide(f"range-lin160-v41-split2-300x320x320-{_epi_name(e)}", "lin160", 41, 2, 300, 320, 320, **e))
+        cs.append(_wide(f"range-lin160-v44-300x320x320-{_epi_name(e)}", "lin160", 44, 0, 300, 320, 320, **e))
+    cs.append(_wide("range-gn_out-v24-split2-128x320x320", "abi", 24, 2, 128, 320, 320, gn_out=True, bias=True, res=True))
+    cs.append(_wide("range-gn_out-v44-128x320x320", "abi", 44, 0, 128, 320, 320, gn_out=True, bias=True, res=True))
+    conv_epi = dict(bias=True, act=ACT_SILU, rowvec=True, res=True)
+    geo, M, K, hw = _conv_geom(2, 16, 16, 192)
+    for v, s in ((96, 2), (96, 0)):
+        cs.append(_wide(f"range-patch-v{v}-c192-2x16x16" + (f"-split{s}" if s else ""), "patch", v, s, M, 160, K, conv=True, rows_per_rv=hw,
+                        **conv_epi, **geo))
+    cs = [_kinded(c, "overflow2") for c in cs]
+    geo, M, K, hw = _conv_geom(2, 9, 7, 128)
+    cs.append(_kinded(_wide("range-conv-v0-c128-s1p1-9x7", "conv", 0, 0, M, 160, K, conv=True, rows_per_rv=hw, hsplit=4,
+                            kernel="gemm160_kernel<4, 1, true, 2, 5>", **conv_epi, **geo), "overflow4"))
+    cs.append(_kinded(_wide("range-conv-v44-c128-s1p1-9x7", "conv", 44, 0, M, 160, K, conv=True, rows_per_rv=hw, **conv_epi, **geo), "overflow4"))
+    for v in (22, 41, 44, 83):
+        cs.append(_kinded(_wide(f"range-lin160-v{v}-300x320x320-rv-res", "lin160", v, 0, 300, 320, 320, **EPI_RV_RES), "staged"))
+    cs.append(_kinded(_wide("range-lin160-v41-split2-300x320x320-rv-res", "lin160", 41, 2, 300, 320, 320, **EPI_RV_RES), "staged"))
+    cs.append(_kinded(_mk("range-reg-t22-301x200x192-rv-res", "reg", "gemm_conv_kernel<2, 2, false>", 301, 200, 192, tile=22, **EPI_RV_RES), "staged"))
+    assert len({c["id"] for c in cs}) == len(cs)
     return cs
 
 
 GEMM_CASES = _build_gemm_cases()
-GEMM_CASE = {c["id"]: c for c in GEMM_CASES}
+GEMM_RANGE_CASES = _build_gemm_range_cases()
+GEMM_CASE = {c["id"]: c for c in GEMM_CASES + GEMM_RANGE_CASES}
 
 
 def gemm_case_record(c):
@@ -973,21 +1162,13 @@ def gemm_case_record(c):
             ups, B, H, W, Cin, Ho, Wo, c["rows_per_rv"], c["k_split"], c["zero_rows"], int(c["gn_out"]), gnf, c["res_rows"])
 
 
-@functools.lru_cache(maxsize=None)
-def gemm_problem(cid):
-    """the seeded fp16 operands of one case (CPU): unit Gaussians against K^-0.5 weights, logical tensors only (gemm_operands
-    puts them into the poisoned buffers a launch sees).  Do not modify the result."""
-    c = GEMM_CASE[cid]
-    M, N, K = c["M"], c["N"], c["K"]
-    # (seeded from the id without its variant / split part: the cases of one problem share their operands, so the GPU file can
-    #  hold a forced variant against the heuristic and a split launch against the unsplit one)
-    g = torch.Generator().manual_seed(zlib.crc32(gemm_problem_key(cid).encode()))
-    rn = lambda *s: torch.randn(s, generator=g)
-    p = dict(case=c, A2=None, bias=None, rowvec=None, R=None, gn_table=None)
+def _put_input(p, x, rn):
+    """the input x (image [B, H, W, Cin] or rows [M - zero_rows, K], fp32) as the fp16 A / A2 of the case; with a GroupNorm
+    prologue also its table and how far the fp32 evaluation of the prologue can be off"""
+    c = p["case"]
     if c["kind"] == "conv":
         B, H, W, Cin = c["image"]
         c1 = c["gn_pro"][0] if c["gn_pro"] is not None else Cin
-        x = rn(B, H, W, Cin) + (0.5 if c["gn_pro"] is not None else 0.0)
         p["A"] = x[..., :c1].half()
         if c1 < Cin:
             p["A2"] = x[..., c1:].half()
@@ -1005,12 +1186,152 @@ def gemm_problem(cid):
             v32 = activation_ref(xx.float() * tab[:, None, None, 0] + tab[:, None, None, 1], act, torch.float32)
             p["pro_delta"] = fp32_allowance(v64, v32)
     else:
-        zr = c["zero_rows"]
-        x = rn(M - zr, K) + (0.5 if c["ln"] is not None else 0.0) + (4.0 if c["ln"] == "shifted" else 0.0)
-        ks_ = c["k_split"] or K
+        ks_ = c["k_split"] or c["K"]
         p["A"] = x[:, :ks_].half()
         if c["k_split"]:
             p["A2"] = x[:, ks_:].half()
+
+
+def gemm_operand_kind(c):
+    """the case's `operands` as (family, S): ("cancel", 2) for cancel2, ("act", 0), ("unit", 0), ..."""
+    m = re.fullmatch(r"([a-z]+?)(\d*)", c["operands"])
+    return m.group(1), int(m.group(2) or 0)
+
+
+def _gemm_problem_of_kind(p, g):
+    """the operands of a case whose `operands` is not `unit` (the recipes: gemm_problem)"""
+    c = p["case"]
+    M, N, K = c["M"], c["N"], c["K"]
+    fam, S = gemm_operand_kind(c)
+    rn = lambda *s: torch.randn(s, generator=g)
+    ri = lambda lo, hi, *s: torch.randint(lo, hi + 1, s, generator=g).float()
+    ru = lambda lo, hi, n: torch.exp(torch.empty(n).uniform_(math.log(lo), math.log(hi), generator=g))
+    conv, geglu = c["kind"] == "conv", c["act"] == ACT_GEGLU
+    Cin = c["image"][3] if conv else K
+    shape = tuple(c["image"][:3]) if conv else (M - c["zero_rows"],)
+    n_out = N // 2 if geglu else N
+    groups = -(-M // c["rows_per_rv"])
+
+    def outliers(n):                    # two of every 64 (of a ragged last block too): its last and a random other one
+        idx = []
+        for b0 in range(0, n, 64):
+            w = min(64, n - b0)
+            idx += [b0 + w - 1, b0 + int(torch.randint(0, w - 1, (1,), generator=g))]
+        return torch.tensor(idx)
+
+    eb, er = 0.5, 1.0                   # bias / row vector and residual amplitudes
+    if fam == "act":
+        sk = ru(0.1, 30.0, Cin)
+        sk[outliers(Cin)] = 300.0
+        x = rn(*shape, Cin) * sk
+        if c["ln"] is not None or c["gn_pro"] is not None:
+            x = x + 4.0 * sk * torch.sign(rn(Cin))
+        gain = ru(0.3, 3.0, N)
+        W = rn(N, K) * K ** -0.5 * gain[:, None]
+        if geglu:                       # sig: the pre-activation std of a row of gain 1
+            sig = float(sk.square().mean().sqrt())
+            W[:N // 2] *= 3.0 / sig
+            W[N // 2:] *= 70.0 / sig / gain[N // 2:, None]
+        eb, er = 5.0, 30.0
+    elif fam in ("cancel", "exact", "overflow"):
+        cols = gemm_slab_columns(c, S)
+        sgn = torch.sign(rn(Cin))
+        sgn_k = sgn[torch.arange(K) % Cin]                                  # (tap-major, channel-minor)
+        rel = torch.zeros(K)
+        if fam == "overflow" and c["cls"] == "conv":
+            assert Cin == 128
+            rel = 1.0 - 2.0 * (torch.arange(K) // 64 % 2)                  # + on the first 64-channel block of a tap, - on the second
+        else:
+            h = len(cols) // 2
+            n_pos, n_neg = sum(len(i) for i in cols[:h]), sum(len(i) for i in cols[h:])
+            rel[torch.cat(cols[:h])] = 1.0
+            rel[torch.cat(cols[h:])] = -n_pos / n_neg
+        assert abs(float(rel.sum())) < 1e-9
+        nominal = max(abs(float(rel[i].sum())) for i in cols)              # the largest |sum of rel| over a slab
+        if fam == "exact":
+            x = 4.0 * ri(-2, 2, *shape, Cin) + 8.0 * sgn
+            W = 8.0 * ri(-1, 1, N, K) + 8.0 * rel * sgn_k
+            assert bool((W % 4 == 0).all()) and 64.0 * nominal == 12288.0
+        else:
+            a = 8.0
+            b = 12288.0 / (a * nominal)
+            x = rn(*shape, Cin) + a * sgn * (1 + 0.1 * rn(*shape, 1))
+            W = rn(N, K) * K ** -0.5 + b * rel * sgn_k * (1 + 0.1 * rn(N, 1))
+            if fam == "overflow":           # (patch: a pixel's partial averages the row factor over nine taps -- less spread)
+                x, W = 2.0 * x, (2.25 if c["cls"] == "patch" else 2.0) * W
+            eb = 100.0                      # (of the size of the results: the bound of these cases is 10 to 20 per element)
+    else:
+        assert fam == "staged" and c["bias"] and c["rowvec"] and c["res"] and not c["bias_per_row"]
+        x, W = rn(*shape, Cin), rn(N, K) * K ** -0.5
+    _put_input(p, x, rn)
+    p["W"] = W.half()
+    if fam == "staged":
+        sg = torch.sign(rn(N))
+        big_b, big_r = torch.rand(N, generator=g) < 0.1, torch.rand((groups, N), generator=g) < 0.15
+        p["bias"] = (0.5 * rn(N) + 4e4 * sg * big_b).half()
+        p["rowvec"] = (0.5 * rn(groups, N) + 3.5e4 * sg * big_r).half()
+        either = big_b[None] | big_r[torch.arange(M) // c["rows_per_rv"]]
+        p["R"] = (rn(M, N) - 3e4 * sg * either).half()
+        return p
+    if c["bias"]:
+        p["bias"] = (eb * rn(M if c["bias_per_row"] else N)).half()
+    if c["rowvec"]:
+        p["rowvec"] = (eb * rn(groups, N)).half()
+    if c["res"]:
+        if fam == "exact":
+            assert not c["bias"] and not c["rowvec"]
+            p["R"] = (16.0 * ri(-8, 8, c["res_rows"] or M, n_out)).half()
+        else:
+            R = er * rn(c["res_rows"] or M, n_out)
+            if fam == "act":
+                R[:, outliers(n_out)] *= 10.0
+            p["R"] = R.half()
+    if c["gnf"] is not None:
+        p["gnf_gamma"], p["gnf_beta"] = (1 + 0.2 * rn(N)).half(), (0.1 * rn(N)).half()
+    return p
+
+
+@functools.lru_cache(maxsize=None)
+def gemm_problem(cid):
+    """the seeded fp16 operands of one case (CPU), logical tensors only (gemm_operands puts them into the poisoned buffers a
+    launch sees).  Do not modify the result.  By the case's `operands`:
+      unit       unit Gaussians against K^-0.5 weights: partial sums below 4, results below 5
+      act        SYNTHETIC trained magnitudes (no checkpoint exists where the suite runs: the figures are those reported for
+                 transformer / UNet activations, per-channel scales over two decades and a few massive channels).  Activations
+                 randn * s_k, s_k log-uniform in [0.1, 30], two channels of every 64 at 300 (the last of the block -- so that
+                 the last K index carries weight -- and a random one); LayerNorm-fold and GroupNorm-prologue cases add a
+                 per-channel mean of +-4 s_k; weights randn * K^-0.5 times a per-row gain log-uniform in [0.3, 3]; bias and row
+                 vector 5 randn; residual 30 randn, times 10 in two columns of every 64.  GEGLU: the gate rows are scaled to
+                 a pre-activation std of 70 (about [-300, 300]) and the x rows to 3 times their gain, so that x * gelu(gate)
+                 stays below 3e4
+      cancelS    a shared sign pattern s_k (per channel) of amplitude 8 (1 + 0.1 randn per row) on top of unit noise in A; in W
+                 the same pattern, + in the first half of the slab list of split count S and - in the second, the two
+                 weighted by their K extents so that the sum over K vanishes, scaled so that the largest slab partial is
+                 nominally 12288: partials about +-2e4, results O(1e2 .. 1e3).  Bias and row vector 100 randn (of the size of
+                 the results, so that an epilogue mistake is not lost in the slab term of the bound), the residual as in `unit`
+      exactS     the same from small integers: A = 4 {-2 .. 2} + 8 s_k, W = 8 {-1, 0, 1} +- {8, 8 n0 / n1} s_k (multiples of 4), the
+                 residual 16 {-8 .. 8}: every product is a multiple of 16 and nothing rounds
+      overflowS  (GEMM_RANGE_CASES) cancelS with A and W times 2 (W of the patch kernel times 2.25): partials about +-8e4.  On the implicit convolution the + and
+                 - parts alternate between the 64-channel blocks of every TAP instead (amplitude: one K tile = 12288 * 4):
+                 a border pixel then loses balanced pairs, where the half / half layout leaves it a result beyond the range
+                 even unsplit
+      staged     (GEMM_RANGE_CASES) unit A and W; bias +-4e4 on a tenth of the columns, row vector +-3.5e4 of the same sign on
+                 15 % of its entries, residual -+3e4 wherever either is large"""
+    c = GEMM_CASE[cid]
+    M, N, K = c["M"], c["N"], c["K"]
+    # (seeded from the id without its variant / split part: the cases of one problem share their operands, so the GPU file can
+    #  hold a forced variant against the heuristic and a split launch against the unsplit one)
+    g = torch.Generator().manual_seed(zlib.crc32(gemm_problem_key(cid).encode()))
+    rn = lambda *s: torch.randn(s, generator=g)
+    p = dict(case=c, A2=None, bias=None, rowvec=None, R=None, gn_table=None)
+    if c["operands"] != "unit":
+        return _gemm_problem_of_kind(p, g)
+    if c["kind"] == "conv":
+        B, H, W, Cin = c["image"]
+        x = rn(B, H, W, Cin) + (0.5 if c["gn_pro"] is not None else 0.0)
+    else:
+        x = rn(M - c["zero_rows"], K) + (0.5 if c["ln"] is not None else 0.0) + (4.0 if c["ln"] == "shifted" else 0.0)
+    _put_input(p, x, rn)
     p["W"] = (rn(N, K) * K ** -0.5).half()                                # logical rows: [x | gate] halves for GEGLU
     if c["bias"]:
         p["bias"] = (0.5 * rn(M if c["bias_per_row"] else N)).half()

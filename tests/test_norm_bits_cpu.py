@@ -15,7 +15,7 @@ def test_fixture_names_exactly_the_cases():
     assert gn == [c["id"] for c in KR.GN_CASES] and len(gn) == 27
     assert [cid for k, cid, _, _ in rows if k == "table"] == [c["id"] for c in KR.GN_CASES if c["table"]]
     split = [KR.GEMM_CASE[cid] for k, cid, _, _ in rows if k == "splitk"]
-    assert split == [c for c in KR.GEMM_CASES if c["splits"] > 1]
+    assert split == [c for c in KR.GEMM_CASES if c["splits"] > 1 and c["operands"] == "unit"] and len(split) == 63
     assert {c["reduce"] for c in split} == set(N.SPLITK_REDUCERS)
     assert {c["gnf"] for c in split} == {None, True, False}, "gnf with the raw result kept and skipped"
 

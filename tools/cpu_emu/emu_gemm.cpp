@@ -56,6 +56,7 @@ struct Case {
   int res_rows = 0;        // > 0: the residual holds that many rows, read with one wrap (PfdGemmDesc.res_rows)
   bool declined = false;   // the library must not serve the request: return value 1, nothing written
   int gn_pro = 0;          // 1 / 2: GroupNorm affine map (+ SiLU) in the staging path of the patch kernel (PfdGemmDesc.gn_table)
+  int contract = 0;        // 1 / 2: the slab contract of PfdGemmDesc.ws on integer operands whose two slab partials cancel, inside / beyond the f16 range
 };
 
 // PfdGemmDesc.ups = 2: the 3x3 weight [N][9 Cin] folded (fp32, rounded once) into four 2x2-tap phase blocks [py][px][N][4 Cin]:
@@ -142,6 +143,21 @@ static int run_case(const Case& c) {
   auto rv = rand_h((size_t)((M + rows_per_rv - 1) / rows_per_rv) * N, 0.5f);
   for (long r = 0; r < c.zero_rows; ++r)
     for (long k = 0; k < lda_full; ++k) Afull[r * lda_full + k] = (h16)0;
+  if (c.contract) {
+    // split-K 2 over five K tiles: slabs [0, 192) and [192, K).  A = 4 {-2..2} + 8 s_k, W = 8 {-1, 0, 1} + 8 s_k in the first slab
+    // and - 12 s_k in the second, bias 16 {-4..4}: every product is a multiple of 16, the two partials are about +-12288 and
+    // nothing rounds; contract 2 doubles A and the noise of W and triples its common part (multiples of 32, partials about
+    // +-73728: most beyond 65504, a few per cent of them back inside)
+    std::uniform_int_distribution<int> d2(-2, 2), d1(-1, 1), d4(-4, 4), sg(0, 1);
+    const float mul = c.contract == 2 ? 2.f : 1.f;
+    std::vector<float> sk(K);
+    for (auto& v : sk) v = sg(rng) ? 1.f : -1.f;
+    for (int m = 0; m < M; ++m)
+      for (int k = 0; k < K; ++k) Afull[(size_t)m * K + k] = (h16)(mul * (4.f * d2(rng) + 8.f * sk[k]));
+    for (int n = 0; n < N; ++n)
+      for (int k = 0; k < K; ++k) Wt[(size_t)n * K + k] = (h16)(mul * 8.f * d1(rng) + (c.contract == 2 ? 3.f : 1.f) * (k < 192 ? 8.f : -12.f) * sk[k]);
+    for (auto& v : bias) v = (h16)(16.f * d4(rng));
+  }
   // device operands: rows below zero_rows are not stored; columns >= k_split live in a second buffer
   const int K1 = c.k_split ? c.k_split : (int)lda_full, K2 = c.k_split ? K - c.k_split : 0;
   const long Mz = a_rows - c.zero_rows;
@@ -182,6 +198,51 @@ static int run_case(const Case& c) {
     return ok ? 0 : 1;
   }
   if (rc != 0) { printf("FAIL %-70s rc=%d %s\n", c.what, rc, g_err.c_str()); return 1; }
+  if (c.contract) {
+    // include/pfd_hip.h, PfdGemmDesc.ws: epi(sum_s f16(P_s)), the slabs summed in fp32 in slab order, IEEE throughout -- here every
+    // finite quantity is exact, so the whole output is held to the bits (a NaN to being one)
+    size_t bad = 0, n_nan = 0, n_inf = 0;
+    double pmax = 0;
+    for (int m = 0; m < M; ++m)
+      for (int n = 0; n < N; ++n) {
+        double P[2] = {0, 0};
+        for (int k = 0; k < K; ++k) P[k >= 192] += (double)Afull[(size_t)m * K + k] * (double)Wt[(size_t)n * K + k];
+        pmax = std::max(pmax, std::max(fabs(P[0]), fabs(P[1])));
+        float v = (float)(h16)P[0] + (float)(h16)P[1];
+        v += (float)(h16)P[1] * 0.f;   // the group of four is filled up with the last slab weighted by 0: NaN where that slab is +-inf
+        v += (float)bias[n];
+        if (c.act == PFD_ACT_RELU) v = fmaxf(v, 0.f);
+        const h16 want = (h16)v, got = C[(size_t)m * N + n];
+        if (c.contract == 1 && (double)want != P[0] + P[1] + (double)bias[n]) ++bad;   // (the double-precision sum itself)
+        n_nan += v != v; n_inf += std::isinf(v);
+        if (v != v ? !((float)got != (float)got) : memcmp(&want, &got, sizeof(h16)) != 0) {
+          if (++bad <= 4) printf("     (%d, %d): partials %.0f %.0f bias %.0f -> %g, expected %g\n", m, n, P[0], P[1], (double)bias[n], (double)got, (double)want);
+        }
+      }
+    bool ok = bad == 0 && (c.contract == 1 ? pmax < 32768 && n_nan + n_inf == 0 : n_nan > 0 && n_inf > 0);
+    std::string extra;
+    if (ok && c.gn_stats) {   // the statistics are the sums of the stored values (all finite here)
+      const int cpg = N / 32, tn = N / 160, ngl = 160 / cpg;
+      double worst = 0;
+      for (int sl = 0; sl < M / 64; ++sl)
+        for (int t = 0; t < tn; ++t)
+          for (int gl = 0; gl < ngl; ++gl) {
+            double a = 0, q = 0;
+            for (int r = 0; r < 64; ++r)
+              for (int cc = 0; cc < cpg; ++cc) { const double v = (double)C[(size_t)(sl * 64 + r) * N + t * 160 + gl * cpg + cc]; a += v; q += v * v; }
+            const size_t o = (((size_t)sl * tn + t) * 16 + gl) * 2;
+            worst = std::max(worst, std::max(fabs(a - gn1[o]) / (1 + fabs(a)), fabs(q - gn1[o + 1]) / (1 + fabs(q))));
+          }
+      ok = ok && worst <= 1e-3;
+      extra = " | statistics err " + std::to_string(worst);
+    }
+    if (c.contract == 1)
+      printf("%s %-70s bit-equal to the double-precision sum: %zu elements differ, max |partial| %.0f%s\n", ok ? "ok  " : "FAIL", c.what, bad, pmax, extra.c_str());
+    else
+      printf("%s %-70s IEEE pattern of sum_s f16(P_s): %zu elements differ, %zu NaN, %zu inf, max |partial| %.0f\n", ok ? "ok  " : "FAIL", c.what, bad, n_nan, n_inf, pmax);
+    fflush(stdout);
+    return ok ? 0 : 1;
+  }
   // double-precision reference
   double max_err = 0, max_ref = 0;
   for (int m = 0; m < M; ++m) {
@@ -530,6 +591,10 @@ int main(int argc, char** argv) {
   { auto c = conv("fused GroupNorm: split-K 2 conv 4x4x128 -> 1280 (cpg 40), row vector, raw skipped", 1280, 83, 2, 3, 1, 1, 0, 8, 4, 4, 128, false, -1); c->rowvec = true; c->gnf = 1; }
   { auto c = conv("fused GroupNorm: split-K 3 conv 4x4x192 -> 1280, residual, raw kept", 1280, 23, 3, 3, 1, 1, 0, 4, 4, 4, 192, true, -1); c->gnf = 2; }
   { auto c = conv("fused GroupNorm: split-K 2 patch conv 16x16x128 -> 1280, raw skipped", 1280, 98, 2, 3, 1, 1, 0, 4, 16, 16, 128, false, -1); c->rowvec = true; c->gnf = 1; }
+  // the slab contract of PfdGemmDesc.ws (include/pfd_hip.h) on the real split-K paths: partial sums that cancel, and one that leaves the range
+  { auto c = lin("slab contract: exact cancelling partials, split-K 2, 128x160x320", 128, 160, 320, 23, 2, false, -1); c->contract = 1; }
+  { auto c = lin("slab contract: the same, 128x320x320, through the reduction that emits group sums", 128, 320, 320, 23, 2, false, -1); c->contract = 1; c->gn_stats = true; }
+  { auto c = lin("slab contract: a partial beyond the range, split-K 2, 128x160x320", 128, 160, 320, 23, 2, false, -1); c->contract = 2; }
   // the barrier forms of the patch kernel (sanity of the emulation on the hardware-validated kernels)
   conv("variant 98 patch conv 16x16 (loader waves, barrier per tap), 2 channel blocks", 160, 98, 1, 3, 1, 1, 0, 1, 16, 16, 128, true, -1);
   conv("variant 96 patch conv 16x16 (3-stage weight ring), 2 channel blocks", 160, 96, 1, 3, 1, 1, 0, 1, 16, 16, 128, true, 98);
