@@ -2297,6 +2297,10 @@ int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s
   if (patch_variant || p.gn_table) return 1;
   const bool auto_variant = variant == V_AUTO;
   const int nk_all = p.K / BK;
+  // the transformer tail fold (proj_out over the virtual concat [h1 | g]: a two-source linear with K = 5 k_split);
+  // tail_split: its rule below chose two-stage 128-row blocks that are meant to be split and co-resident
+  const bool tail_fold = p.ksize == 0 && d->k_split > 0 && d->K == 5 * d->k_split;
+  bool tail_split = false;
   if (auto_variant) {
     // measured on MI355X: every GEMM/conv of a UNet pass replayed with COLD weights (the 1.7 GB of other
     // layers evict every W between two uses) under each forced variant (profiles/r01_gemm_replay_variants.log),
@@ -2332,8 +2336,13 @@ int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s
     if (bn == 160) {
       // (nk_all >= 5 since round 5 -- the 64^2 GEGLU projection, K = 320, too: -0.3 % end to end; >= 10 came from the cold replay)
             if (p.act == PFD_ACT_GEGLU && p.ksize == 0 && p.N % 320 == 0 && p.M >= 2048 && nk_all >= 5) variant = V84_256_GEGLU;
-      else if (p.ksize == 0 && (variant == V24_128 || variant == V25_128_RING) && p.M <= 2048 && nk_all >= 32)
+      else if (p.ksize == 0 && (variant == V24_128 || variant == V25_128_RING) && p.M <= 2048 && nk_all >= 32) {
         variant = V43_64_W8_RING;   // (>= 64 until round 5; >= 32: -0.5 % end to end)
+        // the tail fold where the 64-row form would not split (more than 128 tiles: 2048 x 1280 x 6400 at C2): 128-row tiles on
+        // two stages, split by the rule below (4 slabs of 25 K tiles, two blocks per CU): 62.2 -> 47.4 us in the cold replay
+        // (43 unsplit; 83 split 2 / 4: 50.9 / 57.7; profiles/ff_tail_fold_replay.log)
+        if (tail_fold && tiles(64) > 128) { variant = V82_128_W8; tail_split = true; }
+      }
       else if (p.ksize > 0 && p.stride == 2 && p.M <= 8192 && (variant == V24_128 || variant == V25_128_RING || variant == V22_64))
         variant = V43_64_W8_RING;
       else if (variant == V24_128) variant = V82_128_W8;
@@ -2374,7 +2383,7 @@ int pfd_gemm160_try(const PfdGemmDesc* d, int variant, int splits, hipStream_t s
     const int nk_split = nk_all / splits;
     if (variant == V22_64 && tiles(64) * splits <= 256 && nk_split >= 8) variant = V23_64_RING;
     if (variant == V24_128 && tiles(128) < 256 && nk_split >= 6) variant = V25_128_RING;
-    if (variant == V82_128_W8 && (p.ksize == 0 || (p.stride == 1 && !p.ups)) && tiles(128) <= 256 && nk_split >= 6)
+    if (variant == V82_128_W8 && !tail_split && (p.ksize == 0 || (p.stride == 1 && !p.ups)) && tiles(128) <= 256 && nk_split >= 6)
       variant = V83_128_W8_RING;
   }
   const int conv = p.ksize > 0 ? 1 : 0;

@@ -44,6 +44,7 @@ struct Case : GemmCase {
   Case& gn_out() { GemmCase::gn_out = 1; return *this; }
   Case& res_rows(int v) { GemmCase::res_rows = v; return *this; }
   Case& zero_rows(int v) { GemmCase::zero_rows = v; return *this; }
+  Case& k_split(int v) { GemmCase::k_split = v; return *this; }   // columns >= v of the operand in a second buffer
   Case& declined() { GemmCase::declined = 1; return *this; }
 };
 static Case lin(int M, int N, int K) { Case c; c.M = M; c.N = N; c.K = K; return c; }
@@ -273,6 +274,29 @@ static void run_ups_fold_cases() {
   run_gemm_case(conv(2, 16, 48, 64, 320).ups(2));
   run_gemm_case(conv(1, 8, 8, 64, 160).ups(2).declined());
   run_gemm_case(conv(1, 16, 16, 64, 160).ups(2).res().declined());   // residual: not served
+}
+
+// The transformer tail fold: proj_out over the virtual concat [h1 | g] (K = 5 k_split) with everything proj_out's epilogue
+// carries -- residual, the residual of a CFG pair stored once (res_rows), the GroupNorm statistics of the output -- under the
+// heuristic and every linear variant it can land on, unsplit and split (a split whose K range holds tiles of BOTH sources, and
+// the statistics-emitting reduction).  Columns >= k_split of the first buffer hold 7.0: they must never be read.
+static void run_ff_tail_fold_cases(bool full) {
+  for (int v : {0, 9200, 9300, 5100, 5300, 3200, 3300, 5400}) {
+    run_gemm_case(lin(1024, 320, 1600).k_split(320).res().res_rows(512).gn_out().tile(v));   // the CFG pair's proj_out
+    run_gemm_case(lin(640, 320, 1600).k_split(320).res().gn_out().tile(v));   // whole residual, ragged last 128- / 256-row tile
+  }
+  run_gemm_case(lin(1024, 320, 1600).k_split(320).res());   // a Linear proj_out: no statistics
+  run_gemm_case(lin(448, 640, 3200).k_split(640).res().gn_out().ld(+8));   // 640 channels, ld + 8
+  run_gemm_case(lin(1024, 320, 1600).k_split(320).res().res_rows(512).tile(5304));   // 4 splits of 7 K tiles, 5 from h1: plain reduction
+  run_gemm_case(lin(1024, 320, 1600).k_split(320).res().res_rows(512).gn_out().tile(5304));   // ... statistics-emitting reduction
+  run_gemm_case(lin(1024, 320, 1600).k_split(320).res().gn_out().tile(9302));   // 128-row tiles, 2 splits
+  run_gemm_case(lin(512, 1280, 6400).k_split(1280).res().gn_out());   // the mid block's shape: the heuristic splits it (cpg 40)
+  run_gemm_case(lin(576, 2560, 2240).k_split(448).res());   // > 128 64-row tiles: the dispatcher's tail-fold rule (82, split 2)
+  if (full) {       // the other shapes a C2 UNet pass launches, against fp64 (minutes of host time)
+    run_gemm_case(lin(2048, 1280, 6400).k_split(1280).res().gn_out());
+    run_gemm_case(lin(8192, 640, 3200).k_split(640).res().gn_out());
+    run_gemm_case(lin(32768, 320, 1600).k_split(320).res().res_rows(16384).gn_out());
+  }
 }
 
 // K-tile-contiguous weights (PfdGemmDesc.w_tiled): every wide-tile kernel family, both tile widths, conv K walks, split-K
@@ -1255,6 +1279,7 @@ static void run_default_cases() {
   run_gemm_case(conv(1, 9, 9, 64, 320).stride(2).pad(0).ld(+8));   // pad 0, ld+8
   run_gemm_case(conv(2, 6, 6, 128, 160).k(1).pad(0));   // 1x1 as conv
   run_ups_fold_cases();
+  run_ff_tail_fold_cases(false);
   run_narrow_conv_cases();
 
   run_gemm_case(conv(1, 16, 48, 128, 160).act(PFD_ACT_SILU).res().rowvec());   // patch kernel, 2-D tiles
@@ -1415,7 +1440,7 @@ struct Mode {
 #define CASES(body) [](int, char**) { body; }
 static const Mode kModes[] = {
     {"", nullptr, CASES(print_device(); run_default_cases()), nullptr,
-     "default run: GEMM / conv (with --ups-fold, --narrow and the first two --patch-wide cases), --ln, the first 12 --attn\n"
+     "default run: GEMM / conv (with --ups-fold, --ff-tail-fold, --narrow and the first two --patch-wide cases), --ln, the first 12 --attn\n"
      "                             and the first 2 --attn512 cases, Swin attention, GroupNorm, LayerNorm, softmax, --elementwise, --image.\n"
      "                             NOT in it: --gn-fusion, --tile-variants, --ups-fold full, the rest of --patch-wide, --attn, --attn512"},
     {"--bench", nullptr, CASES(print_device(); run_default_cases()), bench_unet_list, "the default run, then the UNet-shaped GEMM / attention / GroupNorm timings"},
@@ -1425,6 +1450,8 @@ static const Mode kModes[] = {
     {"--patch-wide", nullptr, CASES(run_patch_wide_cases()), nullptr, "3x3 patch kernels on 48- / 96-wide images (2-D output tiles)"},
     {"--ups-fold", nullptr, [](int n, char** a) { run_ups_fold_mode(n > 0 && !strcmp(a[0], "full")); }, nullptr,
      "[full]  upsample convolution as four 2x2-tap phase convolutions; full: also the two large C2 shapes"},
+    {"--ff-tail-fold", nullptr, [](int n, char** a) { run_ff_tail_fold_cases(n > 0 && !strcmp(a[0], "full")); }, nullptr,
+     "[full]  proj_out folded over [h1 | g]: k_split + residual (+ res_rows) + statistics, unsplit and split; full: the C2 shapes"},
     {"--narrow", nullptr, CASES(run_narrow_mode()), nullptr, "conv3x3_narrow_kernel (N <= 16): cases and timings of the pipeline's shapes"},
     {"--ln", nullptr, CASES(run_ln_fold_suite()), nullptr, "LayerNorm folded into the GEMM, add_rowvec + row statistics"},
     {"--attn", nullptr, CASES(run_attn_cases()), nullptr, "attention, d = 40 ... 160 (run once per PFD_ATTN* test hook)"},

@@ -127,6 +127,27 @@ def fold_layernorm(w, b, gamma, beta):
     return wg, cs, bp.to(torch.float16).contiguous()
 
 
+def fold_ff_tail(wpo, bpo, w2, b2):
+    """Operands of `proj_out(ff_out(g) + h1)` as ONE contraction over the virtual concat [h1 | g] (PfdGemmDesc.k_split):
+    wpo [C_out, inner] (a 1x1 convolution's [C_out, inner, 1, 1] too), w2 [inner, Kff], biases or None ->
+    (W' = [Wpo | Wpo W2] as [C_out, inner + Kff], b' = Wpo b2 + bpo).  Wpo W2 is accumulated in fp32 over the fp16 weights by
+    the library's own GEMM and rounded ONCE (fp64 weights: the algebra itself in fp64, nothing rounded); b' by elementwise
+    product + row sum in fp32 (no BLAS inside lib/, as in fold_layernorm).  Runs once per weight version."""
+    wpo = wpo.detach().reshape(wpo.shape[0], -1)
+    w2 = w2.detach()
+    if wpo.dtype == torch.float64:
+        bf = wpo @ b2.detach() if b2 is not None else wpo.new_zeros(wpo.shape[0])
+        return torch.cat([wpo, wpo @ w2], 1), bf if bpo is None else bf + bpo.detach()
+    wpo16 = _dev16(wpo).contiguous()
+    wf = ops.gemm(wpo16, _dev16(w2).t().contiguous())                      # [C_out, Kff] = Wpo [C_out, inner] @ (W2^T [Kff, inner])^T
+    bf = torch.zeros(wpo.shape[0], dtype=torch.float32, device=wpo.device)
+    if b2 is not None:
+        bf = (wpo16.float() * _dev16(b2).float()[None, :]).sum(1)
+    if bpo is not None:
+        bf = bf + _dev16(bpo).float()
+    return torch.cat([wpo16, wf], 1).contiguous(), bf.to(torch.float16).contiguous()
+
+
 class _Packed:
     """mixin: self._packed(name, builder, *params) -> cached kernel-layout tensors"""
 

@@ -587,6 +587,12 @@ int main(int argc, char** argv) {
   // split-K reduction that also emits the GroupNorm statistics (three row sweeps in flight)
   { auto c = lin("split-K 4 + GroupNorm statistics (N 320: cpg 10), residual", 128, 320, 1024, 23, 4, true, -1); c->gn_stats = true; }
   { auto c = conv("split-K 2 conv 8x8x128 -> 1280 + statistics (cpg 40), SiLU-free", 1280, 83, 2, 3, 1, 1, 0, 2, 8, 8, 128, true, -1); c->gn_stats = true; }
+  // the transformer tail fold (proj_out over [h1 | g]): two sources + residual with one wrap + group sums of the output in one
+  // launch, on the store pass of the 128-row and 64-row eight-wave tiles and through the split-K reduction (slab 0 holds K tiles
+  // of both sources)
+  { auto c = lin("tail fold: k_split 64 of K 320, res_rows 128, group sums (cpg 10), 8-wave 128-row tile", 256, 320, 320, 82, 1, true, -1); c->k_split = 64; c->res_rows = 128; c->gn_stats = true; }
+  { auto c = lin("tail fold: k_split 64 of K 320, res_rows 64, group sums, 8-wave 64-row ring", 128, 320, 320, 43, 1, true, -1); c->k_split = 64; c->res_rows = 64; c->gn_stats = true; }
+  { auto c = lin("tail fold: k_split 128 of K 640, res_rows 64, split-K 2 through the reduction that emits group sums", 128, 320, 640, 43, 2, true, -1); c->k_split = 128; c->res_rows = 64; c->gn_stats = true; }
   // split-K reduction that also NORMALISES (PfdGemmDesc.gnf_y, round 5): 8 samples so that B * 32 >= 128 blocks as the host demands
   { auto c = conv("fused GroupNorm: split-K 2 conv 4x4x128 -> 1280 (cpg 40), row vector, raw skipped", 1280, 83, 2, 3, 1, 1, 0, 8, 4, 4, 128, false, -1); c->rowvec = true; c->gnf = 1; }
   { auto c = conv("fused GroupNorm: split-K 3 conv 4x4x192 -> 1280, residual, raw kept", 1280, 23, 3, 3, 1, 1, 0, 4, 4, 4, 192, true, -1); c->gnf = 2; }
