@@ -11,6 +11,10 @@ Multi-GPU (new, the reference is single-device): samples are independent, so ran
 samples [r*n/P, (r+1)*n/P) of the global batch.  x_T is drawn ONCE for the global shape from a
 CPU generator and sliced, so results do not depend on P.  The only collective is one RCCL
 all-gather of the decoded images after the loop (`gather=True`).
+
+Both request doors -- `PromptFreePipeline.generate` here, `PromptFreeServer.submit` / `_generate` in lib/serving.py -- go through
+`check_request` (arguments -> `Request`, on the host) and `PromptFreePipeline.assemble` (slices of requests -> one sampler call):
+generate hands over one slice, its rank's samples of one request; a server one slice per request of its batch.
 """
 import os
 
@@ -280,6 +284,111 @@ def check_control_strength(control, control_scale, control_layer_scales, control
     return out
 
 
+class Request:
+    """one checked request (`check_request`): what both doors -- PromptFreePipeline.generate and PromptFreeServer.submit --
+    turn their arguments into before anything touches the device, and what `PromptFreePipeline.assemble` reads.  A field
+    that was not given is None."""
+    __slots__ = ("image", "n", "height", "width", "steps", "scale", "eta", "seed", "control", "uncond", "as_uint8",
+                 "device_noise", "future", "mixed", "solver", "control_preprocess", "control_thresholds", "init", "strength",
+                 "init_k", "mask", "composite", "weights", "regional", "ctl", "rescale")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+    def key(self):
+        """requests with equal keys can share one DDIM batch (mixed: any two scales other than 1 can)"""
+        how = () if self.solver in (None, 'ddim') else (self.solver,)     # a batch runs ONE solver; the DDIM keys are unchanged
+        if self.init is not None:     # img2img: a batch runs ONE number of steps; every other key is unchanged
+            how = how + (('init', int(self.init_k)),)
+        if self.mask is not None:     # inpainting: masked requests share batches with each other only; every other key is unchanged
+            how = how + (('mask', bool(self.composite)),)
+        if self.regional is not None:  # regional mixing: with regional requests of the same number of regions and references only
+            how = how + (('regions',) + tuple(self.regional[1].shape),)
+        elif self.weights is not None:  # several references: with each other only, whatever their number; every other key is unchanged
+            how = how + ('refmix',)
+        if self.ctl is not None:      # a scaled / windowed control: equal layers, steps and cond_only; the strengths may differ
+            how = how + (('control',) + tuple(self.ctl[1:]),)
+        if self.rescale is not None:  # guidance rescale: with each other only, whatever their phi; every other key is unchanged
+            how = how + ('rescale',)
+        if self.mixed:
+            return (self.height, self.width, self.steps, float(self.scale) == 1.0, float(self.eta),
+                    self.control is None, self.uncond is None, bool(self.as_uint8), bool(self.device_noise)) + how
+        return (self.height, self.width, self.steps, float(self.scale), float(self.eta), self.control is None,
+                self.uncond is None, bool(self.as_uint8), bool(self.device_noise)) + how
+
+    def shareable(self):
+        """eta > 0 WITHOUT device_noise draws its noise from the global RNG inside the loop (ddim.py:166): batched with
+        other requests the draw -- and so the result for a given seed -- would depend on the company; such requests run
+        alone, seeded.  With device_noise the noise of sample j is a function of (request seed, j, step, element)
+        (lib/noise.py), whatever it is batched with: shareable at any eta.  ControlNet requests always run alone, unless
+        the server mixes batches: then they share with each other (`control is None` is part of the key)."""
+        return (float(self.eta) == 0.0 or bool(self.device_noise)) and (self.control is None or bool(self.mixed))
+
+
+def check_request(*, image, n, height, width, steps, scale, eta, seed, control, uncond, as_uint8, device_noise, solver,
+                  control_preprocess, control_thresholds, init, strength, mask, composite, image_weights, regions,
+                  region_weights, control_scale, control_layer_scales, control_window, control_cond_only, guidance_rescale,
+                  num_timesteps, init_posterior='sample', first=0, n_local=None):
+    """the arguments of a request of n samples (`PromptFreePipeline.generate` describes them), checked on the host before
+    anything touches the device -> Request.  The one place where a feature's arguments are checked, for both doors.
+    The caller runs the n_local samples from `first` on (generate: its rank's; default: all n): a per-sample argument is
+    checked for all n, and what comes to nothing ON THOSE samples -- a control of strength 0, a phi of 0 -- is dropped from
+    the record, which otherwise speaks of the whole request.  image, control and mask are kept as given, so a picture per
+    sample is one per sample of the caller.  num_timesteps: a callable, asked only when a strength argument is off its
+    default."""
+    from . import control as control_lib
+    from . import guidance as guidance_lib
+    from .model_zoo.ddim import is_per_sample
+    from .solver import solver_order
+    n_local = int(n) if n_local is None else int(n_local)
+    if solver_order(solver) is not None and (float(eta) != 0.0 or device_noise):     # an unknown name raises here too
+        raise ValueError(f"solver {solver!r} is deterministic: eta must be 0 and device_noise off")
+    image, image_weights, regional = check_regions(image, regions, region_weights, image_weights)
+    refs = check_references(image, image_weights if regional is None else [1.0] * len(image))
+    weights = None
+    if refs is not None:      # one reference left: the plain request of that picture
+        image, weights = (refs[0][0], None) if len(refs[0]) == 1 else (list(refs[0]), [float(w) for w in refs[1]])
+    if is_per_sample(scale) and tuple(torch.as_tensor(scale).shape) != (n,):
+        raise ValueError(f"scale must be one number or {n} numbers, one per sample of the global batch")
+    cfg = is_per_sample(scale) or float(scale) != 1.0          # scale 1: no unconditional half
+    if torch.is_tensor(guidance_rescale):
+        guidance_rescale = guidance_rescale.detach().cpu().numpy()
+    phi = guidance_lib.check_phi(guidance_rescale, n)
+    rescale = guidance_lib.normalise(phi[first:first + n_local], n_local, 2 if cfg else 1)      # None: nothing of it on those samples
+    if rescale is not None:
+        rescale = phi.astype(np.float32)
+    if torch.is_tensor(control) and control.dim() == 4 and control.shape[0] not in (1, n_local):
+        raise ValueError(f"control must be [1, 3, H, W] (shared) or [{n_local}, 3, H, W] (one hint per local "
+                         f"sample): got {control.shape[0]} hints")
+    if weights is None and image_io.wants_ingest(image):
+        image_io.check_u8_picture(image, 'image', min_side=32)
+    if control is not None and image_io.wants_ingest(control):
+        image_io.check_resize(image_io.check_u8_picture(control, 'control')[:2], (int(height), int(width)), 'control')
+    thresholds = image_io.check_control_preprocess(control, control_preprocess, control_thresholds)
+    init_k = None if init is None else image_io.check_img2img(init, int(height), int(width), int(steps), strength, init_posterior)
+    image_io.check_mask(mask, init, int(height), int(width), composite, as_uint8, n=n_local)
+    if mask is not None and float(eta) != 0.0 and not device_noise:
+        raise ValueError("a masked request with eta > 0 needs device_noise=True: the masked step draws nothing from "
+                         "the global generator")
+
+    def total_k():      # (schedule length, steps the run evaluates)
+        total = schedule_length(steps, num_timesteps())
+        return total, total if init_k is None else int(init_k)
+    ctl = check_control_strength(control, control_scale, control_layer_scales, control_window, control_cond_only, n,
+                                 2 if cfg else 1, total_k, first=first, n_local=n_local)
+    if ctl == 'off':
+        control, ctl = None, None        # nothing left of the control: the uncontrolled request, before a hint is made
+    elif ctl is not None:        # (strengths float64 [n], layer weights, controlled steps, cond_only); a server's key: all but the first
+        ctl = (control_lib.sample_scales(control_scale.tolist() if torch.is_tensor(control_scale) else control_scale, n),
+               tuple(float(v) for v in control_lib.layer_scales(control_layer_scales)), ctl[1], bool(control_cond_only) and cfg)
+    return Request(image=image, weights=weights, regional=regional, ctl=ctl, rescale=rescale, n=int(n), height=int(height),
+                   width=int(width), steps=int(steps), scale=scale, eta=eta, seed=int(seed), control=control, uncond=uncond,
+                   as_uint8=as_uint8, device_noise=bool(device_noise), solver=solver, control_preprocess=control_preprocess,
+                   control_thresholds=thresholds, init=init, strength=strength, init_k=init_k, mask=mask,
+                   composite=bool(composite) if mask is not None else None)
+
+
 class PromptFreePipeline:
     """One rank's view of a (possibly multi-GPU) request: shard -> encode -> DDIM loop -> decode -> gather.
     `sampler` is injectable (the gloo CPU tests drive this very code with a stand-in for the GPU compute)."""
@@ -372,6 +481,11 @@ class PromptFreePipeline:
         ub[:, nu:] = float('-inf')
         return torch.cat([uncond, pad], 1), ub
 
+    def _dtypes(self):
+        """(the model dtype, the dtype the picture kernels write for it: fp16 and fp32 themselves, fp32 for any other)"""
+        dtype = self.net.get_dtype() if hasattr(self.net, 'get_dtype') else torch.float32
+        return dtype, (dtype if dtype in (torch.float16, torch.float32) else torch.float32)
+
     @serialised
     @torch.no_grad()
     def ingest(self, picture, size=None, what='image'):
@@ -379,8 +493,7 @@ class PromptFreePipeline:
         `ToTensor()(im)[None].to(device).to(dtype)` (app.py:234), behind `im.resize([W, H], BICUBIC)` when size = (H, W)
         is given (app.py:232,244) -- both as HIP kernels (ops.image_from_u8); one byte per channel crosses PCIe"""
         u8 = image_io.to_device_u8(picture, self.net.device, what)
-        dtype = self.net.get_dtype() if hasattr(self.net, 'get_dtype') else torch.float32
-        kdtype = dtype if dtype in (torch.float16, torch.float32) else torch.float32
+        dtype, kdtype = self._dtypes()
         x = ops.image_from_u8(u8, size, dtype=kdtype)
         return x if kdtype == dtype else x.to(dtype)
 
@@ -397,10 +510,9 @@ class PromptFreePipeline:
         dev = self.net.device
         if preprocess is None:
             return self.ingest(control, (height, width), 'control') if image_io.wants_ingest(control) else control.to(dev)
-        dtype = self.net.get_dtype() if hasattr(self.net, 'get_dtype') else torch.float32
+        dtype, kdtype = self._dtypes()
         if image_io.wants_ingest(control):
             image_io.check_resize(image_io.check_u8_picture(control, 'control')[:2], (height, width), 'control')
-            kdtype = dtype if dtype in (torch.float16, torch.float32) else torch.float32
             u8 = ops.image_from_u8(image_io.to_device_u8(control, dev, 'control'), (height, width), layout='u8')
             hint = ops.canny_u8(u8, low, high, out='hint', dtype=kdtype)
             return hint if kdtype == dtype else hint.to(dtype)
@@ -436,12 +548,9 @@ class PromptFreePipeline:
             pic = init.to(dev)
         moments = self._enc_stage(pic) if self._enc_stage is not None else self.net.vae_encode_moments(pic, 'image')
         sf = (getattr(self.net, 'latent_scale_factor', None) or {}).get('image', None)
-        if want_x0:
-            x0, x_t = ops.latent_start(moments, keys.to(dev), 1.0 if sf is None else sf, self._level(steps, k),
-                                       posterior=posterior, want_x0=True)
-            return x_t, k, x0
-        x_t = ops.latent_start(moments, keys.to(dev), 1.0 if sf is None else sf, self._level(steps, k), posterior=posterior)
-        return x_t, k
+        out = ops.latent_start(moments, keys.to(dev), 1.0 if sf is None else sf, self._level(steps, k), posterior=posterior,
+                               want_x0=want_x0)
+        return (out[1], k, out[0]) if want_x0 else (out, k)
 
     @serialised
     @torch.no_grad()
@@ -541,114 +650,24 @@ class PromptFreePipeline:
         reference (0.7 is the paper's value).  One small launch in front of the step kernel (pfd_guidance_rescale_f32); a
         sample's result does not depend on its company nor on the world size.  0 (or all zero, or scale 1): the plain
         request, its path, graph and bits.  Works with every other argument; draws nothing."""
-        from .model_zoo.ddim import is_per_sample
-        from .solver import solver_order
-        if solver_order(solver) is not None and (eta != 0. or device_noise):     # an unknown name raises here too
-            raise ValueError(f"solver {solver!r} is deterministic: eta must be 0 and device_noise off")
         P, r = self.world_size, self.rank
-        dev = self.net.device
-        image, image_weights, regional = check_regions(image, regions, region_weights, image_weights)
-        refs = check_references(image, image_weights if regional is None else [1.0] * len(image))     # checked before anything touches the device
-        if refs is not None and len(refs[0]) == 1:
-            image, refs = refs[0][0], None                # one reference left: the plain request
-        if is_per_sample(scale):     # checked before anything touches the device
-            if tuple(torch.as_tensor(scale).shape) != (n_global,):
-                raise ValueError(f"scale must be one number or {n_global} numbers, one per sample of the global batch")
-            scale = shard_scales(scale, r, P)
-        phi = shard_rescale(guidance_rescale, n_global, r, P)     # checked before anything touches the device
-        if torch.is_tensor(control) and control.dim() == 4 and control.shape[0] not in (1, n_global // P):
-            raise ValueError(f"control must be [1, 3, H, W] (shared) or [{n_global // P}, 3, H, W] (one hint per local "
-                             f"sample): got {control.shape[0]} hints")
-        u8_image = refs is None and image_io.wants_ingest(image)
-        u8_control = control is not None and image_io.wants_ingest(control)
-        if u8_image:                 # checked before anything touches the device
-            image_io.check_u8_picture(image, 'image', min_side=32)
-        if u8_control:
-            image_io.check_resize(image_io.check_u8_picture(control, 'control')[:2], (height, width), 'control')
-        image_io.check_control_preprocess(control, control_preprocess, control_thresholds)
-        if init is not None:         # strength first: checked before anything touches the device
-            image_io.check_img2img(init, height, width, steps, strength, init_posterior)
-            if n_global % P:
-                raise ValueError("global batch must divide over the ranks")
-        image_io.check_mask(mask, init, height, width, composite, as_uint8, n=n_global // P)
-        if mask is not None and eta != 0. and not device_noise:
-            raise ValueError("a masked request with eta > 0 needs device_noise=True: the masked step draws nothing from "
-                             "the global generator")
+        if n_global % P:
+            raise ValueError("global batch must divide over the ranks")
+        n = n_global // P
+        req = check_request(
+            image=image, n=n_global, height=height, width=width, steps=steps, scale=scale, eta=eta, seed=seed, control=control,
+            uncond=uncond, as_uint8=as_uint8, device_noise=device_noise, solver=solver, control_preprocess=control_preprocess,
+            control_thresholds=control_thresholds, init=init, strength=strength, mask=mask, composite=composite,
+            image_weights=image_weights, regions=regions, region_weights=region_weights, control_scale=control_scale,
+            control_layer_scales=control_layer_scales, control_window=control_window, control_cond_only=control_cond_only,
+            guidance_rescale=guidance_rescale, num_timesteps=lambda: self.net.num_timesteps, init_posterior=init_posterior,
+            first=r * n, n_local=n)
         if composite and not decode:
             raise ValueError("composite=True needs decode=True")
-        ctl_strength = check_control_strength(
-            control, control_scale, control_layer_scales, control_window, control_cond_only, n_global,
-            2 if (is_per_sample(scale) or scale != 1.) else 1,
-            lambda: (schedule_length(steps, self.net.num_timesteps),) * 2 if init is None else
-            (schedule_length(steps, self.net.num_timesteps), image_io.check_img2img(init, height, width, steps, strength, init_posterior)),
-            first=r * (n_global // P), n_local=n_global // P)
-        if ctl_strength == 'off':
-            control, ctl_strength = None, None        # nothing left of the control: the uncontrolled request, before a hint is made
-        mk = _Marks(torch.device(dev).type == 'cuda') if timings is not None else None
+        mk = _Marks(torch.device(self.net.device).type == 'cuda') if timings is not None else None
         if mk:
             mk.mark()
-        xT = shard_xT(n_global, height, width, seed, r, P) if init is None else None
-        n = xT.shape[0] if init is None else n_global // P
-        kbias = None
-        if u8_image:
-            image = self.ingest(image)
-        rtable = None
-        if regional is not None:          # the tokens of the references side by side; a row of logits per region
-            cond, zeros, rtable = self.encode_regions(refs[0], regional[1], n)
-        elif refs is not None:
-            cond, zeros, kbias = self.encode_references(refs[0], refs[1], n)
-        elif image.shape[0] > 1:
-            # one reference image PER SAMPLE (SURVEY 8(d): the "+737 GFLOP/img" variant): SeeCoder is run once per image
-            # (its decoder MHA attends across the batch axis, seecoder.py:70,83 -- a batch of images would mix them)
-            if image.shape[0] != n:
-                raise ValueError(f"{image.shape[0]} reference images for {n} local samples")
-            pairs = [self.encode_reference(image[i:i + 1].to(dev), 1) for i in range(n)]
-            cond, zeros = torch.cat([c for c, _ in pairs]), torch.cat([z for _, z in pairs])
-        else:
-            cond, zeros = self.encode_reference(image.to(dev), n)
-        ukb = None
-        if uncond is None:
-            uncond = zeros
-        elif (kbias is not None or rtable is not None) and uncond.shape[1] != cond.shape[1]:
-            uncond, ukb = self.pad_uncond(uncond.to(dev).to(cond.dtype), cond[:, :, 0])
-            if uncond.shape[0] == 1 and n > 1:
-                uncond, ukb = uncond.expand(n, -1, -1), ukb.expand(n, -1)
-        if mk:
-            mk.mark()
-        if init is None:
-            x_info = {'type': 'image', 'xt': xT.to(dev)}
-            shape = list(xT.shape)
-        else:
-            keys = shard_noise_keys(n_global, seed, r, P)
-            if mask is None:
-                x_t, k = self.init_latent(init, height, width, steps, strength, keys, init_posterior)
-                x_info = {'type': 'image', 'xt': x_t, 'xt_steps': k}
-            else:
-                x_t, k, x0 = self.init_latent(init, height, width, steps, strength, keys, init_posterior, want_x0=True)
-                x_info = {'type': 'image', 'xt': x_t, 'xt_steps': k, 'mask': self.mask_grid(mask, height, width, n=n),
-                          'x0_keep': x0, 'keep_key': keys.to(dev)}
-            shape = list(x_t.shape)
-            if mk:
-                mk.mark()
-        if device_noise:
-            x_info['noise_key'] = shard_noise_keys(n_global, seed, r, P).to(dev)
-        c_info = {'type': 'image', 'conditioning': cond, 'unconditional_conditioning': uncond,
-                  'unconditional_guidance_scale': scale}
-        if regional is not None:
-            c_info['region_bias'], c_info['region_map'] = rtable, regional[0]
-            if ukb is not None:
-                c_info['unconditional_region_bias'] = ukb[:, None].expand(-1, rtable.shape[1], -1)
-        elif kbias is not None:
-            c_info['key_bias'] = kbias
-            if ukb is not None:
-                c_info['unconditional_key_bias'] = ukb
-        if control is not None:
-            c_info['control'] = self.control_hint(control, height, width, control_preprocess, control_thresholds)
-            if ctl_strength is not None:
-                c_info['control_scale'] = torch.from_numpy(ctl_strength[0]).to(dev)
-                c_info['control_steps'] = ctl_strength[1]
-        if phi is not None and (is_per_sample(scale) or scale != 1.):     # (scale 1: no unconditional half, nothing to rescale)
-            c_info['guidance_rescale'] = phi
+        x_info, c_info, shape = self.assemble([(req, r * n, n)], posterior=init_posterior, mark=mk.mark if mk else None)
         how = {} if solver == 'ddim' else {'solver': solver}     # the default call is what it was
         x, _ = self.sampler.sample(steps=steps, shape=shape, x_info=x_info, c_info=c_info, eta=eta,
                                    verbose=verbose, **how)
@@ -660,7 +679,7 @@ class PromptFreePipeline:
             img = self.net.vae_decode(x, 'image', out_uint8=True)
             if composite:
                 img = self.composite(img, init, mask, height, width)
-        else:
+        else:       # (float images go through the graphed VAE stage here; a server decodes them directly)
             img = self._vae_stage(x) if self._vae_stage is not None else self.net.vae_decode(x, 'image')
         if mk:
             mk.mark()
@@ -673,3 +692,119 @@ class PromptFreePipeline:
         if gather:
             img = all_gather_batch(img, P)
         return img, x
+
+    @serialised
+    @torch.no_grad()
+    def assemble(self, slices, coalesced=False, posterior='sample', mark=None, draw_xT=None):
+        """slices of checked requests -> (x_info, c_info, shape) of ONE sampler call: the one place where a feature's entries
+        of x_info / c_info are built, for both doors.  slices: [(Request, first sample, n), ...] -- samples [first, first + n)
+        of each request, side by side in that order.  generate hands over one slice, its rank's; a server one per request of
+        the batch, from 0 on.  What is equal over a batch (a server's key says so) is read from the first request.
+        coalesced -- the slices are a server's batch, several requests side by side: every context is expanded to its samples
+        and mixed contexts are padded to the longest of the batch, the logits of the unconditional rows are there when any
+        request gave an uncond, every sample has its own mask and its own region map.  False, generate's one request: an
+        uncond is handed on as given and padded (`pad_uncond`) only where it is shorter than a mix, a mask stays [1 | n, h, w],
+        the region map is the one map.
+        posterior: the init_posterior of generate.  mark: called behind the context encode and behind the init encode of a
+        slice (generate's timings).  draw_xT: the caller's `shard_xT` -- a server hands over the one of ITS module, so that
+        whoever replaces `serving.shard_xT` (a test that proves that no x_T is drawn) replaces what runs; None: this module's."""
+        from . import control as control_lib
+        from .model_zoo.ddim import is_per_sample
+        from .noise import sample_keys
+        dev = self.net.device
+        r0 = slices[0][0]
+        mixing = r0.weights is not None or r0.regional is not None
+        conds, unconds, xts, keys, masks, x0s, biases, tables, rmaps = ([] for _ in range(9))
+        for r, first, n in slices:
+            if r.regional is not None:          # the references' tokens side by side; ITS table and ITS map (of its own size)
+                c, z, tab = self.encode_regions(r.image, r.regional[1], n)
+                tables.append(tab)
+                rmaps.extend([r.regional[0]] * n)
+            elif r.weights is not None:         # several references: ITS tokens and ITS row of logits
+                c, z, kb = self.encode_references(r.image, r.weights, n)
+                biases.append(kb)
+            elif not image_io.wants_ingest(r.image) and r.image.shape[0] > 1:
+                # one reference image PER SAMPLE (SURVEY 8(d): the "+737 GFLOP/img" variant): SeeCoder is run once per image
+                # (its decoder MHA attends across the batch axis, seecoder.py:70,83 -- a batch of images would mix them)
+                if r.image.shape[0] != n:
+                    raise ValueError(f"{r.image.shape[0]} reference images for {n} local samples")
+                pairs = [self.encode_reference(r.image[i:i + 1].to(dev), 1) for i in range(n)]
+                c, z = torch.cat([c for c, _ in pairs]), torch.cat([z for _, z in pairs])
+            else:
+                c, z = self.encode_reference(self.ingest(r.image) if image_io.wants_ingest(r.image) else r.image.to(dev), n)
+            conds.append(c)
+            if r.uncond is None:
+                unconds.append(z)
+            else:
+                unconds.append(r.uncond.to(dev).to(c.dtype).expand(n, -1, -1) if coalesced else r.uncond)
+            if mark:
+                mark()
+            key = torch.from_numpy(sample_keys(r.seed, first, n))      # sample j of the request is keyed (seed, j), int64 [n, 2]
+            keys.append(key)
+            if r.init is None:                  # ITS x_T stream, drawn once for the whole request (CPU generator)
+                xts.append((draw_xT or shard_xT)(r.n, r.height, r.width, r.seed, 0, 1)[first:first + n])
+                continue
+            start = self.init_latent(r.init, r.height, r.width, r.steps, r.strength, key, posterior, want_x0=r.mask is not None)
+            xts.append(start[0])                # ... or ITS picture, noised under ITS keys
+            if r.mask is not None:              # ... and ITS mask over ITS clean latent
+                x0s.append(start[2])
+                m = self.mask_grid(r.mask, r.height, r.width, n=None if coalesced else n)
+                masks.append(m[:1].expand(n, -1, -1) if coalesced else m)
+            if mark:
+                mark()
+        ubias = None
+        if coalesced and mixing and r0.regional is None:
+            # contexts of different lengths: padded to the longest of the batch with zero tokens at -inf
+            nk = max(int(t.shape[1]) for t in conds + unconds)      # (an uncond longer than every mix is padded to as well)
+            ubiases = []
+            for i, (c, u, kb) in enumerate(zip(conds, unconds, biases)):
+                conds[i], biases[i] = self.pad_context(c, kb, nk)
+                ub = torch.zeros((u.shape[0], u.shape[1]), dtype=torch.float32, device=u.device)
+                unconds[i], ub = self.pad_context(u, ub, nk)
+                ubiases.append(ub)
+            if any(r.uncond is not None for r, _, _ in slices):
+                ubias = torch.cat(ubiases)
+        elif not coalesced and mixing and r0.uncond is not None and r0.uncond.shape[1] != conds[0].shape[1]:
+            n = slices[0][2]
+            unconds[0], ubias = self.pad_uncond(r0.uncond.to(dev).to(conds[0].dtype), conds[0][:, :, 0])
+            if unconds[0].shape[0] == 1 and n > 1:
+                unconds[0], ubias = unconds[0].expand(n, -1, -1), ubias.expand(n, -1)
+        xT = torch.cat(xts).to(dev)
+        x_info = {'type': 'image', 'xt': xT}
+        if r0.init is not None:
+            x_info['xt_steps'] = r0.init_k       # equal over a batch: part of the key
+        if r0.device_noise:
+            x_info['noise_key'] = torch.cat(keys).to(dev)
+        if r0.mask is not None:
+            x_info.update(mask=torch.cat(masks).contiguous(), x0_keep=torch.cat(x0s), keep_key=torch.cat(keys).to(dev))
+        # a scale per sample: a vector given to generate, or a mixed server's batch (its scale-1 key keeps the batch without
+        # CFG); else one scale stays the Python number it was given as
+        per_sample = is_per_sample(r0.scale) or (bool(r0.mixed) and float(r0.scale) != 1.0)
+        scale = r0.scale
+        if per_sample:                          # fp32 [N]: each sample its request's scale, or its own entry of it
+            rows = [torch.as_tensor(r.scale).detach().to(device='cpu', dtype=torch.float32).reshape(-1) for r, _, _ in slices]
+            scale = torch.cat([v.expand(r.n)[f:f + n] for v, (r, f, n) in zip(rows, slices)])
+        c_info = {'type': 'image', 'conditioning': torch.cat(conds), 'unconditional_conditioning': torch.cat(unconds),
+                  'unconditional_guidance_scale': scale}
+        if r0.regional is not None:             # (equal numbers of references over a batch: the key says so, nothing to pad)
+            c_info['region_bias'], c_info['region_map'] = torch.cat(tables), (rmaps if coalesced else r0.regional[0])
+            if ubias is not None:
+                c_info['unconditional_region_bias'] = ubias[:, None].expand(-1, c_info['region_bias'].shape[1], -1)
+        elif r0.weights is not None:
+            c_info['key_bias'] = torch.cat(biases)
+            if ubias is not None:
+                c_info['unconditional_key_bias'] = ubias
+        if r0.control is not None:
+            # a mixed server's batch: one hint per sample [N,3,H,W], every request's picture ingested on its own (uint8
+            # pictures may differ in source size) and repeated over the request's samples; else the one hint (or hints) given
+            def hint(r):
+                return self.control_hint(r.control, r.height, r.width, r.control_preprocess, r.control_thresholds or (100, 200))
+            c_info['control'] = torch.cat([hint(r).expand(n, -1, -1, -1) for r, _, n in slices]) if r0.mixed else hint(r0)
+        if r0.ctl is not None:      # each sample its own rows of the table (layers, steps, cond_only are equal over a batch)
+            strengths = [float(v) for r, f, n in slices for v in r.ctl[0][f:f + n]]
+            tab = control_lib.scale_table(strengths, r0.ctl[1], len(strengths), 2 if per_sample or float(r0.scale) != 1.0 else 1,
+                                          r0.ctl[3])
+            c_info['control_scale'], c_info['control_steps'] = torch.from_numpy(tab).to(dev), r0.ctl[2]
+        if r0.rescale is not None:  # each sample its own phi
+            c_info['guidance_rescale'] = torch.from_numpy(np.concatenate([r.rescale[f:f + n] for r, f, n in slices]))
+        return x_info, c_info, list(xT.shape)
