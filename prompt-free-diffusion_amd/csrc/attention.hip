@@ -25,7 +25,7 @@
 //   * the accumulator is rescaled only when some row of the wave actually raised its running max
 //     (exact: alpha == 1 otherwise).
 // Per tile per wave: 2*DQK/16 + 4*DV/32 MFMAs (DQK = D rounded to 16, DV = D rounded to 32).
-#include <stdlib.h>
+#include <type_traits>
 
 #include "pfd_common.h"
 #include "attention_params.h"
@@ -295,97 +295,56 @@ __global__ __launch_bounds__(256, 1) void attention512_kernel(const AttnParams p
   }
 }
 
-static int launch512(const AttnParams& p, hipStream_t s) {
-  if (p.H != 1 || p.Nk % 32 != 0) return PFD_ESHAPE;
-  const bool prof = pfd_prof_on();
-  if (prof)
-    pfd_prof_begin(8, 4.0 * p.B * (double)p.Nq * p.Nk * 512, 2.0 * p.B * 512 * (2.0 * p.Nq + 2.0 * p.Nk), s);
-  // PFD_ATTN512_SLICES: 2 (default since round 4) or 4 -- two 256-column slices recompute QK^T twice instead of four times
-  // and keep 128 accumulator registers per wave in AGPRs (256 + 129 registers, no scratch): 0.363 vs 0.547 ms at the C2
-  // shape, 1.39 vs 1.61 ms at 96^2 (profiles/r03_k18_vae_attention512.log).  One 512-column slice (256 accumulator
-  // registers) crashes hipcc 7.2's register allocator, so it is not instantiated.  Read per launch (once per decoded
-  // batch), so the GPU suite exercises both instantiations in one process.
-  const char* nsl_env = getenv("PFD_ATTN512_SLICES");
-  const int nsl = nsl_env && atoi(nsl_env) == 4 ? 4 : 2;
-  dim3 grid(((p.Nq + 127) / 128) * nsl * p.B);
-  if (nsl == 2) hipLaunchKernelGGL(attention512_kernel<2>, grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(attention512_kernel<4>, grid, dim3(256), 0, s, p);
-  if (prof) pfd_prof_end(s);
-  return pfd_check_launch("pfd_attention_f16");
+// One launch of a (D, waves) build of the kernel text over the caller's parameter block
+template <int D, int NWAVES, bool PV16, bool FOLD, class P>
+void launch2(const P& p, dim3 grid, hipStream_t s) {
+  if constexpr (std::is_same_v<P, AttnParamsKB>)
+    hipLaunchKernelGGL((attention_kbias_kernel<D, NWAVES, PV16, FOLD>), grid, dim3(64 * NWAVES), 0, s, p);
+  else if constexpr (std::is_same_v<P, AttnParamsRB>)
+    hipLaunchKernelGGL((attention_rbias_kernel<D, NWAVES, PV16, FOLD>), grid, dim3(64 * NWAVES), 0, s, p);
+  else
+    hipLaunchKernelGGL((attention2_kernel<D, NWAVES, PV16, FOLD>), grid, dim3(64 * NWAVES), 0, s, p);
 }
 
-// PFD_ATTN_FORCE8=1 takes the 8-wave form for every d = 40 problem (test hook: selftest --attn, tools/cpu_emu).
-static bool attn_force8() {
-  static const bool f = getenv("PFD_ATTN_FORCE8") && atoi(getenv("PFD_ATTN_FORCE8")) != 0;
-  return f;
-}
-
-template <int D>
-int launch(const AttnParams& p, hipStream_t s) {
-  const bool prof = pfd_prof_on();
-  if (prof)
-    pfd_prof_begin(8, 4.0 * p.B * p.H * (double)p.Nq * p.Nk * D,
-                   2.0 * p.B * p.H * D * (2.0 * p.Nq + 2.0 * p.Nk), s);
-  // 8-wave blocks pay when a block has many queries to amortise the staging over and the grid still fills the chip twice
-  if constexpr (D == 40) {
-    // round 6: the software-pipelined 64-queries-per-wave kernel (attention3.hip) for self-attention-sized problems (decided on
-    // hardware against the kernel below: 260 vs 284 us at B 8 / 64^2, profiles/r06_bench_attn_*.log; the A/B switch is gone)
-    if (pfd_attention3_takes(p)) {
-      pfd_attention3_launch(p, s);
-      if (prof) pfd_prof_end(s);
-      return pfd_check_launch("pfd_attention_f16");
-    }
-  }
-  const bool big = p.Nq >= 1024 && (long)p.B * p.H * ((p.Nq + 255) / 256) >= 512;
-  const bool w8 = D == 40 && (big || attn_force8());
-  // (round 5: 64-query blocks of two waves for the grids that fill less than the chip -- d = 160 at 16^2 / 8^2 -- measured
-  //  the same or slightly slower, profiles/r05_e2e_ab_candidates.log)
-  const int qb = w8 ? 256 : 128;
-  dim3 grid(((p.Nq + qb - 1) / qb) * p.H * p.B);
-  if constexpr (D == 40) {
-    // 8 waves: PV on 16x16x32 + the maximum folded into the QK^T MFMA (the 4-wave PV16 build spills 24 bytes at 128 VGPRs)
-    if (w8) hipLaunchKernelGGL((attention2_kernel<D, 8, true, true>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((attention2_kernel<D, 4, false>), grid, dim3(256), 0, s, p);
+// The class the plan chose at head dim D.  Only the builds attn_plan() can name are instantiated: attention3_kernel, d = 96 and
+// d = 512 for the plain block only, no 8-wave build for the block with a row per region.
+template <int D, class P>
+void launch_class(const P& p, const AttnPlan& pl, dim3 grid, hipStream_t s) {
+  constexpr bool plain = std::is_same_v<P, AttnParams>, regions = std::is_same_v<P, AttnParamsRB>;
+  if constexpr (!plain && (D == 96 || D == 512)) {
+    // (never reached: the plan declines these)
+  } else if constexpr (D == 512) {
+    if (pl.slices == 2) hipLaunchKernelGGL(attention512_kernel<2>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(attention512_kernel<4>, grid, dim3(256), 0, s, p);
   } else {
-    hipLaunchKernelGGL((attention2_kernel<D, 4, false>), grid, dim3(256), 0, s, p);
+    if constexpr (D == 40 && plain)
+      if (pl.cls == ATTN_A3) return pfd_attention3_launch(p, grid, s);
+    if constexpr (D == 40 && !regions)
+      if (pl.cls == ATTN_W8) return launch2<D, 8, true, true>(p, grid, s);
+    launch2<D, 4, false, false>(p, grid, s);
   }
-  if (prof) pfd_prof_end(s);
-  return pfd_check_launch("pfd_attention_f16");
 }
 
-// pfd_attention_kbias_f16: launch<D>'s rule without attention3_kernel (which has no key-logit operand and is never taken)
-template <int D>
-int launch_kbias(const AttnParamsKB& p, hipStream_t s) {
+// The launcher of the three entry points: plan, one profiling bracket, one grid, the kernel, the launch check under `label`
+template <class P>
+int launch(const P& p, const char* label, hipStream_t s) {
+  constexpr AttnOperand op = std::is_same_v<P, AttnParamsKB> ? ATTN_KBIAS : std::is_same_v<P, AttnParamsRB> ? ATTN_RBIAS : ATTN_PLAIN;
+  const AttnPlan pl = attn_plan(p.B, p.H, p.Nq, p.Nk, p.D, op, attn_hooks(p.D));
+  if (pl.rc != PFD_OK) return pl.rc;
   const bool prof = pfd_prof_on();
   if (prof)
-    pfd_prof_begin(8, 4.0 * p.B * p.H * (double)p.Nq * p.Nk * D,
-                   2.0 * p.B * p.H * D * (2.0 * p.Nq + 2.0 * p.Nk), s);
-  const bool big = p.Nq >= 1024 && (long)p.B * p.H * ((p.Nq + 255) / 256) >= 512;
-  const bool w8 = D == 40 && (big || attn_force8());
-  const int qb = w8 ? 256 : 128;
-  dim3 grid(((p.Nq + qb - 1) / qb) * p.H * p.B);
-  if constexpr (D == 40) {
-    if (w8) hipLaunchKernelGGL((attention_kbias_kernel<D, 8, true, true>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((attention_kbias_kernel<D, 4, false>), grid, dim3(256), 0, s, p);
-  } else {
-    hipLaunchKernelGGL((attention_kbias_kernel<D, 4, false>), grid, dim3(256), 0, s, p);
+    pfd_prof_begin(8, 4.0 * p.B * p.H * (double)p.Nq * p.Nk * p.D,
+                   2.0 * p.B * p.H * p.D * (2.0 * p.Nq + 2.0 * p.Nk), s);
+  dim3 grid(((p.Nq + pl.qb - 1) / pl.qb) * pl.slices * p.H * p.B);
+  switch (p.D) {   // (the plan has declined every other D)
+    case 40: launch_class<40>(p, pl, grid, s); break;
+    case 80: launch_class<80>(p, pl, grid, s); break;
+    case 96: launch_class<96>(p, pl, grid, s); break;
+    case 160: launch_class<160>(p, pl, grid, s); break;
+    case 512: launch_class<512>(p, pl, grid, s); break;
   }
   if (prof) pfd_prof_end(s);
-  return pfd_check_launch("pfd_attention_kbias_f16");
-}
-
-// pfd_attention_rbias_f16: launch_kbias<D>'s rule without the folded 8-wave build (not compiled with a row per region): the
-// 4-wave d = 40 build takes those shapes too
-template <int D>
-int launch_rbias(const AttnParamsRB& p, hipStream_t s) {
-  const bool prof = pfd_prof_on();
-  if (prof)
-    pfd_prof_begin(8, 4.0 * p.B * p.H * (double)p.Nq * p.Nk * D,
-                   2.0 * p.B * p.H * D * (2.0 * p.Nq + 2.0 * p.Nk), s);
-  dim3 grid(((p.Nq + 127) / 128) * p.H * p.B);
-  hipLaunchKernelGGL((attention_rbias_kernel<D, 4, false>), grid, dim3(256), 0, s, p);
-  if (prof) pfd_prof_end(s);
-  return pfd_check_launch("pfd_attention_rbias_f16");
+  return pfd_check_launch(label);
 }
 
 int check_desc(const PfdAttnDesc* d) {
@@ -419,13 +378,7 @@ extern "C" int pfd_attention_kbias_f16(const PfdAttnDesc* d, const float* kbias,
   p.kbias = kbias;
   p.kb_bs = kb_bs;
   p.inv_scale_log2 = 1.0f / p.scale_log2;
-  hipStream_t s = (hipStream_t)stream;
-  switch (d->D) {
-    case 40: return launch_kbias<40>(p, s);
-    case 80: return launch_kbias<80>(p, s);
-    case 160: return launch_kbias<160>(p, s);
-    default: return PFD_ESHAPE;
-  }
+  return launch(p, "pfd_attention_kbias_f16", (hipStream_t)stream);
 }
 
 extern "C" int pfd_attention_rbias_f16(const PfdAttnDesc* d, const float* rbias, int64_t rb_rs, int64_t rb_bs, int nr,
@@ -449,26 +402,12 @@ extern "C" int pfd_attention_rbias_f16(const PfdAttnDesc* d, const float* rbias,
   // (the start value must be finite as a raw score, 2^100 / (scale log2 e) < 2^128, and far below every real score; the header
   //  states the range it promises, 2^-28 < scale log2 e < 2^10 -- the head sizes served have scale = d^-1/2)
   if (!(p.scale_log2 > 0x1p-28f) || !(p.scale_log2 < 0x1p10f)) return PFD_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  switch (d->D) {
-    case 40: return launch_rbias<40>(p, s);
-    case 80: return launch_rbias<80>(p, s);
-    case 160: return launch_rbias<160>(p, s);
-    default: return PFD_ESHAPE;
-  }
+  return launch(p, "pfd_attention_rbias_f16", (hipStream_t)stream);
 }
 
 extern "C" int pfd_attention_f16(const PfdAttnDesc* d, pfd_stream_t stream) {
   if (const int rc = check_desc(d)) return rc;
   AttnParams p;
   fill_params(d, p);
-  hipStream_t s = (hipStream_t)stream;
-  switch (d->D) {
-    case 40: return launch<40>(p, s);
-    case 80: return launch<80>(p, s);
-    case 96: return launch<96>(p, s);
-    case 160: return launch<160>(p, s);
-    case 512: return launch512(p, s);
-    default: return PFD_ESHAPE;
-  }
+  return launch(p, "pfd_attention_f16", (hipStream_t)stream);
 }

@@ -26,8 +26,6 @@
 // The translation unit is compiled with -fno-honor-nans: without it every fmaxf on an MFMA result is preceded by a
 // canonicalising v_max_f32 x, x (53 instead of 23 instructions for the 32-value maximum of a tile).  No NaN can arise here.
 #pragma once
-#include <stdlib.h>
-
 #include "attention_params.h"
 
 namespace {
@@ -309,15 +307,6 @@ __global__ __launch_bounds__(256, 2) void attention3_kernel(const AttnParams p) 
 
 }  // namespace
 
-bool pfd_attention3_takes(const AttnParams& p) {
-  // whole 64-key tiles, at least two of them; enough 256-query blocks to give every CU one
-  // (PFD_ATTN3_FORCE=1: test hook -- selftest --attn, tools/cpu_emu -- that takes small grids too)
-  static const bool force = getenv("PFD_ATTN3_FORCE") && atoi(getenv("PFD_ATTN3_FORCE")) != 0;
-  if (p.D != 40 || p.Nk % 64 != 0 || p.Nk < 128) return false;
-  return force || (p.Nq >= 256 && (long)p.B * p.H * ((p.Nq + 255) / 256) >= 256);
-}
-
-void pfd_attention3_launch(const AttnParams& p, hipStream_t s) {
-  dim3 grid(((p.Nq + 255) / 256) * p.H * p.B);
+void pfd_attention3_launch(const AttnParams& p, dim3 grid, hipStream_t s) {
   hipLaunchKernelGGL(attention3_kernel, grid, dim3(256), 0, s, p);
 }

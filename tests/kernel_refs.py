@@ -229,22 +229,27 @@ ATTN_CLASSES = ("w4", "w8", "a3", "d80", "d96", "d160", "d512_2", "d512_4")
 ATTN_FOLDED = ("w8", "a3")          # Q' = fp16(q * scale * log2 e), softmax as exp2 of the raw products
 
 
-def attention_kernel_class(B, H, Nq, Nk, D, slices=2):
-    """which kernel pfd_attention_f16 launches: csrc/attention.hip launch<D>() (the `big` / `w8` lines), launch512() and the
-    switch of pfd_attention_f16, and pfd_attention3_takes() at the end of csrc/attention3_kernel.h, restated without the
-    process-static test hooks.  None: PFD_ESHAPE."""
+# the class of every kernel `emu_attn --dispatch` can record (tests/golden/attention_dispatch.txt)
+ATTN_KERNEL_CLASS = {"attention3_kernel": "a3", "attention512_kernel<2>": "d512_2", "attention512_kernel<4>": "d512_4"}
+for _k in ("attention2_kernel", "attention_kbias_kernel", "attention_rbias_kernel"):
+    ATTN_KERNEL_CLASS.update({f"{_k}<40, 4, false, false>": "w4", f"{_k}<40, 8, true, true>": "w8", f"{_k}<80, 4, false, false>": "d80",
+                              f"{_k}<96, 4, false, false>": "d96", f"{_k}<160, 4, false, false>": "d160"})
+
+
+def attention_kernel_class(B, H, Nq, Nk, D, slices=2, operand=None):
+    """which kernel pfd_attention_f16 (operand None), pfd_attention_kbias_f16 ("kbias") or pfd_attention_rbias_f16 ("rbias")
+    launches: attn_plan() of csrc/attention_params.h restated without the process-static test hooks, and held to it line by
+    line of the pinned dry run (tests/test_attention_kernels_cpu.py).  None: PFD_ESHAPE."""
     if D == 512:
-        return f"d512_{4 if slices == 4 else 2}" if H == 1 and Nk % 32 == 0 else None
-    if D in (80, 96, 160):
-        return f"d{D}"
-    if D != 40:
+        return f"d512_{4 if slices == 4 else 2}" if not operand and H == 1 and Nk % 32 == 0 else None
+    if D not in (40, 80, 160) and (D != 96 or operand):
         return None
+    if D != 40:
+        return f"d{D}"
     blocks = B * H * ((Nq + 255) // 256)
-    if Nk % 64 == 0 and Nk >= 128 and Nq >= 256 and blocks >= 256:
+    if not operand and Nk % 64 == 0 and Nk >= 128 and Nq >= 256 and blocks >= 256:
         return "a3"
-    if Nq >= 1024 and blocks >= 512:
-        return "w8"
-    return "w4"
+    return "w8" if operand != "rbias" and Nq >= 1024 and blocks >= 512 else "w4"
 
 
 # (B, H, Nq, Nk, D, layout, spike); layouts: dense | fused_qk | vt_offset | shared_kv (attention_problem)

@@ -1,6 +1,6 @@
 """Helpers of the reference-mixing tests (tests/test_refmix_*.py): the cases and key-logit patterns of the kernel tests, the fp64
 weighted attention on torch tensors in the layouts the kernels take (pinned to lib/refmix.weighted_attention, the numpy
-specification, by tests/test_refmix_cpu.py), the dispatcher of pfd_attention_kbias_f16 restated, and the per-element bound.
+specification, by tests/test_refmix_cpu.py) and the per-element bound.
 Imports kernel_refs; changes nothing in it."""
 import functools
 import math
@@ -29,13 +29,8 @@ def case_id(c):
 
 
 def kbias_kernel_class(B, H, Nq, Nk, D):
-    """which kernel pfd_attention_kbias_f16 launches: launch_kbias<D>() of csrc/attention.hip = launch<D>() without
-    attention3_kernel.  None: PFD_ESHAPE."""
-    if D in (80, 160):
-        return f"d{D}"
-    if D != 40:
-        return None
-    return "w8" if Nq >= 1024 and B * H * ((Nq + 255) // 256) >= 512 else "w4"
+    """which kernel pfd_attention_kbias_f16 launches.  None: PFD_ESHAPE."""
+    return KR.attention_kernel_class(B, H, Nq, Nk, D, operand="kbias")
 
 
 def kb_stride(Nk):

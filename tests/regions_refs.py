@@ -1,6 +1,6 @@
 """Helpers of the regional-mixing tests (tests/test_regions_*.py): the cases, logit tables and region maps of the kernel tests, the
 fp64 regional attention on torch tensors in the layouts the kernels take (pinned to lib/regions.regional_attention, the numpy
-specification, by tests/test_regions_cpu.py), the dispatcher of pfd_attention_rbias_f16 restated, and operands that tell every
+specification, by tests/test_regions_cpu.py), and operands that tell every
 named mutant of lib/regions.py from the specification.  Imports kernel_refs and refmix_refs; changes nothing in them.
 
 The bound is refmix_refs.kbias_bound with Bmax and T taken over the table: the accumulator start is the same construction (the
@@ -34,8 +34,8 @@ case_id = RR.case_id
 
 
 def rbias_kernel_class(B, H, Nq, Nk, D):
-    """which kernel pfd_attention_rbias_f16 launches: launch_rbias<D>() of csrc/attention.hip.  None: PFD_ESHAPE."""
-    return {40: "w4", 80: "d80", 160: "d160"}.get(D)
+    """which kernel pfd_attention_rbias_f16 launches.  None: PFD_ESHAPE."""
+    return KR.attention_kernel_class(B, H, Nq, Nk, D, operand="rbias")
 
 
 @functools.lru_cache(maxsize=None)

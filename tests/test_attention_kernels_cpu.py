@@ -2,6 +2,9 @@
 behind pfd_attention_f16 against -- pinned to the oracle's attention cores (oracle/pfd_oracle.py cross_attention / vae_attn),
 checked to index strided operands like dense ones, to stay far inside the GPU bound in their own arithmetic, to read no
 poisoned element, and to be run on operands that tell wrong variants of the kernel from the right one."""
+import os
+import re
+
 import pytest
 import torch
 
@@ -112,6 +115,31 @@ def test_cases_cover_every_dispatch_class():
     assert KR.attention_kernel_class(16, 8, 1023, 148, 40) == "w4" and KR.attention_kernel_class(16, 8, 1024, 148, 40) == "w8"
     assert KR.attention_kernel_class(1, 2, 8, 8, 64) is None and KR.attention_kernel_class(1, 2, 8, 32, 512) is None
     assert KR.attention_kernel_class(1, 1, 8, 40, 512) is None
+
+
+def test_restated_rule_names_the_kernel_of_every_pinned_launch():
+    """the hook-free section of tests/golden/attention_dispatch.txt (the dry run of the three entry points that
+    tests/test_cpu_emulation.py pins to the host code): KR.attention_kernel_class names the class of the recorded kernel on
+    every line that launches, and None on every line declined with PFD_ESHAPE (-2)"""
+    text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "attention_dispatch.txt")).read()
+    section = text.split("# hooks: ")[1].splitlines()
+    assert section[0] == "none" and len(section) > 300
+    seen = set()
+    for line in section[1:]:
+        m = re.match(r"^(plain|kbias|rbias) (\d+) (\d+) (\d+) (\d+) (\d+)(.*) -> (-?\d+)(?: \| (.+) grid \d+ block \d+)?$", line)
+        assert m, line
+        rc, kernel = int(m.group(8)), m.group(9)
+        assert (rc == 0) == (kernel is not None), line
+        if rc == -1:                                 # PFD_EINVAL: the descriptor checks in front of the rule
+            continue
+        sl = re.search(r"slices=(\d+)", m.group(7))
+        got = KR.attention_kernel_class(*map(int, m.group(2, 3, 4, 5, 6)), slices=int(sl.group(1)) if sl else 2,
+                                        operand=None if m.group(1) == "plain" else m.group(1))
+        assert got == (KR.ATTN_KERNEL_CLASS[kernel] if kernel else None), (line, got)
+        seen.add((m.group(1), got))
+    assert {c for api, c in seen if api == "plain"} == set(KR.ATTN_CLASSES) | {None}
+    assert {c for api, c in seen if api == "kbias"} == {"w4", "w8", "d80", "d160", None}
+    assert {c for api, c in seen if api == "rbias"} == {"w4", "d80", "d160", None}
 
 
 # ------------------------------------------------------------------------------------------------

@@ -124,9 +124,10 @@ def test_torch_reference_is_the_numpy_specification(cls, case, shared):
 
 
 def test_dispatch_restated_tables_and_maps():
-    src = open(os.path.join(REPO, "prompt-free-diffusion_amd", "csrc", "attention.hip")).read()
-    body = src[src.index("int launch_rbias("):src.index("int check_desc(")]
-    assert "attention_rbias_kernel<D, 4, false>" in body and "8, true, true" not in body      # one build per head size, 4 waves
+    # one build per head size, 4 waves: what the entry point launched in the pinned dry run of the host code, under every test hook
+    pinned = open(os.path.join(REPO, "tests", "golden", "attention_dispatch.txt")).read()
+    launched = set(re.findall(r"^rbias .* \| (\S+<.*>) grid", pinned, re.M))
+    assert launched == {f"attention_rbias_kernel<{D}, 4, false, false>" for D in (40, 80, 160)} and pinned.count("# hooks: ") == 4
     for cls, c in GR.ALL_CASES:
         assert GR.rbias_kernel_class(*c) == cls and RR.kbias_kernel_class(*c) == cls       # the bit comparison runs one class
         assert c in RR.KBIAS_CASES[cls]

@@ -4,8 +4,10 @@
 //   usage: emu_attn [--quick] [--w4] [--kbias]     (--w4: the 4-wave d = 40 form; prints one line per case with a checksum of the output bits;
 //                                                    --kbias: pfd_attention_kbias_f16, the per-key logit operand, every kernel class it has)
 //          emu_attn --rbias                        (pfd_attention_rbias_f16, a logit row per region of the query: d = 40, 80, 160)
+//          emu_attn --dispatch FILE                (a dry run of the three entry points: what they decide, one text line per request)
 #include <stdio.h>
 
+#include <functional>
 #include <random>
 #include <string>
 
@@ -30,54 +32,108 @@ static std::vector<h16> rand_h(size_t n, float scale) {
 }
 static int g_fail = 0, g_total = 0;
 
-static void run_case(int B, int H, int Nq, int Nk, int D, int spike = 0) {
-  const int C = H * D;
-  const long nkp = (Nk + 7) / 8 * 8;
-  auto Q = rand_h((size_t)B * Nq * C, 1.5f), K = rand_h((size_t)B * Nk * C, 1.5f), V = rand_h((size_t)B * Nk * C, 1.f);
-  if (spike > 0 && spike < Nk)   // key `spike` = 4 x query (spike % Nq): the row maximum jumps in the middle of the stream
-    for (int b = 0; b < B; ++b)
-      for (int c = 0; c < C; ++c) K[((size_t)b * Nk + spike) * C + c] = (h16)(4.0f * (float)Q[((size_t)b * Nq + spike % Nq) * C + c]);
-  std::vector<h16> Vt((size_t)C * B * nkp, (h16)0.f), O((size_t)B * Nq * C, (h16)-9.f);
-  for (int b = 0; b < B; ++b)
-    for (int j = 0; j < Nk; ++j)
-      for (int c = 0; c < C; ++c) Vt[(size_t)c * B * nkp + (size_t)b * nkp + j] = V[((size_t)b * Nk + j) * C + c];
+// the dense descriptor of the drivers: channels-last Q / K / O, V^T rows of B x (Nk rounded up to 8) keys
+static PfdAttnDesc dense_desc(const void* Q, const void* K, const void* Vt, void* O, int B, int H, int Nq, int Nk, int D) {
+  const long C = (long)H * D, nkp = (Nk + 7) / 8 * 8;
   PfdAttnDesc d;
   memset(&d, 0, sizeof(d));
-  d.Q = Q.data(); d.K = K.data(); d.Vt = Vt.data(); d.O = O.data();
+  d.Q = Q; d.K = K; d.Vt = Vt; d.O = O;
   d.ldq = C; d.ldk = C; d.ldo = C; d.ldvt = (long)B * nkp;
   d.q_bs = (long)Nq * C; d.k_bs = (long)Nk * C; d.o_bs = (long)Nq * C; d.vt_bs = nkp;
   d.B = B; d.H = H; d.Nq = Nq; d.Nk = Nk; d.D = D;
   d.scale = 1.0f / sqrtf((float)D);
-  const int rc = pfd_attention_f16(&d, nullptr);
-  double me = 0, mr = 0;
+  return d;
+}
+
+// One problem: random Q, K, V (drawn from rng in this order; the logits of a case come after them), the padded V^T, the output
+// (preset to -9) and the descriptor.  spike > 0: key `spike` = 4 x query (spike % Nq), the row maximum jumps in the middle of the stream
+struct Problem {
+  const int B, H, Nq, Nk, D, C;
+  std::vector<h16> Q, K, V, Vt, O;
+  PfdAttnDesc d;
+  Problem(int B, int H, int Nq, int Nk, int D, int spike = 0)
+      : B(B), H(H), Nq(Nq), Nk(Nk), D(D), C(H * D), Q(rand_h((size_t)B * Nq * C, 1.5f)), K(rand_h((size_t)B * Nk * C, 1.5f)),
+        V(rand_h((size_t)B * Nk * C, 1.f)), O((size_t)B * Nq * C, (h16)-9.f) {
+    const long nkp = (Nk + 7) / 8 * 8;
+    if (spike > 0 && spike < Nk)
+      for (int b = 0; b < B; ++b)
+        for (int c = 0; c < C; ++c) K[((size_t)b * Nk + spike) * C + c] = (h16)(4.0f * (float)Q[((size_t)b * Nq + spike % Nq) * C + c]);
+    Vt.assign((size_t)C * B * nkp, (h16)0.f);
+    for (int b = 0; b < B; ++b)
+      for (int j = 0; j < Nk; ++j)
+        for (int c = 0; c < C; ++c) Vt[(size_t)c * B * nkp + (size_t)b * nkp + j] = V[((size_t)b * Nk + j) * C + c];
+    d = dense_desc(Q.data(), K.data(), Vt.data(), O.data(), B, H, Nq, Nk, D);
+  }
+};
+
+// softmax(scale Q K^T + ln2 row) V in double precision against p.O (a NaN there, or what a declined call left, is an error); row(b, i): the Nk logits of
+// query i of sample b in log2 units, or no function at all.  Returns the maxima the bounds need: the error, |ref|, |V|, and over
+// the live keys A = sum_e |q'_e k_e|, T = |biased score| (both in log2 units) and |logit|
+struct RefMax { double me = 0, mr = 0, vmax = 0, A = 0, T = 0, Bm = 0; };
+static RefMax reference(const Problem& p, const std::function<const float*(int, int)>& row = nullptr) {
+  const double LOG2E = 1.4426950408889634, LN2 = 0.6931471805599453;
+  const int Nq = p.Nq, Nk = p.Nk, D = p.D, C = p.C;
+  RefMax m;
+  for (auto& x : p.V) m.vmax = std::max(m.vmax, fabs((double)x));
   std::vector<double> s(Nk);
-  for (int b = 0; b < B && rc == 0; ++b)
-    for (int h = 0; h < H; ++h)
+  for (int b = 0; b < p.B; ++b)
+    for (int h = 0; h < p.H; ++h)
       for (int i = 0; i < Nq; ++i) {
+        const float* logit = row ? row(b, i) : nullptr;
         double mx = -1e300;
         for (int j = 0; j < Nk; ++j) {
-          double a = 0;
-          for (int e = 0; e < D; ++e) a += (double)Q[((size_t)b * Nq + i) * C + h * D + e] * (double)K[((size_t)b * Nk + j) * C + h * D + e];
-          s[j] = a * d.scale;
+          double a = 0, aa = 0;
+          for (int e = 0; e < D; ++e) {
+            const double pr = (double)p.Q[((size_t)b * Nq + i) * C + h * D + e] * (double)p.K[((size_t)b * Nk + j) * C + h * D + e];
+            a += pr;
+            aa += fabs(pr);
+          }
+          const double bj = logit ? (double)logit[j] : 0.0;
+          s[j] = a * p.d.scale + bj * LN2;
+          if (bj > -1e300) {
+            m.A = std::max(m.A, aa * p.d.scale * LOG2E);
+            m.T = std::max(m.T, fabs(s[j] * LOG2E));
+            m.Bm = std::max(m.Bm, fabs(bj));
+          }
           mx = std::max(mx, s[j]);
         }
         double den = 0;
         for (int j = 0; j < Nk; ++j) { s[j] = exp(s[j] - mx); den += s[j]; }
         for (int e = 0; e < D; ++e) {
           double o = 0;
-          for (int j = 0; j < Nk; ++j) o += s[j] * (double)V[((size_t)b * Nk + j) * C + h * D + e];
+          for (int j = 0; j < Nk; ++j) o += s[j] * (double)p.V[((size_t)b * Nk + j) * C + h * D + e];
           o /= den;
-          mr = std::max(mr, fabs(o));
-          me = std::max(me, fabs(o - (double)O[((size_t)b * Nq + i) * C + h * D + e]));
+          m.mr = std::max(m.mr, fabs(o));
+          const double got = (double)p.O[((size_t)b * Nq + i) * C + h * D + e];
+          m.me = std::max(m.me, got == got ? fabs(o - got) : 1e30);
         }
       }
-  uint64_t sum = 1469598103934665603ull;   // FNV-1a over the output bits
-  for (auto& x : O) { unsigned short u; memcpy(&u, &x, 2); sum = (sum ^ u) * 1099511628211ull; }
-  const bool ok = rc == 0 && me <= 4e-3 * std::max(1.0, mr);
+  return m;
+}
+
+// the bound of the GPU tests (tests/refmix_refs.py kbias_bound): (3 2^-11 + Nk 2^-25 + 2^-16 + 2 ln2 2^-11 A) vmax for the
+// fp16 P, the fp16 result and, in the folded 8-wave form, the fp16 Q' (A = max sum_e |q'_e k_e| in log2 units), plus
+// 2 ln2 (ceil(D / 16) + 1) 2^-24 (Bmax + T) vmax for the accumulator that starts at the logit (T = max |biased score|)
+static double bias_bound(int Nk, int D, bool folded, double A, double BT, double vmax) {
+  return (3 * ldexp(1.0, -11) + Nk * ldexp(1.0, -25) + ldexp(1.0, -16) + (folded ? 2 * 0.6931471805599453 * ldexp(1.0, -11) * A : 0.0) +
+          2 * 0.6931471805599453 * ((D + 15) / 16 + 1) * ldexp(1.0, -24) * BT) * vmax;
+}
+
+static bool tally(bool ok) {
   ++g_total;
   g_fail += !ok;
-  printf("%s attention B%d H%d Nq%d Nk%d D%d  rc %d  max err %.2e (max |ref| %.2f)  bits %016llx\n", ok ? "ok  " : "FAIL", B, H, Nq, Nk, D, rc, me,
-         mr, (unsigned long long)sum);
+  return ok;
+}
+
+static void run_case(int B, int H, int Nq, int Nk, int D, int spike = 0) {
+  Problem p(B, H, Nq, Nk, D, spike);
+  const int rc = pfd_attention_f16(&p.d, nullptr);
+  const RefMax m = reference(p);
+  uint64_t sum = 1469598103934665603ull;   // FNV-1a over the output bits
+  for (auto& x : p.O) { unsigned short u; memcpy(&u, &x, 2); sum = (sum ^ u) * 1099511628211ull; }
+  const bool ok = tally(rc == 0 && m.me <= 4e-3 * std::max(1.0, m.mr));
+  printf("%s attention B%d H%d Nq%d Nk%d D%d  rc %d  max err %.2e (max |ref| %.2f)  bits %016llx\n", ok ? "ok  " : "FAIL", B, H, Nq, Nk, D, rc, m.me,
+         m.mr, (unsigned long long)sum);
   fflush(stdout);
 }
 
@@ -85,13 +141,8 @@ static void run_case(int B, int H, int Nq, int Nk, int D, int spike = 0) {
 // softmax in double precision.  pattern 0: two references 0.7 / 0.3; 1: sample b keeps 1 + b % 2 halves, the rest is -inf (whole
 // trailing tiles masked); 2: -inf on keys 64..127 and on every fifth key, key 0 finite, random logits in [-12, 0] elsewhere
 static void run_case_kbias(int B, int H, int Nq, int Nk, int D, int pattern) {
-  const int C = H * D;
-  const long nkp = (Nk + 7) / 8 * 8, kb_bs = (Nk + 3) / 4 * 4 + 4;
-  auto Q = rand_h((size_t)B * Nq * C, 1.5f), K = rand_h((size_t)B * Nk * C, 1.5f), V = rand_h((size_t)B * Nk * C, 1.f);
-  std::vector<h16> Vt((size_t)C * B * nkp, (h16)0.f), O((size_t)B * Nq * C, (h16)-9.f);
-  for (int b = 0; b < B; ++b)
-    for (int j = 0; j < Nk; ++j)
-      for (int c = 0; c < C; ++c) Vt[(size_t)c * B * nkp + (size_t)b * nkp + j] = V[((size_t)b * Nk + j) * C + c];
+  Problem p(B, H, Nq, Nk, D);
+  const long kb_bs = (Nk + 3) / 4 * 4 + 4;
   float* kb = (float*)aligned_alloc(16, sizeof(float) * B * kb_bs);
   std::uniform_real_distribution<float> u(-12.f, 0.f);
   const int half = Nk / 2;
@@ -105,61 +156,14 @@ static void run_case_kbias(int B, int H, int Nq, int Nk, int D, int pattern) {
       }
       kb[b * kb_bs + j] = v;
     }
-  PfdAttnDesc d;
-  memset(&d, 0, sizeof(d));
-  d.Q = Q.data(); d.K = K.data(); d.Vt = Vt.data(); d.O = O.data();
-  d.ldq = C; d.ldk = C; d.ldo = C; d.ldvt = (long)B * nkp;
-  d.q_bs = (long)Nq * C; d.k_bs = (long)Nk * C; d.o_bs = (long)Nq * C; d.vt_bs = nkp;
-  d.B = B; d.H = H; d.Nq = Nq; d.Nk = Nk; d.D = D;
-  d.scale = 1.0f / sqrtf((float)D);
-  const int rc = pfd_attention_kbias_f16(&d, kb, kb_bs, nullptr);
-  // the bound of the GPU tests (tests/refmix_refs.py kbias_bound): (3 2^-11 + Nk 2^-25 + 2^-16 + 2 ln2 2^-11 A) vmax for the
-  // fp16 P, the fp16 result and, in the folded 8-wave form, the fp16 Q' (A = max sum_e |q'_e k_e| in log2 units), plus
-  // 2 ln2 (ceil(D / 16) + 1) 2^-24 (Bmax + T) vmax for the accumulator that starts at the logit (T = max |biased score|)
-  double me = 0, mr = 0, vmax = 0, Amax = 0, Tmax = 0, Bmax = 0;
-  const double LOG2E = 1.4426950408889634;
-  for (auto& x : V) vmax = std::max(vmax, fabs((double)x));
-  std::vector<double> s(Nk);
-  for (int b = 0; b < B && rc == 0; ++b)
-    for (int h = 0; h < H; ++h)
-      for (int i = 0; i < Nq; ++i) {
-        double mx = -1e300;
-        for (int j = 0; j < Nk; ++j) {
-          double a = 0, aa = 0;
-          for (int e = 0; e < D; ++e) {
-            const double pr = (double)Q[((size_t)b * Nq + i) * C + h * D + e] * (double)K[((size_t)b * Nk + j) * C + h * D + e];
-            a += pr;
-            aa += fabs(pr);
-          }
-          const double bj = (double)kb[b * kb_bs + j];
-          s[j] = a * d.scale + bj * 0.6931471805599453;
-          if (bj > -1e300) {
-            Amax = std::max(Amax, aa * d.scale * LOG2E);
-            Tmax = std::max(Tmax, fabs(s[j] * LOG2E));
-            Bmax = std::max(Bmax, fabs(bj));
-          }
-          mx = std::max(mx, s[j]);
-        }
-        double den = 0;
-        for (int j = 0; j < Nk; ++j) { s[j] = exp(s[j] - mx); den += s[j]; }
-        for (int e = 0; e < D; ++e) {
-          double o = 0;
-          for (int j = 0; j < Nk; ++j) o += s[j] * (double)V[((size_t)b * Nk + j) * C + h * D + e];
-          o /= den;
-          mr = std::max(mr, fabs(o));
-          const double got = (double)O[((size_t)b * Nq + i) * C + h * D + e];
-          me = std::max(me, got == got ? fabs(o - got) : 1e30);
-        }
-      }
+  const int rc = pfd_attention_kbias_f16(&p.d, kb, kb_bs, nullptr);
+  const RefMax m = reference(p, [&](int b, int) { return kb + b * kb_bs; });
   free(kb);
-  const bool folded = D == 40 && getenv("PFD_ATTN_FORCE8") && atoi(getenv("PFD_ATTN_FORCE8")) != 0;
-  const double bound = (3 * ldexp(1.0, -11) + Nk * ldexp(1.0, -25) + ldexp(1.0, -16) + (folded ? 2 * 0.6931471805599453 * ldexp(1.0, -11) * Amax : 0.0) +
-                        2 * 0.6931471805599453 * ((D + 15) / 16 + 1) * ldexp(1.0, -24) * (Bmax + Tmax)) * vmax;
-  const bool ok = rc == 0 && me <= bound;
-  ++g_total;
-  g_fail += !ok;
+  const bool folded = attn_plan(B, H, Nq, Nk, D, ATTN_KBIAS, attn_hooks(D)).cls == ATTN_W8;   // the class with an fp16 Q'
+  const double bound = bias_bound(Nk, D, folded, m.A, m.Bm + m.T, m.vmax);
+  const bool ok = tally(rc == 0 && m.me <= bound);
   printf("%s attention kbias pattern %d B%d H%d Nq%d Nk%d D%d  rc %d  max err %.2e = %.3f of the bound (max |ref| %.2f)\n", ok ? "ok  " : "FAIL",
-         pattern, B, H, Nq, Nk, D, rc, me, me / bound, mr);
+         pattern, B, H, Nq, Nk, D, rc, m.me, m.me / bound, m.mr);
   fflush(stdout);
 }
 
@@ -168,13 +172,8 @@ static void run_case_kbias(int B, int H, int Nq, int Nk, int D, int pattern) {
 // tiles), row 2 masks keys 64 .. 127 (a middle tile) and every fifth key, rows 3 .. are random logits in [-12, 0].  Regions
 // change every five queries (inside a wave's 32) and start at b, so the samples differ; shared: one map for the batch (qr_bs = 0).
 static void run_case_rbias(int B, int H, int Nq, int Nk, int D, int nr, bool shared) {
-  const int C = H * D;
-  const long nkp = (Nk + 7) / 8 * 8, rb_rs = (Nk + 3) / 4 * 4 + 4, rb_bs = nr * rb_rs;
-  auto Q = rand_h((size_t)B * Nq * C, 1.5f), K = rand_h((size_t)B * Nk * C, 1.5f), V = rand_h((size_t)B * Nk * C, 1.f);
-  std::vector<h16> Vt((size_t)C * B * nkp, (h16)0.f), O((size_t)B * Nq * C, (h16)-9.f);
-  for (int b = 0; b < B; ++b)
-    for (int j = 0; j < Nk; ++j)
-      for (int c = 0; c < C; ++c) Vt[(size_t)c * B * nkp + (size_t)b * nkp + j] = V[((size_t)b * Nk + j) * C + c];
+  Problem p(B, H, Nq, Nk, D);
+  const long rb_rs = (Nk + 3) / 4 * 4 + 4, rb_bs = nr * rb_rs;
   float* rb = (float*)aligned_alloc(16, sizeof(float) * B * rb_bs);
   std::uniform_real_distribution<float> u(-12.f, 0.f);
   const int half = Nk / 2;
@@ -193,54 +192,14 @@ static void run_case_rbias(int B, int H, int Nq, int Nk, int D, int nr, bool sha
   std::vector<uint8_t> qr((size_t)B * Nq);
   for (int b = 0; b < B; ++b)
     for (int i = 0; i < Nq; ++i) qr[(size_t)b * Nq + i] = (uint8_t)((i / 5 + (shared ? 0 : b)) % nr);
-  PfdAttnDesc d;
-  memset(&d, 0, sizeof(d));
-  d.Q = Q.data(); d.K = K.data(); d.Vt = Vt.data(); d.O = O.data();
-  d.ldq = C; d.ldk = C; d.ldo = C; d.ldvt = (long)B * nkp;
-  d.q_bs = (long)Nq * C; d.k_bs = (long)Nk * C; d.o_bs = (long)Nq * C; d.vt_bs = nkp;
-  d.B = B; d.H = H; d.Nq = Nq; d.Nk = Nk; d.D = D;
-  d.scale = 1.0f / sqrtf((float)D);
-  const int rc = pfd_attention_rbias_f16(&d, rb, rb_rs, rb_bs, nr, qr.data(), shared ? 0 : Nq, nullptr);
-  // the bound of the GPU tests (tests/refmix_refs.py kbias_bound, unfolded classes), Bmax and T over the table
-  double me = 0, mr = 0, vmax = 0, Tmax = 0, Bmax = 0;
-  const double LOG2E = 1.4426950408889634;
-  for (auto& x : V) vmax = std::max(vmax, fabs((double)x));
-  std::vector<double> s(Nk);
-  for (int b = 0; b < B && rc == 0; ++b)
-    for (int h = 0; h < H; ++h)
-      for (int i = 0; i < Nq; ++i) {
-        const float* row = rb + b * rb_bs + qr[(size_t)(shared ? 0 : b) * Nq + i] * rb_rs;
-        double mx = -1e300;
-        for (int j = 0; j < Nk; ++j) {
-          double a = 0;
-          for (int e = 0; e < D; ++e) a += (double)Q[((size_t)b * Nq + i) * C + h * D + e] * (double)K[((size_t)b * Nk + j) * C + h * D + e];
-          const double bj = (double)row[j];
-          s[j] = a * d.scale + bj * 0.6931471805599453;
-          if (bj > -1e300) {
-            Tmax = std::max(Tmax, fabs(s[j] * LOG2E));
-            Bmax = std::max(Bmax, fabs(bj));
-          }
-          mx = std::max(mx, s[j]);
-        }
-        double den = 0;
-        for (int j = 0; j < Nk; ++j) { s[j] = exp(s[j] - mx); den += s[j]; }
-        for (int e = 0; e < D; ++e) {
-          double o = 0;
-          for (int j = 0; j < Nk; ++j) o += s[j] * (double)V[((size_t)b * Nk + j) * C + h * D + e];
-          o /= den;
-          mr = std::max(mr, fabs(o));
-          const double got = (double)O[((size_t)b * Nq + i) * C + h * D + e];
-          me = std::max(me, got == got ? fabs(o - got) : 1e30);
-        }
-      }
+  const int rc = pfd_attention_rbias_f16(&p.d, rb, rb_rs, rb_bs, nr, qr.data(), shared ? 0 : Nq, nullptr);
+  // the bound of the unfolded classes, Bmax and T over the table
+  const RefMax m = reference(p, [&](int b, int i) { return rb + b * rb_bs + qr[(size_t)(shared ? 0 : b) * Nq + i] * rb_rs; });
   free(rb);
-  const double bound = (3 * ldexp(1.0, -11) + Nk * ldexp(1.0, -25) + ldexp(1.0, -16) +
-                        2 * 0.6931471805599453 * ((D + 15) / 16 + 1) * ldexp(1.0, -24) * (Bmax + Tmax)) * vmax;
-  const bool ok = rc == 0 && me <= bound;
-  ++g_total;
-  g_fail += !ok;
+  const double bound = bias_bound(Nk, D, false, 0.0, m.Bm + m.T, m.vmax);
+  const bool ok = tally(rc == 0 && m.me <= bound);
   printf("%s attention rbias nr %d %s B%d H%d Nq%d Nk%d D%d  rc %d  max err %.2e = %.3f of the bound (max |ref| %.2f)\n", ok ? "ok  " : "FAIL",
-         nr, shared ? "shared" : "per-sample", B, H, Nq, Nk, D, rc, me, me / bound, mr);
+         nr, shared ? "shared" : "per-sample", B, H, Nq, Nk, D, rc, m.me, m.me / bound, m.mr);
   fflush(stdout);
 }
 
@@ -278,13 +237,7 @@ static void run_case_rbias_disc(int D, int kind) {
   std::vector<uint8_t> qr((size_t)B * Nq);
   for (int b = 0; b < B; ++b)
     for (int i = 0; i < Nq; ++i) qr[(size_t)b * Nq + i] = (uint8_t)(kind == 3 ? (i % 6 >= 3) : kind == 4 ? 1 : i % 2);
-  PfdAttnDesc d;
-  memset(&d, 0, sizeof(d));
-  d.Q = Q.data(); d.K = K.data(); d.Vt = Vt.data(); d.O = O.data();
-  d.ldq = C; d.ldk = C; d.ldo = C; d.ldvt = (long)B * nkp;
-  d.q_bs = (long)Nq * C; d.k_bs = (long)Nk * C; d.o_bs = (long)Nq * C; d.vt_bs = nkp;
-  d.B = B; d.H = H; d.Nq = Nq; d.Nk = Nk; d.D = D;
-  d.scale = scale;
+  PfdAttnDesc d = dense_desc(Q.data(), K.data(), Vt.data(), O.data(), B, H, Nq, Nk, D);
   const int rc = pfd_attention_rbias_f16(&d, rb, rb_rs, rb_bs, nr, qr.data(), Nq, nullptr);
   double me = 0;
   for (int b = 0; b < B && rc == 0; ++b)
@@ -297,15 +250,72 @@ static void run_case_rbias_disc(int D, int kind) {
     }
   free(rb);
   // the bound of the GPU tests with vmax = 1, Bmax = 0 and T = 12 (every live score is 0 or -12)
-  const double bound = 3 * ldexp(1.0, -11) + Nk * ldexp(1.0, -25) + ldexp(1.0, -16) + 2 * 0.6931471805599453 * ((D + 15) / 16 + 1) * ldexp(1.0, -24) * 12.0;
-  const bool ok = rc == 0 && me <= bound;
-  ++g_total;
-  g_fail += !ok;
+  const double bound = bias_bound(Nk, D, false, 0.0, 12.0, 1.0);
+  const bool ok = tally(rc == 0 && me <= bound);
   printf("%s attention rbias mutant-operands kind %d D%d  rc %d  max err %.2e = %.3f of the bound\n", ok ? "ok  " : "FAIL", kind, D, rc, me, me / bound);
   fflush(stdout);
 }
 
+// ---- emu_attn --dispatch FILE: a dry run (emu::dry_run: launches are recorded, nothing executes, no pointer is dereferenced) of
+// the three entry points.  One request per line of FILE: "plain|kbias|rbias B H Nq Nk D [key=value ...]" on dense operands with
+// fake aligned pointers; the keys change one thing each: null=<operand>, misalign=<operand> (Q K Vt O bias qregion), ldk, kb_bs,
+// nr, rb_rs, rb_bs, qr_bs (numbers), scale (a float), slices (PFD_ATTN512_SLICES for this call; unset without the key).
+// One line out per request: the request, "-> <return value>", then the instantiated kernel, grid x and block x of the launch.
+// PFD_ATTN_FORCE8 / PFD_ATTN3_FORCE are read once per process: one run of the probe per setting. ----
+static int dispatch_probe(const char* path) {
+  emu::dry_run = true;
+  FILE* f = fopen(path, "r");
+  if (!f) { fprintf(stderr, "emu_attn: cannot open %s\n", path); return 2; }
+  char line[512], api[16];
+  for (int ln = 1; fgets(line, sizeof(line), f); ++ln) {
+    line[strcspn(line, "\n")] = 0;
+    int B, H, Nq, Nk, D, at = 0;
+    if (sscanf(line, "%15s %d %d %d %d %d%n", api, &B, &H, &Nq, &Nk, &D, &at) != 6) { fprintf(stderr, "emu_attn: %s:%d: not a request\n", path, ln); return 2; }
+    const std::string req = line;
+    uintptr_t ptr[6];   // Q K Vt O bias qregion: 16-byte aligned, never dereferenced
+    for (int i = 0; i < 6; ++i) ptr[i] = (uintptr_t)0x10000 * (i + 1);
+    const char* names[6] = {"Q", "K", "Vt", "O", "bias", "qregion"};
+    PfdAttnDesc d = dense_desc(nullptr, nullptr, nullptr, nullptr, B, H, Nq, Nk, D);
+    long kb_bs = (Nk + 3) / 4 * 4 + 4, rb_rs = kb_bs, rb_bs = -1, qr_bs = Nq, nr = 2;
+    unsetenv("PFD_ATTN512_SLICES");
+    for (char* tok = strtok(line + at, " "); tok; tok = strtok(nullptr, " ")) {
+      char key[16], val[32];
+      if (sscanf(tok, "%15[^=]=%31s", key, val) != 2) { fprintf(stderr, "emu_attn: %s:%d: %s\n", path, ln, tok); return 2; }
+      long* num = !strcmp(key, "kb_bs") ? &kb_bs : !strcmp(key, "rb_rs") ? &rb_rs : !strcmp(key, "rb_bs") ? &rb_bs : !strcmp(key, "qr_bs") ? &qr_bs :
+                  !strcmp(key, "nr") ? &nr : nullptr;
+      int op = 0;
+      while (op < 6 && strcmp(val, names[op])) ++op;
+      if (num) *num = atol(val);
+      else if (!strcmp(key, "ldk")) d.ldk = atol(val);
+      else if (!strcmp(key, "scale")) d.scale = strtof(val, nullptr);
+      else if (!strcmp(key, "slices")) setenv("PFD_ATTN512_SLICES", val, 1);
+      else if (!strcmp(key, "null") && op < 6) ptr[op] = 0;
+      else if (!strcmp(key, "misalign") && op < 6) ptr[op] += 8;
+      else { fprintf(stderr, "emu_attn: %s:%d: %s\n", path, ln, tok); return 2; }
+    }
+    if (rb_bs < 0) rb_bs = nr * rb_rs;
+    d.Q = (const void*)ptr[0]; d.K = (const void*)ptr[1]; d.Vt = (const void*)ptr[2]; d.O = (void*)ptr[3];
+    emu::launch_log.clear();
+    int rc;
+    char sizes[128] = "";   // the operand sizes the request left to the probe
+    if (!strcmp(api, "plain")) rc = pfd_attention_f16(&d, nullptr);
+    else if (!strcmp(api, "kbias")) {
+      snprintf(sizes, sizeof(sizes), " (kb_bs %ld)", kb_bs);
+      rc = pfd_attention_kbias_f16(&d, (const float*)ptr[4], kb_bs, nullptr);
+    } else if (!strcmp(api, "rbias")) {
+      snprintf(sizes, sizeof(sizes), " (nr %ld rb_rs %ld rb_bs %ld qr_bs %ld)", nr, rb_rs, rb_bs, qr_bs);
+      rc = pfd_attention_rbias_f16(&d, (const float*)ptr[4], rb_rs, rb_bs, (int)nr, (const uint8_t*)ptr[5], qr_bs, nullptr);
+    } else { fprintf(stderr, "emu_attn: %s:%d: entry point %s\n", path, ln, api); return 2; }
+    printf("%s%s -> %d", req.c_str(), sizes, rc);
+    for (const auto& l : emu::launch_log) printf(" | %s grid %u block %u", l.kernel.c_str(), l.grid_x, l.block_x);
+    printf("\n");
+  }
+  fclose(f);
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 2 && !strcmp(argv[1], "--dispatch")) return dispatch_probe(argv[2]);
   bool quick = false, force8 = true, kbias = false;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--rbias")) {    // every class pfd_attention_rbias_f16 has: the 4-wave d = 40 form, d = 80, d = 160
